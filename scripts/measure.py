@@ -11,8 +11,8 @@ profiles/rNN/ (scripts/README.md lists which profile came from which step).
 Steps:
   tests[:pytest args]                 GPU suite (one process), log + summary line
   smoke                               __graft_entry__.smoke()
-  bench:NAME[:bench.py args]          bench.py, its JSON line kept as NAME.json
-  trace:NAME[:bench.py args]          rocprofv3 --kernel-trace --stats of bench.py (20 timed replays):
+  bench:NAME[:bench.py args]          bench.py --full, its JSON line kept as NAME.json
+  trace:NAME[:bench.py args]          rocprofv3 --kernel-trace --stats of bench.py --full (20 timed replays):
                                       NAME_kernel_stats.csv, NAME_hot_steps.txt, NAME_step_kernels.txt,
                                       NAME_steady_summary.json
   pmc:NAME:COUNTERS:REGEX[:args]      one rocprofv3 --pmc pass (COUNTERS space-separated, one block's
@@ -93,7 +93,7 @@ def step_smoke(out, _):
 def step_bench(out, spec):
     name, _, extra = spec.partition(":")
     log = os.path.join(out, f"{name}.log")
-    rc = run([PY, "-u", "bench.py"] + bench_args(extra), log, 1000)
+    rc = run([PY, "-u", "bench.py", "--full"] + bench_args(extra), log, 1000)
     last = tail(log, 1).strip()
     if rc == 0 and last.startswith("{"):
         with open(os.path.join(out, f"{name}.json"), "w") as fh:
@@ -110,8 +110,9 @@ def step_trace(out, spec):
     shutil.rmtree(d, ignore_errors=True)
     log = os.path.join(out, f"{name}_trace.log")
     cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "run", "--",
-           PY, "-u", os.path.join(REPO, "bench.py"), "--steps", "20", "--warmup", "3", "--profile-steps", "0",
-           "--cpu-baseline", "0", "--pmc-traffic", "0", "--in-graph-prof", "0"] + bench_args(extra)
+           PY, "-u", os.path.join(REPO, "bench.py"), "--full", "--steps", "20", "--warmup", "3",
+           "--profile-steps", "0", "--cpu-baseline", "0", "--pmc-traffic", "0", "--in-graph-prof", "0"] \
+        + bench_args(extra)
     rc = run(cmd, log, 700, env=prof_env(), cwd="/tmp")
     if rc != 0:
         print(tail(log, 15), flush=True)
@@ -145,7 +146,7 @@ def step_pmc(out, spec):
     log = os.path.join(out, f"{name}_pmc.log")
     cmd = (["timeout", "-s", "KILL", "240", "rocprofv3", "--pmc"] + counters.split()
            + ["--output-format", "csv", "-d", d, "-o", "run", "--", PY, "-u", os.path.join(REPO, "bench.py"),
-              "--steps", "6", "--warmup", "3", "--profile-steps", "0", "--graph", "0", "--cpu-baseline", "0",
+              "--full", "--steps", "6", "--warmup", "3", "--profile-steps", "0", "--graph", "0", "--cpu-baseline", "0",
               "--pmc-traffic", "0", "--in-graph-prof", "0"] + bench_args(extra))
     rc = run(cmd, log, 260, env=prof_env(), cwd="/tmp")
     if rc != 0:

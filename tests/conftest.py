@@ -9,9 +9,41 @@ if REPO not in sys.path:
 
 GOLDEN = os.path.join(REPO, "tests", "golden")
 
+
+
+def _miopen_dirs(repo: str) -> tuple:
+    """bench.miopen_dirs, restated (bench.py stays one file and imports torch; this must run before
+    torch starts): a working copy of the committed MIOpen databases under the git-ignored cache
+    directory, or under a per-user temporary directory where the tree cannot be written."""
+    import hashlib
+    import shutil
+    import tempfile
+    src = os.path.join(repo, "tuning", "miopen", "db")
+    in_tree = os.path.join(repo, "tuning", "miopen", "cache")
+    tag = hashlib.sha1(os.path.abspath(repo).encode()).hexdigest()[:10]
+    for cache in (in_tree, os.path.join(tempfile.gettempdir(), f"lss_miopen_{os.getuid()}_{tag}")):
+        db = os.path.join(cache, "db")
+        try:
+            os.makedirs(db, mode=0o700, exist_ok=True)
+            if not os.access(db, os.W_OK):
+                raise PermissionError(db)
+            for name in os.listdir(src):
+                s, d = os.path.join(src, name), os.path.join(db, name)
+                if not os.path.exists(d) or os.path.getmtime(s) > os.path.getmtime(d):
+                    tmp = f"{d}.{os.getpid()}.tmp"
+                    shutil.copyfile(s, tmp)
+                    os.replace(tmp, d)
+            return db, cache
+        except OSError:
+            continue
+    return src, in_tree
+
+
 # MIOpen find results kept in-tree (as bench.py uses them): the conv tests skip the exhaustive search
-os.environ.setdefault("MIOPEN_USER_DB_PATH", os.path.join(REPO, "tuning", "miopen", "db"))
-os.environ.setdefault("MIOPEN_CUSTOM_CACHE_DIR", os.path.join(REPO, "tuning", "miopen", "cache"))
+if "MIOPEN_USER_DB_PATH" not in os.environ or "MIOPEN_CUSTOM_CACHE_DIR" not in os.environ:
+    _db, _cache = _miopen_dirs(REPO)
+    os.environ.setdefault("MIOPEN_USER_DB_PATH", _db)
+    os.environ.setdefault("MIOPEN_CUSTOM_CACHE_DIR", _cache)
 
 
 def pytest_configure(config):

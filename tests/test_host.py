@@ -144,6 +144,140 @@ def test_bench_gpus_flag_launches_one_rank_per_gpu(monkeypatch):
     assert args.config == "c3" and args.batch == 8 and args.mode == "train" and args.bev_layout == "nhwc"
 
 
+def _load_bench():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("_bench", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_bench_plain_run_measures_the_headline_only(monkeypatch):
+    """Without --full every extra measurement is off (roofline child runs, profile steps, CPU baseline,
+    MIOpen's per-process find); --full restores today's defaults, and explicit switches still apply."""
+    import sys as _sys
+    bench = _load_bench()
+    monkeypatch.setattr(_sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, "")
+    assert (a.profile_steps, a.in_graph_prof, a.pmc_traffic, a.cpu_baseline, a.miopen_find) == (0, 0, 0, 0, 0)
+    monkeypatch.setattr(_sys, "argv", ["bench.py", "--full"])
+    a = bench.parse()
+    assert (a.profile_steps, a.in_graph_prof, a.pmc_traffic, a.cpu_baseline, a.miopen_find) == (20, 1, 1, 1, 1)
+    monkeypatch.setattr(_sys, "argv", ["bench.py", "--full", "--cpu-baseline", "0", "--miopen-find", "0",
+                                       "--dump-outputs", "d"])
+    a = bench.parse()
+    assert (a.cpu_baseline, a.miopen_find, a.pmc_traffic, a.dump_outputs) == (0, 0, 1, "d")
+    monkeypatch.setattr(_sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def test_bench_dump_outputs_arrays(tmp_path, monkeypatch):
+    """--dump-outputs: float32 arrays of the step's value and of the gradients in the optimizer's order (not
+    the updated parameters); an array over the cap is the same seeded sample on every call."""
+    import torch
+    bench = _load_bench()
+
+    class Step:  # what collect_outputs reads of a captured train_step.TrainStep
+        params = [torch.arange(6, dtype=torch.float64).reshape(2, 3), torch.full((4,), 7.0)]
+        graph_grads = [torch.ones(2, 3), torch.arange(4.0)]
+
+    arrays = bench.collect_outputs(Step(), torch.tensor(0.25, dtype=torch.bfloat16), "train")
+    assert sorted(arrays) == ["grads", "loss"] and all(a.dtype == np.float32 for a in arrays.values())
+    assert arrays["loss"].shape == () and float(arrays["loss"]) == 0.25
+    assert arrays["grads"].tolist() == [1, 1, 1, 1, 1, 1, 0, 1, 2, 3]
+    Step.graph_grads = None  # eager: the parameters' own .grad, zeros where a parameter has none
+    Step.params[0].grad = torch.full((2, 3), 2.0, dtype=torch.float64)
+    assert bench.collect_outputs(Step(), torch.tensor(0.0), "train")["grads"].tolist() == [2] * 6 + [0] * 4
+    fwd = bench.collect_outputs(bench.FwdStep(None, ()), torch.ones(2, 1, 3, 3), "fwd")
+    assert list(fwd) == ["preds"] and fwd["preds"].shape == (2, 1, 3, 3)
+
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 5)
+    Step.params = [torch.arange(100.0)]
+    Step.graph_grads = [torch.arange(100.0) * 2]
+    a, b = (bench.collect_outputs(Step(), torch.tensor(0.0), "train") for _ in range(2))
+    assert a["grads"].shape == (5,) and np.array_equal(a["grads"], b["grads"])
+    assert len(set(a["grads"].tolist())) > 1 and all(g % 2 == 0 and 0 <= g < 200 for g in a["grads"].tolist())
+    bench.write_outputs(a, str(tmp_path / "out"))
+    assert sorted(os.listdir(tmp_path / "out")) == ["grads.npy", "loss.npy"]
+    assert np.array_equal(np.load(tmp_path / "out" / "grads.npy"), a["grads"])
+
+
+def test_bench_dumped_step_starts_from_the_initial_state():
+    """restore_initial: parameters, Adam state (in place: same tensors) and the generators as at the
+    start, so the step after it repeats the run's first step bit for bit (CPU: no atomics)."""
+    import torch
+    from lss_carla_amd.train_step import TrainStep
+    bench = _load_bench()
+    torch.manual_seed(3)
+    net = torch.nn.Sequential(torch.nn.Linear(5, 7), torch.nn.Dropout(0.5), torch.nn.Linear(7, 1))
+    params = list(net.parameters())
+    opt = torch.optim.Adam(params, lr=1e-2, weight_decay=1e-7)
+    x, y = torch.randn(4, 5), torch.randn(4, 1)
+    step = TrainStep(net, (x,), y, torch.nn.functional.mse_loss, opt, params, amp_dtype=None)
+    assert bench.step_params(step) == params and bench.step_params(bench.FwdStep(net, (x,))) == []
+    snap = [p.detach().clone() for p in params]
+    torch.manual_seed(11)
+    first = step().detach().clone()
+    g1, p1 = [p.grad.clone() for p in params], [p.detach().clone() for p in params]
+    for _ in range(3):
+        step()
+    state_ids = [id(v) for st in opt.state.values() for v in st.values()]
+    bench.restore_initial(step, snap, 11)
+    assert all(torch.equal(p, s) for p, s in zip(params, snap))
+    assert state_ids == [id(v) for st in opt.state.values() for v in st.values()]
+    assert all(float(torch.as_tensor(v).abs().max()) == 0 for st in opt.state.values() for v in st.values())
+    again = step()
+    assert torch.equal(again, first) and all(torch.equal(p.grad, g) for p, g in zip(params, g1))
+    assert all(torch.equal(p, q) for p, q in zip(params, p1))  # the fresh Adam state gives the first update
+
+
+def test_bench_keeps_the_committed_miopen_databases(tmp_path):
+    """MIOpen gets a working copy of tuning/miopen/db: same content, refreshed when the source is newer."""
+    bench = _load_bench()
+    src = tmp_path / "tuning" / "miopen" / "db"
+    src.mkdir(parents=True)
+    (src / "a.udb.txt").write_text("one\n")
+    db, cache = bench.miopen_dirs(str(tmp_path))
+    assert db == os.path.join(cache, "db") and open(os.path.join(db, "a.udb.txt")).read() == "one\n"
+    with open(os.path.join(db, "a.udb.txt"), "a") as fh:  # MIOpen appends to its copy: kept, source untouched
+        fh.write("two\n")
+    bench.miopen_dirs(str(tmp_path))
+    assert open(os.path.join(db, "a.udb.txt")).read() == "one\ntwo\n" and (src / "a.udb.txt").read_text() == "one\n"
+    (src / "a.udb.txt").write_text("three\n")
+    t = os.path.getmtime(os.path.join(db, "a.udb.txt")) + 10
+    os.utime(src / "a.udb.txt", (t, t))
+    bench.miopen_dirs(str(tmp_path))
+    assert open(os.path.join(db, "a.udb.txt")).read() == "three\n"
+
+
+def test_bench_runs_from_a_tree_it_cannot_write(tmp_path, monkeypatch):
+    """Where tuning/miopen/cache cannot be made (a read-only checkout; here: a file is in its place),
+    MIOpen's working copy and kernel cache go to a directory of this user and checkout under the
+    system's temporary directory; the conftest restatement agrees with bench.py."""
+    import tempfile
+    import conftest
+    bench = _load_bench()
+    repo = tmp_path / "ro"
+    (repo / "tuning" / "miopen" / "db").mkdir(parents=True)
+    (repo / "tuning" / "miopen" / "db" / "a.ufdb.txt").write_text("one\n")
+    (repo / "tuning" / "miopen" / "cache").write_text("")
+    (tmp_path / "t").mkdir()
+    monkeypatch.setattr(tempfile, "tempdir", str(tmp_path / "t"))
+    db, cache = bench.miopen_dirs(str(repo))
+    assert cache.startswith(str(tmp_path / "t") + os.sep) and db == os.path.join(cache, "db")
+    assert open(os.path.join(db, "a.ufdb.txt")).read() == "one\n"
+    assert conftest._miopen_dirs(str(repo)) == (db, cache)
+    os.rename(repo, tmp_path / "ro2")  # another checkout, another directory
+    repo = tmp_path / "ro2"
+    cache2 = bench.miopen_dirs(str(repo))[1]
+    assert cache2 != cache and cache2.startswith(str(tmp_path / "t") + os.sep)
+    monkeypatch.setattr(tempfile, "tempdir", str(repo / "tuning" / "miopen" / "cache" / "x"))  # nowhere to write
+    assert bench.miopen_dirs(str(repo)) == (str(repo / "tuning" / "miopen" / "db"),
+                                            str(repo / "tuning" / "miopen" / "cache"))
+
+
 def test_hip_adam_only_for_plain_cuda_adam():
     """optim.supported: the lss_clip_adam path is never taken for CPU tensors or other optimizers."""
     import torch

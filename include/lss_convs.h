@@ -131,6 +131,21 @@ int64_t lss_bce_partials(int64_t n);
  * in device memory), computed in fp32 and rounded once to dtype; grad and dx 16-B aligned. */
 int lss_bce_logits_bwd(const void* grad, int32_t dtype, int64_t n, const float* grad_loss, void* dx, void* stream);
 
+/* Validation metrics of one batch (get_val_info, src/tools.py:243-270), over the first n_valid[0] samples
+ * only (n_valid: one int32 in device memory, clamped to [0, batch]; NULL = batch), accumulated:
+ *   totals[0] += sum of l(x, t) / per_sample   (l: lss_bce_logits's per-element fp32 term; this is the
+ *                                               batch's mean loss times its valid sample count)
+ *   totals[1] += #(x > 0 and t != 0),  totals[2] += #(x > 0 or t != 0)
+ * x: batch * per_sample logits of dtype (fp32 or bf16), target: as many fp32; per_sample need not be a
+ * multiple of anything (the mask is per element); 16-byte loads are used when both are 16-B aligned.
+ * totals: 3 doubles in device memory; partial: lss_bce_iou_partial_bytes(batch * per_sample) bytes of
+ * 8-B aligned scratch. Per-element arithmetic fp32, sums fp64 and counts integer in a fixed order: two
+ * launches (block records, a one-block fold), no atomics, no host read; graph-capturable, and one captured
+ * launch serves any n_valid. */
+int lss_bce_iou_accum(const void* x, int32_t dtype, const float* target, int64_t per_sample, int32_t batch,
+                      const int32_t* n_valid, float pos_weight, double* totals, void* partial, void* stream);
+int64_t lss_bce_iou_partial_bytes(int64_t n);
+
 /* out[c] = sum over (n, pixel) of x[n][c][pixel] (fp32, fixed order), x (N, C, HW) NCHW fp32 or bf16: the
  * bias gradient of the fused lift's depthnet conv (src/models.py:47) from d(logits). One launch. */
 int lss_channel_sums(const void* x, int32_t dtype, int32_t N, int32_t C, int32_t HW, float* out, void* stream);
@@ -147,6 +162,17 @@ int lss_clip_adam_partials(void);
 int lss_clip_adam(int32_t count, float* const* params, const float* const* grads, float* const* exp_avg,
                   float* const* exp_avg_sq, float* const* step, const int64_t* numel, float max_norm, float lr,
                   float beta1, float beta2, float eps, float weight_decay, float* partial, void* stream);
+/* lss_clip_adam that survives a non-finite gradient. When the gradient norm is finite it computes exactly
+ * what lss_clip_adam computes, bit for bit. When it is not (a NaN or an infinity among the gradients, or a
+ * sum of squares that overflows), nothing is written -- parameters, exp_avg, exp_avg_sq and every step
+ * count keep their bits -- and skipped[0] (one int32 in device memory) is advanced by one. Every block
+ * folds the same partials in the same order, so the decision is the same everywhere. Three launches (the
+ * third, one block, advances the step counts or the skip counter), no host synchronisation
+ * (graph-capturable); deterministic. */
+int lss_clip_adam_guarded(int32_t count, float* const* params, const float* const* grads, float* const* exp_avg,
+                          float* const* exp_avg_sq, float* const* step, const int64_t* numel, float max_norm,
+                          float lr, float beta1, float beta2, float eps, float weight_decay, float* partial,
+                          int32_t* skipped, void* stream);
 
 /* Training-mode batch norm fused with an activation (and, for ReLU, a residual add), for
  * nn.BatchNorm2d followed by swish (EfficientNet-B0, src/models.py:68 and the MBConv blocks) or

@@ -15,7 +15,8 @@ _LAZY = {
     "compile_model": "models", "LiftSplatShoot": "models", "CamEncode": "models",
     "BevEncode": "models", "Up": "models",
     "gen_dx_bx": "tools", "SimpleLoss": "tools", "get_batch_iou": "tools", "get_batch_iou_device": "tools",
-    "get_val_info": "tools", "QuickCumsum": "tools", "cumsum_trick": "tools",
+    "get_val_info": "tools", "val_accumulate": "tools",
+    "train": "trainer", "BatchStager": "staging", "EvalStep": "train_step", "QuickCumsum": "tools", "cumsum_trick": "tools",
 }
 
 

@@ -1869,6 +1869,118 @@ __global__ __launch_bounds__(kWave) void k_bce_total(const float* __restrict__ p
     for (int o = kWave / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, kWave);
     if (threadIdx.x == 0) loss[0] = s * inv_n;
 }
+
+// ---- Validation metrics (get_val_info, src/tools.py:243-270) over the first n_valid samples of a batch,
+// one pass: per element the loss term of k_bce_fwd (the same fp32 expression) and the two IoU predicates.
+// The valid samples are the leading `limit = n_valid * per_sample` elements, so the mask is per element:
+// i < limit. Thread = 8 consecutive elements; the loss terms are summed in fp64 and the counts in integers,
+// in a fixed order (lane, wave butterfly, the 4 waves in order) into one record per block; k_bce_iou_fold
+// (one block) folds the records in block order and adds to totals[3].
+struct BceIouPartial {
+    double loss;
+    long long inter, uni;
+};
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_bce_iou(const T* __restrict__ x, const float* __restrict__ t,
+                                                    long long per_sample, int batch, const int* __restrict__ n_valid,
+                                                    float pw, int vec, BceIouPartial* __restrict__ partial) {
+    __shared__ double s_l[kBlock / kWave];
+    __shared__ int s_i[kBlock / kWave], s_u[kBlock / kWave];
+    int nv = n_valid ? n_valid[0] : batch;
+    nv = nv < 0 ? 0 : (nv > batch ? batch : nv);
+    const long long limit = (long long)nv * per_sample;
+    const long long i0 = ((long long)blockIdx.x * kBlock + threadIdx.x) * kBceVpt;
+    double s = 0.0;
+    int ni = 0, nu = 0;
+    if (i0 < limit) {
+        float xv[kBceVpt], tv[kBceVpt];
+        if (vec && i0 + kBceVpt <= limit) {
+            ldv8(x + i0, xv);
+            const float4 a = *reinterpret_cast<const float4*>(t + i0), b = *reinterpret_cast<const float4*>(t + i0 + 4);
+            tv[0] = a.x; tv[1] = a.y; tv[2] = a.z; tv[3] = a.w; tv[4] = b.x; tv[5] = b.y; tv[6] = b.z; tv[7] = b.w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < kBceVpt; ++j) {
+                xv[j] = i0 + j < limit ? ld(x + i0 + j) : 0.f;
+                tv[j] = i0 + j < limit ? t[i0 + j] : 0.f;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < kBceVpt; ++j) {
+            const float xx = xv[j], tt = tv[j];
+            const float lw = fmaf(pw - 1.f, tt, 1.f);
+            const float e = expf(-fabsf(xx));
+            const float l = (1.f - tt) * xx + lw * (log1pf(e) + fmaxf(-xx, 0.f));
+            if (i0 + j < limit) {
+                s += (double)l;
+                const bool p = xx > 0.f, q = tt != 0.f;
+                ni += (p && q) ? 1 : 0;
+                nu += (p || q) ? 1 : 0;
+            }
+        }
+    }
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+        s += __shfl_xor(s, o, kWave);
+        ni += __shfl_xor(ni, o, kWave);
+        nu += __shfl_xor(nu, o, kWave);
+    }
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+        s_l[threadIdx.x / kWave] = s;
+        s_i[threadIdx.x / kWave] = ni;
+        s_u[threadIdx.x / kWave] = nu;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        BceIouPartial r{0.0, 0, 0};
+#pragma unroll
+        for (int w = 0; w < kBlock / kWave; ++w) {
+            r.loss += s_l[w];
+            r.inter += s_i[w];
+            r.uni += s_u[w];
+        }
+        partial[blockIdx.x] = r;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_bce_iou_fold(const BceIouPartial* __restrict__ partial, int nb,
+                                                         double per_sample, double* __restrict__ totals) {
+    __shared__ double s_l[kBlock / kWave];
+    __shared__ long long s_i[kBlock / kWave], s_u[kBlock / kWave];
+    double s = 0.0;
+    long long ni = 0, nu = 0;
+    for (int b = threadIdx.x; b < nb; b += kBlock) {
+        const BceIouPartial r = partial[b];
+        s += r.loss;
+        ni += r.inter;
+        nu += r.uni;
+    }
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+        s += __shfl_xor(s, o, kWave);
+        ni += __shfl_xor(ni, o, kWave);
+        nu += __shfl_xor(nu, o, kWave);
+    }
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+        s_l[threadIdx.x / kWave] = s;
+        s_i[threadIdx.x / kWave] = ni;
+        s_u[threadIdx.x / kWave] = nu;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double l = 0.0;
+        long long a = 0, u = 0;
+#pragma unroll
+        for (int w = 0; w < kBlock / kWave; ++w) {
+            l += s_l[w];
+            a += s_i[w];
+            u += s_u[w];
+        }
+        totals[0] += l / per_sample;
+        totals[1] += (double)a;
+        totals[2] += (double)u;
+    }
+}
 }  // namespace
 
 extern "C" {
@@ -2228,6 +2340,36 @@ int lss_channel_sums(const void* x, int32_t dtype, int32_t N, int32_t C, int32_t
         hipLaunchKernelGGL(k_channel_sums<bf16>, dim3(C), dim3(kBlock), 0, s, (const bf16*)x, N, C, HW, out);
     else
         hipLaunchKernelGGL(k_channel_sums<float>, dim3(C), dim3(kBlock), 0, s, (const float*)x, N, C, HW, out);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+int64_t lss_bce_iou_partial_bytes(int64_t n) {
+    return n <= 0 ? 0 : lss_bce_partials(n) * (int64_t)sizeof(BceIouPartial);
+}
+
+int lss_bce_iou_accum(const void* x, int32_t dtype, const float* target, int64_t per_sample, int32_t batch,
+                      const int32_t* n_valid, float pos_weight, double* totals, void* partial, void* stream) {
+    const int esz = dtype == LSS_CONV_BF16 ? 2 : dtype == LSS_CONV_F32 ? 4 : 0;
+    if (!x || !target || !totals || !partial || !esz || per_sample <= 0 || batch <= 0 ||
+        per_sample > LLONG_MAX / batch || (reinterpret_cast<uintptr_t>(partial) & 7) ||
+        (reinterpret_cast<uintptr_t>(totals) & 7))
+        return LSS_CONV_EINVAL;
+    const long long n = (long long)per_sample * batch;
+    const long long nb = (n + (long long)kBlock * kBceVpt - 1) / ((long long)kBlock * kBceVpt);
+    if (nb > INT_MAX) return LSS_CONV_EINVAL;
+    // 16-byte loads only from 16-byte aligned bases (a thread's first element is a multiple of 8)
+    const int vec = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(target)) & 15) == 0;
+    hipStream_t s = (hipStream_t)stream;
+    BceIouPartial* pp = (BceIouPartial*)partial;
+    if (esz == 2)
+        hipLaunchKernelGGL(k_bce_iou<bf16>, dim3((unsigned)nb), dim3(kBlock), 0, s, (const bf16*)x, target,
+                           (long long)per_sample, (int)batch, (const int*)n_valid, pos_weight, vec, pp);
+    else
+        hipLaunchKernelGGL(k_bce_iou<float>, dim3((unsigned)nb), dim3(kBlock), 0, s, (const float*)x, target,
+                           (long long)per_sample, (int)batch, (const int*)n_valid, pos_weight, vec, pp);
+    hipLaunchKernelGGL(k_bce_iou_fold, dim3(1), dim3(kBlock), 0, s, (const BceIouPartial*)pp, (int)nb,
+                       (double)per_sample, totals);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
 }

@@ -9,6 +9,9 @@
 // torch's path runs a foreach norm, about eight scalar kernels, a foreach multiply of every gradient and the
 // fused Adam kernel: the gradients are read three times and written once; here they are read twice.
 // The clipped gradient itself is not written back (nothing reads it after the step).
+// lss_clip_adam_guarded: the same update unless the norm is a NaN or an infinity; then pass 2 returns before
+// writing anything and a third, one-block launch counts the skipped step instead of advancing the step counts
+// (they cannot be advanced in pass 1, before the norm is known, nor in pass 2, whose blocks all read them).
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -63,6 +66,9 @@ __device__ __forceinline__ float block_sum(float x, float* s_w) {
     return t;  // every thread
 }
 
+// kGuard (lss_clip_adam_guarded): the step counts are not advanced here but by k_guard_commit, once the
+// norm is known to be finite
+template <bool kGuard>
 __global__ __launch_bounds__(kBlock) void k_clip_sumsq(Segs s, float* __restrict__ partial) {
     __shared__ float s_w[kBlock / kWave];
     long long lo, hi;
@@ -87,7 +93,17 @@ __global__ __launch_bounds__(kBlock) void k_clip_sumsq(Segs s, float* __restrict
     });
     const float t = block_sum(acc, s_w);
     if (threadIdx.x == 0) partial[blockIdx.x] = t;
-    if (blockIdx.x == 0 && (int)threadIdx.x < s.count) s.step[threadIdx.x][0] += 1.f;
+    if (!kGuard && blockIdx.x == 0 && (int)threadIdx.x < s.count) s.step[threadIdx.x][0] += 1.f;
+}
+
+// a NaN or an infinity (tested on the bits)
+__device__ __forceinline__ bool non_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+
+// the squared gradient norm from the partials; the same order in every block of every kernel that folds them
+__device__ __forceinline__ float fold_partials(const float* __restrict__ partial, int npartial, float* s_w) {
+    float acc = 0.f;
+    for (int i = threadIdx.x; i < npartial; i += kBlock) acc += partial[i];
+    return block_sum(acc, s_w);
 }
 
 __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, float c, float wd, float b1, float b2,
@@ -98,13 +114,13 @@ __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, 
     p -= step_size * m / (sqrtf(v) / bc2_sqrt + eps);
 }
 
+template <bool kGuard>
 __global__ __launch_bounds__(kBlock) void k_clip_adam(Segs s, const float* __restrict__ partial, int npartial,
                                                       float max_norm, float lr, float b1, float b2, float eps,
                                                       float wd) {
     __shared__ float s_w[kBlock / kWave];
-    float acc = 0.f;
-    for (int i = threadIdx.x; i < npartial; i += kBlock) acc += partial[i];
-    const float norm = sqrtf(block_sum(acc, s_w));
+    const float norm = sqrtf(fold_partials(partial, npartial, s_w));
+    if (kGuard && non_finite(norm)) return;  // uniform over the grid: no block writes anything
     // clip_coef.clamp(max=1) as torch computes it: a NaN / inf norm passes through (fminf would return
     // 1 for a NaN and leave the step unclipped), so every parameter goes non-finite as with torch
     const float q = max_norm / (norm + 1e-6f);
@@ -112,7 +128,7 @@ __global__ __launch_bounds__(kBlock) void k_clip_adam(Segs s, const float* __res
     long long lo, hi;
     block_range(s.start[s.count], lo, hi);
     for_segments(s, lo, hi, [&](int k, long long a, long long b) {
-        const float t = s.step[k][0];
+        const float t = kGuard ? s.step[k][0] + 1.f : s.step[k][0];  // (guarded: advanced after this kernel)
         const float step_size = lr / (1.f - powf(b1, t));
         const float bc2_sqrt = sqrtf(1.f - powf(b2, t));
         float* p = s.p[k];
@@ -143,6 +159,23 @@ __global__ __launch_bounds__(kBlock) void k_clip_adam(Segs s, const float* __res
     });
 }
 
+// After a guarded update (one block): advance every step count, or count the skipped step.
+__global__ __launch_bounds__(kBlock) void k_guard_commit(Segs s, const float* __restrict__ partial, int npartial,
+                                                         int* __restrict__ skipped) {
+    __shared__ float s_w[kBlock / kWave];
+    const float norm = sqrtf(fold_partials(partial, npartial, s_w));
+    if (non_finite(norm)) {
+        if (threadIdx.x == 0) skipped[0] += 1;
+    } else if ((int)threadIdx.x < s.count) {
+        s.step[threadIdx.x][0] += 1.f;
+    }
+}
+
+int clip_adam(int32_t count, float* const* params, const float* const* grads, float* const* exp_avg,
+              float* const* exp_avg_sq, float* const* step, const int64_t* numel, float max_norm, float lr,
+              float beta1, float beta2, float eps, float weight_decay, float* partial, int32_t* skipped,
+              void* stream);
+
 }  // namespace
 
 extern "C" {
@@ -152,6 +185,28 @@ int lss_clip_adam_partials(void) { return kMaxBlocks; }
 int lss_clip_adam(int32_t count, float* const* params, const float* const* grads, float* const* exp_avg,
                   float* const* exp_avg_sq, float* const* step, const int64_t* numel, float max_norm, float lr,
                   float beta1, float beta2, float eps, float weight_decay, float* partial, void* stream) {
+    return clip_adam(count, params, grads, exp_avg, exp_avg_sq, step, numel, max_norm, lr, beta1, beta2, eps,
+                     weight_decay, partial, nullptr, stream);
+}
+
+int lss_clip_adam_guarded(int32_t count, float* const* params, const float* const* grads, float* const* exp_avg,
+                          float* const* exp_avg_sq, float* const* step, const int64_t* numel, float max_norm,
+                          float lr, float beta1, float beta2, float eps, float weight_decay, float* partial,
+                          int32_t* skipped, void* stream) {
+    if (!skipped) return LSS_CONV_EINVAL;
+    return clip_adam(count, params, grads, exp_avg, exp_avg_sq, step, numel, max_norm, lr, beta1, beta2, eps,
+                     weight_decay, partial, skipped, stream);
+}
+
+}  // extern "C"
+
+namespace {
+
+// skipped: NULL = lss_clip_adam, else the guarded update
+int clip_adam(int32_t count, float* const* params, const float* const* grads, float* const* exp_avg,
+              float* const* exp_avg_sq, float* const* step, const int64_t* numel, float max_norm, float lr,
+              float beta1, float beta2, float eps, float weight_decay, float* partial, int32_t* skipped,
+              void* stream) {
     if (count <= 0 || count > LSS_ADAM_MAX_TENSORS || !params || !grads || !exp_avg || !exp_avg_sq || !step ||
         !numel || !partial || !(max_norm > 0.f))
         return LSS_CONV_EINVAL;
@@ -178,11 +233,19 @@ int lss_clip_adam(int32_t count, float* const* params, const float* const* grads
     long long nb2 = (total + kBlock * 8 - 1) / (kBlock * 8);
     nb2 = nb2 < 1 ? 1 : (nb2 > kMaxAdamBlocks ? kMaxAdamBlocks : nb2);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_clip_sumsq, dim3((unsigned)nb), dim3(kBlock), 0, st, s, partial);
-    hipLaunchKernelGGL(k_clip_adam, dim3((unsigned)nb2), dim3(kBlock), 0, st, s, (const float*)partial, (int)nb, max_norm,
-                       lr, beta1, beta2, eps, weight_decay);
+    if (skipped) {
+        hipLaunchKernelGGL(k_clip_sumsq<true>, dim3((unsigned)nb), dim3(kBlock), 0, st, s, partial);
+        hipLaunchKernelGGL(k_clip_adam<true>, dim3((unsigned)nb2), dim3(kBlock), 0, st, s, (const float*)partial,
+                           (int)nb, max_norm, lr, beta1, beta2, eps, weight_decay);
+        hipLaunchKernelGGL(k_guard_commit, dim3(1), dim3(kBlock), 0, st, s, (const float*)partial, (int)nb,
+                           (int*)skipped);
+    } else {
+        hipLaunchKernelGGL(k_clip_sumsq<false>, dim3((unsigned)nb), dim3(kBlock), 0, st, s, partial);
+        hipLaunchKernelGGL(k_clip_adam<false>, dim3((unsigned)nb2), dim3(kBlock), 0, st, s, (const float*)partial,
+                           (int)nb, max_norm, lr, beta1, beta2, eps, weight_decay);
+    }
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
 }
 
-}  // extern "C"
+}  // namespace

@@ -5,7 +5,8 @@
 optimizer's own state tensors (``step``, ``exp_avg``, ``exp_avg_sq``, created as torch creates them), so
 ``opt.state_dict()`` stays what torch would save and either path can continue the other. The gradient
 norm is fp32 over all the tensors' gradients; the gradients themselves are left unclipped (nothing reads
-them after the step). Kernels: ``lss_clip_adam`` (include/lss_convs.h). Anything it does not cover
+them after the step). Kernels: ``lss_clip_adam`` (include/lss_convs.h), or
+``lss_clip_adam_guarded`` when the caller passes a skip counter (a non-finite gradient then skips the step). Anything it does not cover
 (amsgrad, maximize, several parameter groups, tensor learning rates, CPU tensors, other dtypes, an Adam
 that is neither ``capturable`` nor ``fused``, whose ``step`` torch keeps on the host) keeps torch's path
 (``supported``).
@@ -13,7 +14,7 @@ that is neither ``capturable`` nor ``fused``, whose ``step`` torch keeps on the 
 from __future__ import annotations
 
 import ctypes
-from typing import Sequence
+from typing import Optional, Sequence
 
 import torch
 
@@ -61,7 +62,10 @@ class ClipAdam:
             st["step"] = st["step"].to(device=p.device, dtype=torch.float32)
         return st
 
-    def step(self, max_norm: float) -> None:
+    def step(self, max_norm: float, skipped: Optional[torch.Tensor] = None) -> None:
+        """skipped (one int32 on the device): the guarded update, ``lss_clip_adam_guarded`` -- a step whose
+        gradient norm is a NaN or an infinity writes nothing and adds one to it; a finite step is the same
+        update bit for bit. None: torch's behaviour (a non-finite gradient poisons every parameter)."""
         lib = _lib.load()
         g = self.opt.param_groups[0]
         ps = list(g["params"])
@@ -73,6 +77,15 @@ class ClipAdam:
         arr = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])  # noqa: E731
         numel = (ctypes.c_int64 * n)(*[p.numel() for p in ps])
         b1, b2 = g["betas"]
+        if skipped is not None:
+            if not (skipped.is_cuda and skipped.device == dev and skipped.dtype == torch.int32 and skipped.numel() == 1):
+                raise RuntimeError("ClipAdam.step: skipped must be one int32 on the parameters' device")
+            _lib.check(lib.lss_clip_adam_guarded(
+                n, arr(ps), arr([p.grad for p in ps]), arr([s["exp_avg"] for s in sts]),
+                arr([s["exp_avg_sq"] for s in sts]), arr([s["step"] for s in sts]), numel, float(max_norm),
+                float(g["lr"]), float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]),
+                _lib.ptr(self._partial), _lib.ptr(skipped), _lib.stream_handle(dev)), "lss_clip_adam_guarded")
+            return
         _lib.check(lib.lss_clip_adam(n, arr(ps), arr([p.grad for p in ps]), arr([s["exp_avg"] for s in sts]),
                                      arr([s["exp_avg_sq"] for s in sts]), arr([s["step"] for s in sts]), numel,
                                      float(max_norm), float(g["lr"]), float(b1), float(b2), float(g["eps"]),

@@ -153,9 +153,14 @@ def _to_device_pinned(buf: bytes, dev: torch.device) -> torch.Tensor:
 
 
 # ----------------------------------------------------------------------------- device kernels
-def augment_images(imgs_u8: torch.Tensor, augs: Sequence[dict], final_dim: Sequence[int]) -> torch.Tensor:
+def augment_images(imgs_u8: torch.Tensor, augs: Sequence[dict], final_dim: Sequence[int], out=None,
+                   keep=None) -> torch.Tensor:
     """(n, H, W, 3) uint8 device images + one aug dict per image (resize_dims, crop, flip, rotate) ->
-    (n, 3, fH, fW) fp32 = normalize_img(img_transform(img)) (src/tools.py:120-128, 167-171)."""
+    (n, 3, fH, fW) fp32 = normalize_img(img_transform(img)) (src/tools.py:120-128, 167-171).
+
+    out: a contiguous fp32 device tensor of n * 3 * fH * fW elements to write instead of a new one.
+    keep: a list that receives the device tensors allocated here (the parameter block, the table
+    concatenation, the source) -- a caller running this on a side stream holds them until its event."""
     if not imgs_u8.is_cuda:
         raise RuntimeError("lss_carla_amd.simbev: images must be on the MI355X (no CPU fallback)")
     if imgs_u8.dtype != torch.uint8 or imgs_u8.dim() != 4 or imgs_u8.shape[-1] != 3:
@@ -204,14 +209,21 @@ def augment_images(imgs_u8: torch.Tensor, augs: Sequence[dict], final_dim: Seque
         torch.zeros(1, device=dev, dtype=torch.int32)
     par_d = _to_device_pinned(bytes(params), dev)
     src = imgs_u8.contiguous()
-    out = torch.empty(n, 3, fH, fW, device=dev, dtype=torch.float32)
+    if out is None:
+        out = torch.empty(n, 3, fH, fW, device=dev, dtype=torch.float32)
+    elif not (out.is_cuda and out.device == dev and out.dtype == torch.float32 and out.is_contiguous()
+              and out.numel() == n * 3 * fH * fW):
+        raise RuntimeError(f"out= must be a contiguous fp32 device tensor of {(n, 3, fH, fW)}")
+    if keep is not None:
+        keep.extend([par_d, tab_d, src])
     _lib.check(lib.lss_simbev_images(_lib.ptr(src), n, H, W, _lib.ptr(par_d), _lib.ptr(tab_d), fH, fW,
                                      _lib.ptr(out), _lib.stream_handle(dev)), "lss_simbev_images")
     return out
 
 
-def vehicle_masks(bev_u8: torch.Tensor) -> torch.Tensor:
-    """(n, C, X, Y) uint8 device BEV maps -> (n, 1, X, Y) fp32 binimgs (src/data_simbev.py:236-244)."""
+def vehicle_masks(bev_u8: torch.Tensor, out=None) -> torch.Tensor:
+    """(n, C, X, Y) uint8 device BEV maps -> (n, 1, X, Y) fp32 binimgs (src/data_simbev.py:236-244);
+    out: a contiguous fp32 device tensor of n * X * Y elements to write instead of a new one."""
     if not bev_u8.is_cuda:
         raise RuntimeError("lss_carla_amd.simbev: BEV maps must be on the MI355X (no CPU fallback)")
     if bev_u8.dtype == torch.bool:
@@ -219,7 +231,11 @@ def vehicle_masks(bev_u8: torch.Tensor) -> torch.Tensor:
     if bev_u8.dtype != torch.uint8:
         bev_u8 = (bev_u8 > 0).to(torch.uint8)
     n, C, X, Y = bev_u8.shape
-    out = torch.empty(n, 1, X, Y, device=bev_u8.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty(n, 1, X, Y, device=bev_u8.device, dtype=torch.float32)
+    elif not (out.is_cuda and out.device == bev_u8.device and out.dtype == torch.float32 and out.is_contiguous()
+              and out.numel() == n * X * Y):
+        raise RuntimeError(f"out= must be a contiguous fp32 device tensor of {(n, 1, X, Y)}")
     b = bev_u8.contiguous()
     _lib.check(_lib.load().lss_simbev_vehicle_mask(_lib.ptr(b), n, C, X, Y, _lib.ptr(out),
                                                    _lib.stream_handle(b.device)), "lss_simbev_vehicle_mask")

@@ -144,3 +144,56 @@ def make_images(B: int, N: int, final_dim: Sequence[int], seed: int = 0) -> torc
 def make_labels(B: int, X: int, Y: int, seed: int = 0) -> torch.Tensor:
     g = torch.Generator().manual_seed(seed + 2)
     return (torch.rand((B, 1, X, Y), generator=g) < 0.03).to(torch.float32)
+
+
+def make_simbev_tree(root, n_scenes: int, per_scene: int, H: int = IMG_H, W: int = IMG_W, seed: int = 0,
+                     n_classes: int = 8, X: int = 200, Y: int = 200, quality: int = 90) -> int:
+    """Write a synthetic dataset with SimBEV's layout (src/data_simbev.py:40-75) under ``root``:
+    ``SimBEV_cvt_label/scene_XXXX/yaw0pitch0/meta.json`` (per sample: six JPEG paths, the §8d rig's
+    intrinsics / 4x4 extrinsics, the BEV file) + ``bev_*.npz`` ((n_classes, X, Y) uint8 under "bev", a few
+    vehicle boxes in classes 1-3), and ``sweeps/RGB-CAM_*/`` H x W JPEGs of smooth random content (so a
+    decode costs what a photograph's does). The loader's 80/20 scene split applies. Returns the sample count."""
+    import json
+    import os
+
+    import numpy as np
+    from PIL import Image
+
+    from .simbev import CAMERA_ORDER
+
+    rng = np.random.default_rng(seed)
+    rig = make_rig(1, 6, (H, W), seed=seed)
+    extr = np.tile(np.eye(4), (6, 1, 1))
+    extr[:, :3, :3] = rig["rots"][0].double().numpy()
+    extr[:, :3, 3] = rig["trans"][0].double().numpy()
+    fx = W / (2.0 * math.tan(math.radians(HFOV_DEG / 2.0)))
+    K = [[fx, 0.0, W / 2.0], [0.0, fx, H / 2.0], [0.0, 0.0, 1.0]]
+    cams = [f"RGB-CAM_{c.upper()}" for c in CAMERA_ORDER]
+    for c in cams:
+        os.makedirs(os.path.join(root, "sweeps", c), exist_ok=True)
+    n = 0
+    for s in range(n_scenes):
+        d = os.path.join(root, "SimBEV_cvt_label", f"scene_{s:04d}", "yaw0pitch0")
+        os.makedirs(d, exist_ok=True)
+        meta = []
+        for k in range(per_scene):
+            tok = f"s{s}_{k}"
+            paths = []
+            for c in cams:
+                low = rng.integers(0, 256, size=(H // 8 + 1, W // 8 + 1, 3), dtype=np.uint8)
+                img = Image.fromarray(low).resize((W, H), Image.BILINEAR)
+                rel = f"sweeps/{c}/{tok}.jpg"
+                img.save(os.path.join(root, rel), quality=quality)
+                paths.append(rel)
+            bev = np.zeros((n_classes, X, Y), dtype=np.uint8)
+            for _ in range(12):
+                cls = int(rng.integers(1, 4))
+                x0, y0 = int(rng.integers(0, X - 10)), int(rng.integers(0, Y - 5))
+                bev[cls, x0:x0 + 9, y0:y0 + 4] = 1
+            np.savez_compressed(os.path.join(d, f"bev_{tok}.npz"), bev=bev)
+            meta.append({"token": tok, "images": paths, "intrinsics": [K] * 6, "extrinsics": extr.tolist(),
+                         "bev": f"bev_{tok}.npz"})
+            n += 1
+        with open(os.path.join(d, "meta.json"), "w") as fh:
+            json.dump(meta, fh)
+    return n

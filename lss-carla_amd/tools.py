@@ -139,6 +139,41 @@ def get_batch_iou_device(preds: torch.Tensor, binimgs: torch.Tensor):
         return (pred & tgt).sum().float(), (pred | tgt).sum().float()
 
 
+_VAL_PARTIAL = {}
+
+
+def val_accumulate(preds: torch.Tensor, binimgs: torch.Tensor, totals: torch.Tensor, n_valid=None,
+                   pos_weight: float = 2.13) -> torch.Tensor:
+    """One validation batch into get_val_info's accumulators, ``lss_bce_iou_accum`` (include/lss_convs.h):
+    totals (3 float64 on the device) += (mean loss x samples, intersection, union) over the first
+    ``n_valid`` samples (one int32 on the device, read there; None: all of them). preds: fp32 or bf16
+    logits, binimgs: fp32 labels of the same shape. Two launches, no host synchronisation, capturable
+    (the scratch is kept per device and size: one stream at a time)."""
+    from . import _lib
+    if not (preds.is_cuda and binimgs.device == preds.device and totals.device == preds.device):
+        raise RuntimeError("val_accumulate: device tensors only (no CPU fallback)")
+    if (binimgs.dtype != torch.float32 or binimgs.shape != preds.shape or totals.dtype != torch.float64
+            or totals.numel() != 3 or not totals.is_contiguous() or preds.dim() < 1 or preds.numel() == 0):
+        raise RuntimeError(f"val_accumulate: preds {tuple(preds.shape)} {preds.dtype}, labels {tuple(binimgs.shape)} "
+                           f"{binimgs.dtype}, totals {tuple(totals.shape)} {totals.dtype}")
+    if n_valid is not None and not (n_valid.device == preds.device and n_valid.dtype == torch.int32
+                                    and n_valid.numel() == 1):
+        raise RuntimeError("val_accumulate: n_valid must be one int32 on the logits' device")
+    lib = _lib.load()
+    x, t = preds.detach().contiguous(), binimgs.contiguous()
+    batch = x.shape[0]
+    per_sample = x.numel() // batch
+    nbytes = int(lib.lss_bce_iou_partial_bytes(x.numel()))
+    key = (x.device, nbytes)
+    partial = _VAL_PARTIAL.get(key)
+    if partial is None:
+        partial = _VAL_PARTIAL[key] = torch.empty(nbytes // 8, device=x.device, dtype=torch.float64)
+    _lib.check(lib.lss_bce_iou_accum(_lib.ptr(x), _lib.dtype_code(x.dtype), _lib.ptr(t), per_sample, batch,
+                                     _lib.ptr(n_valid), float(pos_weight), _lib.ptr(totals), _lib.ptr(partial),
+                                     _lib.stream_handle(x.device)), "lss_bce_iou_accum")
+    return totals
+
+
 def val_totals(model, loader, loss_fn, device):
     """The device accumulators of get_val_info: (sum of loss x batch size, intersection, union) as
     float64 device tensors; nothing in the loop synchronises the host."""

@@ -41,11 +41,16 @@ class TrainStep:
                  loss_fn: Callable, opt: torch.optim.Optimizer, params: Sequence[torch.Tensor],
                  all_reduce: bool = False, amp_dtype: Optional[torch.dtype] = torch.bfloat16,
                  max_grad_norm: float = 5.0, pre_step: Optional[Callable[[], None]] = None,
-                 overlap_all_reduce: bool = False, force_collectives: bool = False):
+                 overlap_all_reduce: bool = False, force_collectives: bool = False,
+                 skip_nonfinite: bool = False, keep_preds: bool = False):
         """overlap_all_reduce: all-reduce each parameter's gradient (e.g. each FlatParamGroups
         master) from its post-accumulate hook, on a side stream, while the backward continues -- inside
         the captured graph too; the step waits for them before the update. force_collectives: issue
-        the collectives even at world size 1 (tests of the captured path on one GPU)."""
+        the collectives even at world size 1 (tests of the captured path on one GPU). skip_nonfinite: a
+        step whose gradient norm is a NaN or an infinity leaves parameters and optimizer state untouched
+        and is counted in ``self.skipped`` (one int32 on the device; needs the HIP update, optim.supported).
+        keep_preds: keep the step's detached logits as ``self.static_preds`` (captured: a static tensor
+        every replay rewrites), for the caller's training IoU."""
         self.forward, self.inputs, self.labels = forward, tuple(inputs), labels
         # host work staged into the step's static device inputs before each step is launched
         # (e.g. ops.HostInverses.update: the reference's host torch.inverse of the rig)
@@ -64,6 +69,8 @@ class TrainStep:
         self.graphs = None
         self.graph_grads = None
         self.static_loss = None
+        self.keep_preds, self.static_preds = bool(keep_preds), None
+        self.skipped = torch.zeros(1, device=labels.device, dtype=torch.int32) if skip_nonfinite else None
 
     @property
     def captured(self) -> bool:
@@ -77,6 +84,8 @@ class TrainStep:
         with torch.autocast(dev_type, dtype=self.amp_dtype or torch.bfloat16, enabled=self.amp_dtype is not None,
                             cache_enabled=not capturing):
             preds = self.forward(*self.inputs)
+        if self.keep_preds:
+            self.static_preds = preds.detach()
         # (a loss that computes in fp32 itself, tools.SimpleLoss, takes the bf16 logits: no cast kernels)
         loss = self.loss_fn(preds if getattr(self.loss_fn, "computes_in_fp32", False) else preds.float(), self.labels)
         loss.backward()
@@ -118,8 +127,11 @@ class TrainStep:
         if optim.supported(self.opt, self.params):  # both in two launches on the GPU (lss_clip_adam)
             if getattr(self, "_clip_adam", None) is None or self._clip_adam.opt is not self.opt:
                 self._clip_adam = optim.ClipAdam(self.opt)
-            self._clip_adam.step(self.max_grad_norm)
+            self._clip_adam.step(self.max_grad_norm, skipped=self.skipped)
             return
+        if self.skipped is not None:
+            raise RuntimeError("TrainStep(skip_nonfinite=True) needs the HIP update (a fused / capturable "
+                               "torch.optim.Adam over fp32 device tensors, optim.supported)")
         torch.nn.utils.clip_grad_norm_(self.params, self.max_grad_norm)
         self.opt.step()
 
@@ -131,9 +143,12 @@ class TrainStep:
         self.update()
         return loss
 
-    def capture(self, warmup: int = 2, on_warmup: Optional[Callable[[int], None]] = None) -> None:
+    def capture(self, warmup: int = 2, on_warmup: Optional[Callable[[int], None]] = None,
+                error_mode: Optional[str] = None) -> None:
         """`warmup` eager steps on a side stream (MIOpen find, optimizer state, allocator), then
-        capture (the optimizer must be built with capturable=True)."""
+        capture (the optimizer must be built with capturable=True). error_mode: the capture's
+        capture_error_mode ("thread_local" when other threads of the process use the runtime meanwhile,
+        e.g. a DataLoader's pinning thread); None: "global", or "thread_local" with collectives."""
         dev = self.labels.device
         side = torch.cuda.Stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))
@@ -152,6 +167,7 @@ class TrainStep:
             # Let it reap the completed works, and restrict the capture's checks to this thread.
             time.sleep(0.5)
             mode = "thread_local"
+        mode = error_mode or mode
         g_fb, g_up = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         with torch.cuda.graph(g_fb, capture_error_mode=mode):
             # detached: holding the captured autograd graph would keep its AccumulateGrad nodes
@@ -173,3 +189,79 @@ class TrainStep:
         self.all_reduce(self.graph_grads)
         g_up.replay()
         return self.static_loss
+
+
+class EvalStep:
+    """The validation step of get_val_info (src/tools.py:243-270) over static inputs: forward only, the
+    model in eval mode, no_grad, the training step's autocast dtype, then ``tools.val_accumulate`` into
+    ``totals`` (3 float64 on the device: loss x samples, intersection, union) -- eager, or one HIP graph.
+
+    forward: the callable the training step runs (e.g. ``FlatParams.bind(model)``: every call, and every
+    replay, materialises the current masters). n_valid (one int32 on the device, e.g.
+    ``BatchStager.n_valid``): how many leading samples of the static batch count; it is read on the
+    device, so one graph serves full and partial batches. The training graphs are not affected by the
+    module's mode flag: a captured graph replays the kernels it recorded."""
+
+    def __init__(self, model: torch.nn.Module, forward: Callable[..., torch.Tensor], inputs: Sequence[torch.Tensor],
+                 labels: torch.Tensor, n_valid: Optional[torch.Tensor] = None, pos_weight: float = 2.13,
+                 amp_dtype: Optional[torch.dtype] = torch.bfloat16, n_samples: Optional[int] = None):
+        self.model, self.forward, self.inputs, self.labels = model, forward, tuple(inputs), labels
+        self.n_samples = n_samples  # len(valloader.dataset): what read() divides the loss total by
+        self.n_valid, self.pos_weight, self.amp_dtype = n_valid, float(pos_weight), amp_dtype
+        self.totals = torch.zeros(3, device=labels.device, dtype=torch.float64)
+        self.graph = None
+        self.static_preds = None
+
+    @property
+    def captured(self) -> bool:
+        return self.graph is not None
+
+    def eager(self) -> None:
+        from . import tools
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            dev_type = self.labels.device.type
+            capturing = dev_type == "cuda" and torch.cuda.is_current_stream_capturing()
+            with torch.no_grad():
+                with torch.autocast(dev_type, dtype=self.amp_dtype or torch.bfloat16,
+                                    enabled=self.amp_dtype is not None, cache_enabled=not capturing):
+                    preds = self.forward(*self.inputs)
+                self.static_preds = preds
+                tools.val_accumulate(preds, self.labels, self.totals, n_valid=self.n_valid,
+                                     pos_weight=self.pos_weight)
+        finally:
+            self.model.train(was_training)
+
+    def capture(self, warmup: int = 1, error_mode: str = "global") -> None:
+        """`warmup` eager steps on a side stream, then capture; the totals are reset afterwards and the
+        module's mode is what it was. error_mode: as TrainStep.capture's."""
+        dev = self.labels.device
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            for _ in range(max(warmup, 1)):
+                self.eager()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, capture_error_mode=error_mode):
+            self.eager()
+        self.graph = g
+        self.reset()
+
+    def __call__(self) -> None:
+        if self.graph is None:
+            self.eager()
+        else:
+            self.graph.replay()
+
+    def reset(self) -> None:
+        self.totals.zero_()
+
+    def read(self, n_samples: Optional[int] = None) -> dict:
+        """get_val_info's dict: the loss total over ``n_samples`` (``len(valloader.dataset)``; default: the
+        constructor's), and intersection / union (an empty union raises ZeroDivisionError, as the
+        reference's does). The one host read of a validation pass."""
+        loss, inter, union = self.totals.tolist()
+        return {"loss": loss / (self.n_samples if n_samples is None else n_samples), "iou": inter / union}

@@ -1,0 +1,392 @@
+"""The training loop of train_simbev.py:23-458 on the captured step, fed by ``simbev.compile_data``.
+
+``train(dataroot, ...)`` takes the reference's arguments and behaves as its loop does -- same model,
+loss, clipping and Adam, validation every ``val_step`` steps with a best-IoU checkpoint, a checkpoint
+every ``save_step`` steps and at the end, resume from either trainer's checkpoints -- but each step is
+two HIP graph replays (train_step.TrainStep over flat fp32 masters, as bench.py builds it) whose static
+inputs ``staging.BatchStager`` fills from the loader's raw batches, one batch ahead:
+
+    stage(batch k+1)  staging stream: H2D copies + the two SimBEV kernels, while step k runs
+    commit()          slot -> static tensors, host torch.inverse of the rig staged (ops.HostInverses)
+    step()            graph A (forward, loss, backward), graph B (clip + Adam, guarded)
+
+The host reads the device at the reference's cadence only: the loss every 10 steps, the training IoU and
+the count of skipped (non-finite) steps every 100, validation totals once per validation
+(train_step.EvalStep: one more graph, over the same static tensors), checkpoints. Nothing else
+synchronises. Events go to ``logdir/metrics.jsonl`` (one JSON object per line) and, when importable, to
+tensorboardX / wandb. ``graph=False`` runs the same loop eagerly on the same stager.
+
+    python -m lss_carla_amd.trainer --dataroot /data/simbev --bsz 8 --final_h 128 --final_w 352
+
+Differences from the reference, all deliberate: the matplotlib figures are not drawn; the first
+validation always writes ``model_best.pt`` (the reference skips it while the IoU is 0); every camera is
+used (``ncams=6``: validation uses all six and a captured step has one static shape); a step whose
+bf16 gradient is not finite is skipped and counted instead of poisoning the weights (``skip_nonfinite``).
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import time
+from typing import Callable, Optional
+
+from . import miopen_db
+
+miopen_db.use_committed()  # the committed MIOpen find results, as bench.py uses them (before torch starts)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+
+class _Log:
+    """metrics.jsonl plus the optional writers (neither is required to be installed)."""
+
+    def __init__(self, logdir: str, use_wandb: bool, wandb_kwargs: dict, config: dict):
+        self.f = open(os.path.join(logdir, "metrics.jsonl"), "a")
+        self.tb, self.wandb = None, None
+        try:
+            from tensorboardX import SummaryWriter
+            self.tb = SummaryWriter(logdir=logdir)
+        except ImportError:
+            pass
+        if use_wandb:
+            try:
+                import wandb
+                wandb.init(config=config, dir=logdir, **wandb_kwargs)
+                self.wandb = wandb
+            except ImportError:
+                print("wandb is not installed: logging to metrics.jsonl only")
+
+    def event(self, kind: str, counter: int, **values) -> None:
+        self.f.write(json.dumps({"event": kind, "counter": counter, **values}) + "\n")
+        self.f.flush()
+        scalars = {f"{kind}/{k}": v for k, v in values.items() if isinstance(v, (int, float))}
+        if self.tb is not None:
+            for k, v in scalars.items():
+                self.tb.add_scalar(k, v, counter)
+        if self.wandb is not None:
+            self.wandb.log({**scalars, "iteration": counter})
+
+    def close(self) -> None:
+        self.f.close()
+        if self.tb is not None:
+            self.tb.close()
+        if self.wandb is not None:
+            self.wandb.finish()
+
+
+class _Cycle:
+    """`n` pre-decoded raw batches of a loader, cycled for the loader's length (measurement: the loop
+    without the decode)."""
+
+    def __init__(self, loader, n: int):
+        self.batches, self.length = [], len(loader)
+        for b in loader:
+            self.batches.append(b)
+            if len(self.batches) >= n:
+                break
+
+    def __len__(self):
+        return self.length
+
+    def __iter__(self):
+        for i in range(self.length):
+            yield self.batches[i % len(self.batches)]
+
+
+def build_step(grid_conf, data_aug_conf, bsz, device, *, dtype="bf16", lr=1e-3, weight_decay=1e-7,
+               max_grad_norm=5.0, pos_weight=2.13, skip_nonfinite=True, n_val=None) -> dict:
+    """The model and its steps as bench.py's train branch builds them -- unused parameters frozen, one flat
+    fp32 master per backward group, fused capturable Adam, TrainStep without a pre_step (the stager's
+    commit stages the inverses) -- plus the stager and the EvalStep over the same static tensors. Nothing is
+    captured yet."""
+    import lss_carla_amd as L
+    from . import parallel, simbev, tools
+    from .flat_params import FlatParamGroups, lss_backward_groups
+    from .staging import BatchStager
+    from .train_step import EvalStep, TrainStep
+
+    amp_dtype = torch.bfloat16 if dtype == "bf16" else None
+    model = L.compile_model(grid_conf, data_aug_conf, outC=1).to(device)
+    model.bevencode.to(memory_format=torch.channels_last)
+    model.camencode.up1.to(memory_format=torch.channels_last)
+    model.train()
+    parallel.freeze_unused(model)
+    flat = FlatParamGroups(model, lss_backward_groups(), cast_dtype=amp_dtype)
+    masters = flat.masters
+    opt = torch.optim.Adam(masters, lr=lr, weight_decay=weight_decay, fused=True, capturable=True)
+    stager = BatchStager(data_aug_conf["final_dim"], bsz, len(simbev.CAMERA_ORDER),
+                         (data_aug_conf["H"], data_aug_conf["W"]), grid_conf, device)
+    model.static_inverses = (stager.hinv.pinv, stager.hinv.kinv)  # staged by the stager's commit
+    loss_fn = tools.SimpleLoss(pos_weight).to(device)
+    forward = flat.bind(model)
+    step = TrainStep(forward, stager.inputs, stager.binimgs, loss_fn, opt, masters, all_reduce=False,
+                     amp_dtype=amp_dtype, max_grad_norm=max_grad_norm, pre_step=None,
+                     skip_nonfinite=bool(skip_nonfinite), keep_preds=True)
+    evaluate = EvalStep(model, forward, stager.inputs, stager.binimgs, n_valid=stager.n_valid,
+                        pos_weight=pos_weight, amp_dtype=amp_dtype, n_samples=n_val)
+    return {"model": model, "flat": flat, "masters": masters, "opt": opt, "stager": stager, "step": step,
+            "evaluate": evaluate, "loss_fn": loss_fn, "forward": forward}
+
+
+def train(
+    dataroot,
+    nepochs=100,
+    gpuid=0,
+    H=224,
+    W=480,
+    resize_lim=(1.0, 1.0),
+    final_dim=(128, 352),
+    bot_pct_lim=(0.0, 0.0),
+    rot_lim=(0.0, 0.0),
+    rand_flip=False,
+    ncams=6,
+    max_grad_norm=5.0,
+    pos_weight=2.13,
+    logdir="./runs/simbev",
+    xbound=[-50.0, 50.0, 0.5],
+    ybound=[-50.0, 50.0, 0.5],
+    zbound=[-10.0, 10.0, 20.0],
+    dbound=[4.0, 45.0, 1.0],
+    bsz=4,
+    nworkers=4,
+    lr=1e-3,
+    weight_decay=1e-7,
+    val_step=500,
+    save_step=1000,
+    resume=None,
+    use_wandb=True,
+    wandb_project="lift-splat-shoot",
+    wandb_name=None,
+    wandb_entity=None,
+    *,
+    graph=True,
+    dtype="bf16",
+    miopen_find=True,
+    seed=None,
+    max_steps=None,
+    skip_nonfinite=True,
+    loss_step=10,
+    iou_step=100,
+    cycle_batches=0,
+    on_start: Optional[Callable[[dict], None]] = None,
+):
+    """Train LiftSplatShoot on a SimBEV tree; the reference's arguments (train_simbev.py:23-98) plus:
+
+    graph: replay the step as HIP graphs (False: the same loop, eager). dtype: "bf16" (autocast) or
+    "fp32". miopen_find: torch.backends.cudnn.benchmark for this process. seed: torch's seed, and
+    np.random is reseeded with ``seed + epoch`` at every epoch (None: as the reference, from the OS).
+    max_steps: stop after this many steps of this call. skip_nonfinite: the guarded update.
+    loss_step / iou_step: the cadence of the loss and of the IoU / skipped-step reads (the reference's
+    10 and 100). cycle_batches: cycle this many pre-decoded batches instead of reading the loader
+    (measurement). on_start: called once, before the first step, with the loop's objects.
+    Returns a summary dict (counter, epoch, best_val_iou, skipped, frames_per_s of the training steps)."""
+    from . import checkpoint, simbev, tools
+
+    if gpuid < 0 or not torch.cuda.is_available():
+        raise RuntimeError("lss_carla_amd.trainer: needs an MI355X (the hot path has no CPU fallback)")
+    if ncams != len(simbev.CAMERA_ORDER):
+        raise NotImplementedError("ncams must be 6: validation uses every camera and the step's shape is static")
+    if dtype not in ("bf16", "fp32"):
+        raise ValueError(f"dtype {dtype!r}: bf16 or fp32")
+    os.makedirs(logdir, exist_ok=True)
+    grid_conf = {"xbound": xbound, "ybound": ybound, "zbound": zbound, "dbound": dbound}
+    data_aug_conf = {"resize_lim": resize_lim, "final_dim": final_dim, "rot_lim": rot_lim, "H": H, "W": W,
+                     "rand_flip": rand_flip, "bot_pct_lim": bot_pct_lim, "Ncams": ncams}
+    config = {"dataroot": str(dataroot), "nepochs": nepochs, "batch_size": bsz, "learning_rate": lr,
+              "weight_decay": weight_decay, "num_workers": nworkers, "num_cameras": ncams, "image_H": H, "image_W": W,
+              "final_dim": list(final_dim), "max_grad_norm": max_grad_norm, "pos_weight": pos_weight,
+              "grid_conf": grid_conf, "val_step": val_step, "save_step": save_step, "graph": bool(graph),
+              "dtype": dtype, "seed": seed}
+    log = _Log(logdir, use_wandb, {"project": wandb_project, "name": wandb_name, "entity": wandb_entity}, config)
+
+    device = torch.device(f"cuda:{gpuid}")
+    torch.cuda.set_device(device)
+    torch.backends.cudnn.benchmark = bool(miopen_find)
+    if seed is not None:
+        torch.manual_seed(seed)
+        np.random.seed(seed)
+    trainloader, valloader = simbev.compile_data("unused", dataroot, data_aug_conf, grid_conf, bsz, nworkers,
+                                                 "segmentationdata", device=device)
+    train_raw, val_raw = trainloader.loader, valloader.loader  # raw batches: the stager finishes them
+    if len(train_raw) == 0:
+        raise RuntimeError(f"the training split has fewer than bsz={bsz} samples")
+    if cycle_batches:
+        train_raw = _Cycle(train_raw, int(cycle_batches))
+    n_val = len(valloader.dataset)
+    print(f"Train batches: {len(train_raw)}  Val batches: {len(val_raw)}  device {device}  graph {bool(graph)} {dtype}")
+
+    ctx = build_step(grid_conf, data_aug_conf, bsz, device, dtype=dtype, lr=lr, weight_decay=weight_decay,
+                     max_grad_norm=max_grad_norm, pos_weight=pos_weight, skip_nonfinite=skip_nonfinite,
+                     n_val=n_val)
+    model, flat, masters, opt = ctx["model"], ctx["flat"], ctx["masters"], ctx["opt"]
+    stager, step, evaluate = ctx["stager"], ctx["step"], ctx["evaluate"]
+
+    counter, start_epoch = 0, 0
+    if resume is not None and os.path.exists(resume):
+        counter, start_epoch = checkpoint.load_checkpoint(resume, model, flat, opt)
+        print(f"Resumed from epoch {start_epoch}, iteration {counter}")
+    start_counter = counter
+    for m in masters:
+        checkpoint.init_state(opt, m)  # the state tensors exist (at fixed addresses) before any capture
+
+    def snapshot():
+        return ([t.detach().clone() for t in model.state_dict().values()],
+                [{k: v.detach().clone() for k, v in opt.state[m].items()} for m in masters])
+
+    def restore(snap):
+        with torch.no_grad():
+            for t, s in zip(model.state_dict().values(), snap[0]):
+                t.copy_(s)
+            for m, st in zip(masters, snap[1]):
+                for k, v in st.items():
+                    opt.state[m][k].copy_(v)
+            if step.skipped is not None:
+                step.skipped.zero_()
+
+    def save(path, epoch, val_iou=None):
+        checkpoint.save_checkpoint(path, model, flat, opt, counter, epoch, val_iou)
+
+    def validate():
+        """EvalStep over the val loader through the stager (no training batch is staged meanwhile)."""
+        it = iter(val_raw)
+        stager.stage(next(it))
+        first = True
+        for _ in range(len(val_raw)):
+            stager.commit()
+            if first and graph and not evaluate.captured:
+                evaluate.capture(warmup=1, error_mode="thread_local")  # on the first validation batch; resets the totals
+            if first:
+                evaluate.reset()
+                first = False
+            evaluate()
+            nxt = next(it, None)
+            if nxt is not None:
+                stager.stage(nxt)
+        return evaluate.read()
+
+    best_val_iou = -1.0
+    last_loss = None
+    t_train, n_timed, t_mark = 0.0, 0, None
+    started = False
+    done = False
+    epoch = start_epoch
+    for epoch in range(start_epoch, nepochs):
+        np.random.seed(None if seed is None else seed + epoch)
+        it = iter(train_raw)
+        nxt = next(it, None)
+        if nxt is not None:
+            stager.stage(nxt)
+        while nxt is not None:
+            stager.commit()
+            if not started:
+                started = True
+                if graph:
+                    # the warm-up steps of the capture are real updates: undo them
+                    snap = snapshot()
+                    step.capture(warmup=2, error_mode="thread_local")
+                    restore(snap)
+                    del snap
+                if on_start is not None:
+                    on_start({"model": model, "flat": flat, "opt": opt, "step": step, "stager": stager,
+                              "counter": counter, "epoch": epoch})
+                torch.cuda.synchronize(device)
+                t_mark = time.perf_counter()
+            will_val = (counter + 1) % val_step == 0
+            loss = step()
+            counter += 1
+            n_timed += 1
+            nxt = None
+            if max_steps is not None and counter - start_counter >= max_steps:
+                done = True
+            elif not will_val:
+                nxt = next(it, None)  # staged while the step runs
+                if nxt is not None:
+                    stager.stage(nxt)
+            if counter % loss_step == 0:
+                last_loss = float(loss.item())
+                log.event("train", counter, epoch=epoch, loss=last_loss)
+            if counter % iou_step == 0:
+                _, _, iou = tools.get_batch_iou(step.static_preds, stager.binimgs)
+                skipped = int(step.skipped.item()) if step.skipped is not None else 0
+                log.event("train_iou", counter, epoch=epoch, iou=iou, skipped=skipped)
+            if will_val or counter % save_step == 0:
+                torch.cuda.synchronize(device)
+                t_train += time.perf_counter() - t_mark
+            if will_val:
+                info = validate()
+                print(f"  Validation at {counter} - Loss: {info['loss']:.4f}, IoU: {info['iou']:.4f}")
+                log.event("val", counter, epoch=epoch, loss=info["loss"], iou=info["iou"])
+                if info["iou"] > best_val_iou:
+                    best_val_iou = info["iou"]
+                    save(os.path.join(logdir, "model_best.pt"), epoch, best_val_iou)
+            if counter % save_step == 0:
+                save(os.path.join(logdir, f"model_{counter:06d}.pt"), epoch)
+            if will_val or counter % save_step == 0:
+                t_mark = time.perf_counter()
+            if will_val and not done:
+                nxt = next(it, None)
+                if nxt is not None:
+                    stager.stage(nxt)
+            if done:
+                break
+        if done:
+            break
+    torch.cuda.synchronize(device)
+    if t_mark is not None:
+        t_train += time.perf_counter() - t_mark
+    final_epoch = epoch if done else nepochs
+    save(os.path.join(logdir, "model_final.pt"), final_epoch)
+    skipped = int(step.skipped.item()) if step.skipped is not None else 0
+    if started:
+        last_loss = float((step.static_loss if step.captured else loss).item())
+    fps = n_timed * bsz / t_train if t_train > 0 else 0.0
+    log.event("final", counter, epoch=final_epoch, loss=last_loss, skipped=skipped, frames_per_s=fps,
+              best_val_iou=best_val_iou if best_val_iou >= 0 else None)
+    log.close()
+    print(f"Training complete at iteration {counter}; best validation IoU: {max(best_val_iou, 0.0):.4f}")
+    return {"counter": counter, "epoch": final_epoch, "best_val_iou": best_val_iou if best_val_iou >= 0 else None,
+            "skipped": skipped, "frames_per_s": fps, "loss": last_loss}
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser(description="Train LSS on a SimBEV dataset (captured step on the MI355X)")
+    p.add_argument("--dataroot", type=str, required=True, help="SimBEV dataset root directory")
+    p.add_argument("--nepochs", type=int, default=100)
+    p.add_argument("--gpuid", type=int, default=0)
+    p.add_argument("--bsz", type=int, default=4)
+    p.add_argument("--nworkers", type=int, default=4)
+    p.add_argument("--lr", type=float, default=1e-3)
+    p.add_argument("--weight_decay", type=float, default=1e-7)
+    p.add_argument("--H", type=int, default=224)
+    p.add_argument("--W", type=int, default=480)
+    p.add_argument("--final_h", type=int, default=128)
+    p.add_argument("--final_w", type=int, default=352)
+    p.add_argument("--ncams", type=int, default=6)
+    p.add_argument("--logdir", type=str, default="./runs/simbev")
+    p.add_argument("--val_step", type=int, default=500)
+    p.add_argument("--save_step", type=int, default=1000)
+    p.add_argument("--resume", type=str, default=None)
+    p.add_argument("--use_wandb", action="store_true", default=False)
+    p.add_argument("--wandb_project", type=str, default="lift-splat-shoot")
+    p.add_argument("--wandb_name", type=str, default=None)
+    p.add_argument("--wandb_entity", type=str, default=None)
+    # beyond the reference's flags
+    p.add_argument("--graph", type=int, default=1, help="0: the same loop, eager")
+    p.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
+    p.add_argument("--miopen_find", type=int, default=1)
+    p.add_argument("--seed", type=int, default=None)
+    p.add_argument("--max_steps", type=int, default=None)
+    p.add_argument("--skip_nonfinite", type=int, default=1)
+    a = p.parse_args(argv)
+    return train(dataroot=a.dataroot, nepochs=a.nepochs, gpuid=a.gpuid, H=a.H, W=a.W, final_dim=(a.final_h, a.final_w),
+                 ncams=a.ncams, bsz=a.bsz, nworkers=a.nworkers, lr=a.lr, weight_decay=a.weight_decay, logdir=a.logdir,
+                 val_step=a.val_step, save_step=a.save_step, resume=a.resume, use_wandb=a.use_wandb,
+                 wandb_project=a.wandb_project, wandb_name=a.wandb_name, wandb_entity=a.wandb_entity,
+                 graph=bool(a.graph), dtype=a.dtype, miopen_find=bool(a.miopen_find), seed=a.seed,
+                 max_steps=a.max_steps, skip_nonfinite=bool(a.skip_nonfinite))
+
+
+if __name__ == "__main__":
+    main()

@@ -20,6 +20,10 @@ Steps:
                                       per-kernel averages in NAME.txt
   kbench:NAME:args                    scripts/kbench.py with args, log kept
   py:NAME:script args                 python scripts/<script> args (a diagnostics script), log kept
+  train_loop[:steps]                  trainer.train on a synthetic SimBEV tree at config-3 sizes (224x480 JPEGs, B=8,
+                                      written to a temporary directory): frames/s of (a) the loop with 14 loader
+                                      workers, (b) the loop cycling pre-decoded host batches, (c) bench.py's default,
+                                      (d) bench.py --caller reference, in train_loop.json
   lib:VARIANT                         later steps load lss-carla_amd/variants/VARIANT.so (product: the default)
 """
 from __future__ import annotations
@@ -193,6 +197,49 @@ def step_py(out, spec):
     return rc
 
 
+def step_train_loop(out, spec):
+    import json
+    import tempfile
+    steps = int(spec) if spec else 200
+    script = os.path.join("scripts", "train_loop.py")
+    result = {"steps": steps, "bsz": 8}
+
+    def last_json(log):
+        last = tail(log, 1).strip()
+        return json.loads(last) if last.startswith("{") else None
+
+    with tempfile.TemporaryDirectory(prefix="lss_simbev_") as root:
+        # 80 % of the samples train: enough for `steps` batches of 8 in one epoch
+        samples = int(steps * 8 / 0.8) + 40
+        rc = run([PY, "-u", script, "--make", root, "--samples", str(samples)], os.path.join(out, "tree.log"), 900)
+        if rc != 0:
+            return rc
+        for key, extra in (("a_loop_14_workers", ["--nworkers", "14"]),
+                           ("b_loop_predecoded", ["--nworkers", "0", "--cycle-batches", "4"])):
+            log = os.path.join(out, f"train_loop_{key}.log")
+            rc = run([PY, "-u", script, "--dataroot", root, "--steps", str(steps)] + extra, log, 900)
+            got = last_json(log) if rc == 0 else None
+            if got is None:
+                print(tail(log, 15), flush=True)
+                return rc or 1
+            result[key] = got["frames_per_s"]
+            print(f"  {key}: {got}", flush=True)
+    for key, extra in (("c_bench_default", []), ("d_bench_reference_caller", ["--caller", "reference"])):
+        log = os.path.join(out, f"train_loop_{key}.log")
+        rc = run([PY, "-u", "bench.py", "--gpus", "1"] + extra, log, 900)
+        got = last_json(log) if rc == 0 else None
+        if got is None:
+            print(tail(log, 15), flush=True)
+            return rc or 1
+        result[key] = got.get("value")
+        print(f"  {key}: {got.get('value')} {got.get('unit', '')}", flush=True)
+    with open(os.path.join(out, "train_loop.json"), "w") as fh:
+        json.dump(result, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(result), flush=True)
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tag", required=True)
@@ -202,7 +249,7 @@ def main():
     os.makedirs(out, exist_ok=True)
     os.chdir(REPO)
     fns = {"tests": step_tests, "smoke": step_smoke, "bench": step_bench, "trace": step_trace, "pmc": step_pmc,
-           "kbench": step_kbench, "py": step_py}
+           "kbench": step_kbench, "py": step_py, "train_loop": step_train_loop}
     for s in a.steps:
         kind, _, spec = s.partition(":")
         print(f"== {s}", flush=True)

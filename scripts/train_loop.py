@@ -1,0 +1,53 @@
+"""Frames/s of trainer.train's steps on a synthetic SimBEV tree at config-3 sizes (scripts/measure.py's
+train_loop step): one JSON line {"frames_per_s", "steps", "nworkers", "cycle_batches", ...}.
+
+  python scripts/train_loop.py --dataroot DIR --steps 200 --nworkers 14            the loop as a user runs it
+  python scripts/train_loop.py --dataroot DIR --steps 200 --cycle-batches 4        pre-decoded host batches cycled:
+                                                                                    the step plus the staging only
+  python scripts/train_loop.py --make DIR --samples 2000                           write the tree and exit
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import tempfile
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--make", default="")
+    ap.add_argument("--samples", type=int, default=2000, help="--make: samples written (80 % are the training split)")
+    ap.add_argument("--dataroot", default="")
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--bsz", type=int, default=8)
+    ap.add_argument("--nworkers", type=int, default=14)
+    ap.add_argument("--cycle-batches", type=int, default=0)
+    ap.add_argument("--graph", type=int, default=1)
+    ap.add_argument("--miopen-find", type=int, default=0)
+    a = ap.parse_args()
+    from lss_carla_amd import miopen_db
+    miopen_db.use_committed()  # before torch starts
+    from lss_carla_amd import synthetic as syn
+    if a.make:
+        per_scene = 20
+        n = syn.make_simbev_tree(a.make, (a.samples + per_scene - 1) // per_scene, per_scene)
+        print(json.dumps({"made": a.make, "samples": n}))
+        return
+    from lss_carla_amd import trainer
+    with tempfile.TemporaryDirectory() as logdir:
+        out = trainer.train(a.dataroot, nepochs=1000, bsz=a.bsz, nworkers=a.nworkers, logdir=logdir,
+                            val_step=10 ** 9, save_step=10 ** 9, use_wandb=False, graph=bool(a.graph),
+                            miopen_find=bool(a.miopen_find), seed=0, max_steps=a.steps,
+                            cycle_batches=a.cycle_batches)
+    print(json.dumps({"frames_per_s": out["frames_per_s"], "steps": out["counter"], "bsz": a.bsz,
+                      "nworkers": a.nworkers, "cycle_batches": a.cycle_batches, "graph": a.graph,
+                      "skipped": out["skipped"], "loss": out["loss"]}))
+
+
+if __name__ == "__main__":
+    main()

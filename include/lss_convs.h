@@ -10,6 +10,14 @@
  * by (Ho, Wo): taps that fall outside the input read zero (TF "same" static padding, asymmetric
  * for the stride-2 layers). Asynchronous on the stream; 0 on success, a positive hipError_t on a
  * launch failure, LSS_CONV_EINVAL for bad arguments.
+ *
+ * Alignment contract (whole header). Pointers are bare addresses: a function cannot see the tensor's
+ * dtype, strides or storage offset, so each one states the alignment its vector accesses need and
+ * checks it on the host, before any HIP call -- a pointer that misses it is LSS_CONV_EINVAL, never a
+ * launch (there is no scalar fallback; a caller holding a dense view at an odd offset copies it first,
+ * as lss_carla_amd._lib.aligned does). fp32 arrays (weights, statistics, partials) are read by element.
+ * The lss_dwconv_* functions: x, y, dy, dx 16-B aligned (the LDS-staged and the plane kernels load and
+ * store 16-B vectors).
  */
 #ifndef LSS_CONVS_H
 #define LSS_CONVS_H
@@ -52,7 +60,8 @@ int lss_dwconv_bwd_weight2(const void* x, const void* dy, int32_t dtype, int32_t
  * y[r] = bf16(sum_c x[r, c] * w[c] + bias[0]) (fp32 accumulation; w holds the bf16-rounded weights
  * as fp32, as autocast's conv operands; bias is a device scalar, nullable). Backward: dx[r, c] = bf16(dy[r] * w[c]) and partial
  * (lss_head1_blocks(P), C + 1) fp32 = per block of rows, sum_r dy[r] * x[r, c] (columns 0..C-1) and
- * sum_r dy[r] (column C); the caller sums the blocks (fixed order). */
+ * sum_r dy[r] (column C); the caller sums the blocks (fixed order).
+ * Alignment: x and dx 16-B aligned (rows are read as 16-B vectors); y and dy by element (2 B). */
 int lss_head1_blocks(int32_t P);
 int lss_head1_fwd(const void* x, const float* w, const float* bias, int32_t P, int32_t C, void* y, void* stream);
 int lss_head1_bwd(const void* x, const void* dy, const float* w, int32_t P, int32_t C, void* dx, float* partial,
@@ -185,7 +194,11 @@ int lss_clip_adam_guarded(int32_t count, float* const* params, const float* cons
  * partial: (C, ngroups, 2) fp32 scratch, ngroups from lss_bn_groups. save_mean, save_rstd, scale,
  * shift are the four rows of one (4, C) fp32 array (outputs kept for lss_bn_bwd).
  * num_batches_tracked (nullable): the module's int64 counter, incremented on the device (no
- * separate launch per BN layer). */
+ * separate launch per BN layer).
+ * Alignment of x, residual, y (and dy, dx, dresidual in the backward): the width of the vector the
+ * kernels pick from the layout and HW -- LSS_CONV_NHWC: 16 B; LSS_CONV_NCHW: 16 B for fp32 with
+ * HW % 4 == 0 and bf16 with HW % 8 == 0, 8 B for bf16 with HW % 8 == 4, else one element. gamma, beta,
+ * the statistics and scratch: 4 B; num_batches_tracked: 8 B. */
 int lss_bn_groups(int32_t N, int32_t C, int32_t HW, int32_t layout);
 int lss_bn_fwd(const void* x, const void* residual, int32_t dtype, int32_t layout, int32_t N, int32_t C, int32_t HW,
                const float* gamma, const float* beta, float eps, float momentum, float* running_mean,
@@ -222,7 +235,8 @@ int lss_bn_bwd2(const void* dy, const void* x, const void* y, int32_t dtype, int
  * dy[p][c] = bf16(g1[p] * w1[c]) (g1: N*HW bf16, w1: C fp32), computed in the kernels instead of read --
  * the gradient the one-channel head hands back (lss_head1_bwd2 with dx = NULL). Otherwise lss_bn_bwd's
  * NHWC path with y = NULL, no residual; act LSS_ACT_NONE or LSS_ACT_RELU. And lss_bn_fwd / lss_bn_fwd2
- * accept y = NULL for LSS_CONV_NHWC: statistics, saved stats and running stats only, no apply pass. */
+ * accept y = NULL for LSS_CONV_NHWC: statistics, saved stats and running stats only, no apply pass.
+ * Alignment: x and dx 16 B, g1 by element (2 B), the fp32 arrays 4 B. */
 int lss_bn_bwd_rank1(const void* g1, const float* w1, const void* x, int32_t N, int32_t C, int32_t HW,
                      const float* scale, const float* shift, const float* save_mean, const float* save_rstd,
                      int32_t act, int32_t ngroups, float* partial, float* coef, float* dgamma, float* dbeta, void* dx,
@@ -256,7 +270,8 @@ int lss_upsample_bwd2(const void* dy, int32_t N, int32_t Hi, int32_t Wi, int32_t
  * NCHW bf16 (HW % 4 == 0, C <= 2048, sq <= 64), W1 (sq, C), b1 (sq), W2 (C, sq), b2 (C) fp32
  * masters. Weights and values are rounded to bf16 where bf16 autocast rounds them (conv operands,
  * pooled map, both conv outputs, swish, sigmoid). Saved for the backward: m (N, C) pooled means, r / h (N, sq) reduce-conv output and
- * its swish, sig (N, C); all fp32 buffers. */
+ * its swish, sig (N, C); all fp32 buffers. Alignment: x, y (and dy, dx of lss_se_bwd) 8-B aligned
+ * (four bf16 per access). */
 int lss_se_fwd(const void* x, int32_t N, int32_t C, int32_t HW, const float* w1, const float* b1, const float* w2,
                const float* b2, int32_t sq, float* m, float* r, float* h, float* sig, void* y, void* stream);
 

@@ -185,6 +185,16 @@ def ptr(t: Optional[torch.Tensor]):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+def aligned(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """t, or a copy with the same strides when its data pointer is not 16-B aligned. ``ptr()`` hands a
+    kernel the bare address and the kernels' vector accesses (up to 16 B) need it aligned: a fresh
+    allocation is, a dense view at an odd storage offset (a slice of a flat buffer) is not, and reaches
+    the kernel only as a copy. For dense tensors (contiguous in some memory format)."""
+    if t is None or t.data_ptr() % 16 == 0:
+        return t
+    return t.clone(memory_format=torch.preserve_format)
+
+
 def stream_handle(device: torch.device):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 

@@ -1278,6 +1278,19 @@ template <typename T> inline bool fused_reg(int V, long cnt) {
 
 inline int vec_nchw(int HW) { return HW % 8 == 0 ? 8 : (HW % 4 == 0 ? 4 : 1); }
 
+// The widest access the kernels make on an activation tensor, as a pointer mask: 16 B (NHWC; NCHW fp32
+// with V >= 4, bf16 with V = 8), 8 B (NCHW bf16, V = 4), one element (V = 1). Checked on the host before
+// any launch: a tensor view at another offset is the caller's to copy.
+inline uintptr_t bn_align_mask(int dtype, int layout, int HW) {
+    const int es = dtype == LSS_CONV_F32 ? 4 : 2;
+    if (layout == LSS_CONV_NHWC) return 15;
+    const int b = vec_nchw(HW) * es;
+    return (uintptr_t)((b > 16 ? 16 : b) - 1);
+}
+template <typename... P> inline bool ptrs_ok(uintptr_t mask, P... p) {  // NULL passes (nullable arguments)
+    return ((... | reinterpret_cast<uintptr_t>(p)) & mask) == 0;
+}
+
 #ifndef LSS_BN_CLUSTER
 #define LSS_BN_CLUSTER 1  // NCHW, G > 1: the cluster kernels when a sync workspace is given (lss_bn_*2)
 #endif
@@ -1356,6 +1369,9 @@ int lss_bn_fwd2(const void* x, const void* residual, int32_t dtype, int32_t layo
     // the saved statistics are one (4, C) array: mean, rstd, scale, shift
     if (save_rstd != save_mean + C || scale != save_mean + 2 * C || shift != save_mean + 3 * C) return LSS_CONV_EINVAL;
     if (layout == LSS_CONV_NHWC && ngroups > kMaxGroupsNhwc) return LSS_CONV_EINVAL;
+    if (!ptrs_ok(bn_align_mask(dtype, layout, HW), x, residual, y) ||
+        !ptrs_ok(3, gamma, beta, running_mean, running_var, partial, save_mean) || !ptrs_ok(7, num_batches_tracked))
+        return LSS_CONV_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     const BnParams P{gamma, beta, eps, momentum, running_mean, running_var, save_mean, num_batches_tracked};
     const int G = ngroups;
@@ -1447,6 +1463,9 @@ int lss_bn_bwd2(const void* dy, const void* x, const void* y, int32_t dtype, int
     if (act == LSS_ACT_RELU && !y && layout != LSS_CONV_NHWC) return LSS_CONV_EINVAL;
     if (act != LSS_ACT_NONE && act != LSS_ACT_RELU && act != LSS_ACT_SWISH) return LSS_CONV_EINVAL;
     if (layout == LSS_CONV_NHWC && ngroups > kMaxGroupsNhwc) return LSS_CONV_EINVAL;
+    if (!ptrs_ok(bn_align_mask(dtype, layout, HW), dy, x, y, dx, dresidual) ||
+        !ptrs_ok(3, save_mean, partial, coef, dgamma, dbeta))
+        return LSS_CONV_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     const int G = ngroups;
     const float* stats = save_mean;
@@ -1552,6 +1571,9 @@ int lss_bn_bwd_rank1(const void* g1, const float* w1, const void* x, int32_t N, 
         return LSS_CONV_EINVAL;
     if (save_rstd != save_mean + C || scale != save_mean + 2 * C || shift != save_mean + 3 * C) return LSS_CONV_EINVAL;
     if (act != LSS_ACT_NONE && act != LSS_ACT_RELU) return LSS_CONV_EINVAL;
+    // x / dx: 16-B rows; g1: one bf16 per pixel, read by element
+    if (!ptrs_ok(15, x, dx) || !ptrs_ok(1, g1) || !ptrs_ok(3, w1, save_mean, partial, coef, dgamma, dbeta))
+        return LSS_CONV_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     const int G = ngroups;
     const Rank1 r1{(const bf16*)g1, w1};

@@ -326,6 +326,11 @@ inline int launch_status() {
     return e == hipSuccess ? 0 : (int)e;
 }
 
+// every pointer 16-B aligned (NULL passes): the vector accesses of the kernels behind an entry point
+template <typename... P> inline bool aligned16(P... p) {
+    return ((... | reinterpret_cast<uintptr_t>(p)) & 15) == 0;
+}
+
 inline bool geo_ok(int N, int C, int Hi, int Wi, int K, int S, int Ho, int Wo) {
     return N > 0 && C > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && (K == 3 || K == 5) && (S == 1 || S == 2) &&
            (long)N * C * Hi * Wi < INT_MAX && (long)N * C * Ho * Wo < INT_MAX;
@@ -1993,6 +1998,7 @@ int lss_head1_fwd(const void* x, const float* w, const float* bias, int32_t P, i
 int lss_head1_fwd2(const void* x, const float* w, const float* bias, int32_t P, int32_t C, const float* bn_stats,
                    void* y, void* stream) {
     if (!x || !w || !y || P <= 0 || C <= 0 || C % 8 != 0 || 64 % (C / 8) != 0) return LSS_CONV_EINVAL;
+    if (!aligned16(x) || (reinterpret_cast<uintptr_t>(y) & 1)) return LSS_CONV_EINVAL;  // uint4 rows; y by element
     const dim3 gr(lss_head1_blocks(P)), bl(kBlock);
     hipStream_t s = (hipStream_t)stream;
 #define LSS_HEAD1_FWD(L) \
@@ -2020,6 +2026,7 @@ int lss_head1_bwd2(const void* x, const void* dy, const float* w, int32_t P, int
                    float* partial, void* stream) {
     if (!x || !dy || !w || (!dx && !bn_stats) || !partial || P <= 0 || C <= 0 || C % 8 != 0 || 64 % (C / 8) != 0)
         return LSS_CONV_EINVAL;
+    if (!aligned16(x, dx) || (reinterpret_cast<uintptr_t>(dy) & 1)) return LSS_CONV_EINVAL;
     const dim3 gr(lss_head1_blocks(P)), bl(kBlock);
     hipStream_t s = (hipStream_t)stream;
 #define LSS_HEAD1_BWD(L)                                                                                          \
@@ -2129,7 +2136,7 @@ int lss_pw_conv(const void* x, const void* a, int32_t a_layout, int32_t N, int32
 int lss_dwconv_fwd(const void* x, int32_t dtype, const float* w, int32_t N, int32_t C, int32_t Hi, int32_t Wi,
                    int32_t K, int32_t stride, int32_t pad_top, int32_t pad_left, int32_t Ho, int32_t Wo, void* y,
                    void* stream) {
-    if (!x || !w || !y || !geo_ok(N, C, Hi, Wi, K, stride, Ho, Wo)) return LSS_CONV_EINVAL;
+    if (!x || !w || !y || !geo_ok(N, C, Hi, Wi, K, stride, Ho, Wo) || !aligned16(x, y)) return LSS_CONV_EINVAL;
     const DwGeo g{C, Hi, Wi, Ho, Wo, pad_top, pad_left, N * C};
     return dispatch_kst<Fwd>(K, stride, dtype, x, w, g, 0, y, (hipStream_t)stream);
 }
@@ -2137,7 +2144,7 @@ int lss_dwconv_fwd(const void* x, int32_t dtype, const float* w, int32_t N, int3
 int lss_dwconv_bwd_data(const void* dy, int32_t dtype, const float* w, int32_t N, int32_t C, int32_t Hi, int32_t Wi,
                         int32_t K, int32_t stride, int32_t pad_top, int32_t pad_left, int32_t Ho, int32_t Wo, void* dx,
                         void* stream) {
-    if (!dy || !w || !dx || !geo_ok(N, C, Hi, Wi, K, stride, Ho, Wo)) return LSS_CONV_EINVAL;
+    if (!dy || !w || !dx || !geo_ok(N, C, Hi, Wi, K, stride, Ho, Wo) || !aligned16(dy, dx)) return LSS_CONV_EINVAL;
     const DwGeo g{C, Hi, Wi, Ho, Wo, pad_top, pad_left, N * C};
     return dispatch_kst<BwdData>(K, stride, dtype, dy, w, g, dx, (hipStream_t)stream);
 }
@@ -2145,7 +2152,8 @@ int lss_dwconv_bwd_data(const void* dy, int32_t dtype, const float* w, int32_t N
 int lss_dwconv_bwd_weight(const void* x, const void* dy, int32_t dtype, int32_t N, int32_t C, int32_t Hi, int32_t Wi,
                           int32_t K, int32_t stride, int32_t pad_top, int32_t pad_left, int32_t Ho, int32_t Wo,
                           int32_t ngroups, float* partial, void* stream) {
-    if (!x || !dy || !partial || ngroups <= 0 || ngroups > N || !geo_ok(N, C, Hi, Wi, K, stride, Ho, Wo))
+    if (!x || !dy || !partial || ngroups <= 0 || ngroups > N || !geo_ok(N, C, Hi, Wi, K, stride, Ho, Wo) ||
+        !aligned16(x, dy))
         return LSS_CONV_EINVAL;
     const DwGeo g{C, Hi, Wi, Ho, Wo, pad_top, pad_left, N * C};
     return dispatch_kst<BwdWeight>(K, stride, dtype, x, dy, g, (int)N, (int)ngroups, partial, DwFold{nullptr, nullptr},
@@ -2156,7 +2164,7 @@ int lss_dwconv_bwd_weight2(const void* x, const void* dy, int32_t dtype, int32_t
                            int32_t K, int32_t stride, int32_t pad_top, int32_t pad_left, int32_t Ho, int32_t Wo,
                            int32_t ngroups, float* partial, uint32_t* sync, float* dw, void* stream) {
     if (!x || !dy || !partial || !sync || !dw || ngroups <= 0 || ngroups > N || C > kDwSyncMaxC ||
-        !geo_ok(N, C, Hi, Wi, K, stride, Ho, Wo))
+        !geo_ok(N, C, Hi, Wi, K, stride, Ho, Wo) || !aligned16(x, dy))
         return LSS_CONV_EINVAL;
     const DwGeo g{C, Hi, Wi, Ho, Wo, pad_top, pad_left, N * C};
     return dispatch_kst<BwdWeight>(K, stride, dtype, x, dy, g, (int)N, (int)ngroups, partial, DwFold{sync, dw},

@@ -309,6 +309,11 @@ inline bool se_ok(int N, int C, int HW, int sq) {
            (long)N * C * HW < INT_MAX;
 }
 
+// x / y / dy / dx are read and written four bf16 (8 B) at a time; the fp32 arrays by element
+inline bool se_aligned(const void* a, const void* b, const void* c = nullptr) {
+    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 7) == 0;
+}
+
 inline int blocks(long n, int per) { return (int)((n + per - 1) / per); }
 
 }  // namespace
@@ -318,6 +323,7 @@ extern "C" {
 int lss_se_fwd(const void* x, int32_t N, int32_t C, int32_t HW, const float* w1, const float* b1, const float* w2,
                const float* b2, int32_t sq, float* m, float* r, float* h, float* sig, void* y, void* stream) {
     if (!x || !w1 || !b1 || !w2 || !b2 || !m || !r || !h || !sig || !y || !se_ok(N, C, HW, sq)) return LSS_CONV_EINVAL;
+    if (!se_aligned(x, y)) return LSS_CONV_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     const int planes = N * C, n4 = planes * HW / 4;
     hipLaunchKernelGGL(k_se_mean, dim3(blocks(planes, kBlock / kWave)), dim3(kBlock), 0, s,
@@ -335,6 +341,7 @@ int lss_se_bwd(const void* dy, const void* x, int32_t N, int32_t C, int32_t HW, 
                void* dx, void* stream) {
     if (!dy || !x || !w1 || !w2 || !r || !sig || !t || !dh_part || !de || !dr || !dm || !dx || !se_ok(N, C, HW, sq))
         return LSS_CONV_EINVAL;
+    if (!se_aligned(dy, x, dx)) return LSS_CONV_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     const int planes = N * C, n4 = planes * HW / 4;
     hipLaunchKernelGGL(k_se_dot, dim3(blocks(planes, kBlock / kWave)), dim3(kBlock), 0, s,

@@ -124,7 +124,7 @@ class _HipDepthwise(torch.autograd.Function):
             x = x.to(torch.get_autocast_dtype("cuda"))
         if x.dtype not in (torch.float32, torch.bfloat16):
             x = x.float()
-        x = x.contiguous()
+        x = _lib.aligned(x.contiguous())  # (the kernels' vector accesses: 16-B aligned tensors)
         N, C, Hi, Wi = x.shape
         K = weight.shape[-1]
         pl, pr, pt, pb = pads
@@ -145,7 +145,7 @@ class _HipDepthwise(torch.autograd.Function):
         stride, pt, pl, Ho, Wo, wdtype = ctx.conf
         N, C, Hi, Wi = x.shape
         K = int(round((w.shape[1]) ** 0.5))
-        dy = dy.to(x.dtype).contiguous()
+        dy = _lib.aligned(dy.to(x.dtype).contiguous())
         st = _lib.stream_handle(x.device)
         code = _lib.dtype_code(x.dtype)
         dx = dw = None
@@ -172,6 +172,17 @@ class _HipDepthwise(torch.autograd.Function):
         return dx, dw, None, None
 
 
+def _dw_eligible(conv: nn.Conv2d, x: torch.Tensor) -> bool:
+    """_HipDepthwise computes in the activations' dtype as the conv sees it -- the autocast dtype under
+    autocast, else x's -- and the lss_dwconv_* kernels take fp32 and bf16 (K in {3, 5}, stride 1 or 2). An
+    fp16 or fp64 caller, or fp16 autocast, takes the module's own conv: same dtypes out as in."""
+    dt = x.dtype
+    if torch.is_autocast_enabled("cuda") and dt != torch.float64:
+        dt = torch.get_autocast_dtype("cuda")
+    return (x.is_cuda and x.dim() == 4 and dt in (torch.float32, torch.bfloat16)
+            and conv.kernel_size in ((3, 3), (5, 5)) and conv.stride in ((1, 1), (2, 2)))
+
+
 class _HipPointwise(torch.autograd.Function):
     """1x1 conv (stride 1, no bias) over NCHW activations in bf16 (the autocast conv's operands): forward
     and backward-data on ``lss_pw_conv`` (MFMA, pixels as the GEMM rows; MIOpen's per-image batched
@@ -183,7 +194,7 @@ class _HipPointwise(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight):
         from . import _lib
-        xb = x.to(torch.bfloat16).contiguous()
+        xb = _lib.aligned(x.to(torch.bfloat16).contiguous())  # (lss_pw_wrw reads it too: 8-B vectors)
         wb = weight.to(torch.bfloat16)
         N, Cin, H, W = xb.shape
         Cout = wb.shape[0]
@@ -208,7 +219,7 @@ class _HipPointwise(torch.autograd.Function):
         lib = _lib.load()
         xb, wb = ctx.saved_tensors
         xdt, wdt = ctx.dtypes
-        dy = dy.to(torch.bfloat16).contiguous()
+        dy = _lib.aligned(dy.to(torch.bfloat16).contiguous())
         dx = dw = None
         if ctx.needs_input_grad[0]:
             if ctx.gemm and dy.data_ptr() % 16 == 0:
@@ -364,7 +375,7 @@ class MBConvBlock(nn.Module):
         if self.expand != 1:
             x = bn_act(self._bn0, pointwise_conv(self._expand_conv, x), "swish")
         dw = self._depthwise_conv
-        if self.depthwise_impl == "hip" and x.is_cuda:
+        if self.depthwise_impl == "hip" and _dw_eligible(dw, x):
             x = _HipDepthwise.apply(x, dw.weight, dw.stride[0], depthwise_same_pads(dw))
         elif self.depthwise_impl == "native" and x.is_cuda:
             x = _NativeConv2d.apply(dw.static_padding(x), dw.weight, dw.stride, dw.padding, dw.dilation, dw.groups)
@@ -394,6 +405,7 @@ class _HipSqueezeExcite(torch.autograd.Function):
     def forward(ctx, x, w1, b1, w2, b2):
         from . import _lib
         lib = _lib.load()
+        x = _lib.aligned(x)  # (8-B vector accesses: a view at an odd storage offset is copied)
         N, C, H, W = x.shape
         sq = w1.shape[0]
         f32 = dict(device=x.device, dtype=torch.float32)
@@ -418,7 +430,7 @@ class _HipSqueezeExcite(torch.autograd.Function):
         w1s, w1t, b1t, w2s, w2t, b2t = ctx.shapes
         N, C, H, W = x.shape
         sq = W1.shape[0]
-        dy = dy.to(torch.bfloat16).contiguous()
+        dy = _lib.aligned(dy.to(torch.bfloat16).contiguous())
         f32 = dict(device=x.device, dtype=torch.float32)
         t, de, dm = torch.empty(N, C, **f32), torch.empty(N, C, **f32), torch.empty(N, C, **f32)
         dr = torch.empty(N, sq, **f32)

@@ -55,10 +55,24 @@ UP1_CHANNELS_LAST = True
 USE_FLIP_BWD = True
 
 
+_FLIP_DTYPES = (torch.float32, torch.bfloat16)
+
+
+def _flip_dtypes_ok(conv: nn.Conv2d, x: torch.Tensor) -> bool:
+    """_Conv3x3 casts its inputs to bf16 under any autocast (custom_fwd) and lss_conv_flip_weight takes
+    fp32 / bf16 only: x and the weight both fp32 or both bf16 with autocast off, or either of the two
+    under bf16 autocast (the trunk's bf16 maps meet fp32 weights there). fp16 / fp64 callers and fp16
+    autocast take conv(x)."""
+    if torch.is_autocast_enabled("cuda"):
+        return (torch.get_autocast_dtype("cuda") == torch.bfloat16 and x.dtype in _FLIP_DTYPES
+                and conv.weight.dtype in _FLIP_DTYPES)
+    return x.dtype == conv.weight.dtype and x.dtype in _FLIP_DTYPES
+
+
 def _flip_eligible(conv: nn.Conv2d, x: torch.Tensor) -> bool:
     return (USE_FLIP_BWD and x.is_cuda and x.dim() == 4 and conv.kernel_size == (3, 3) and conv.stride == (1, 1)
             and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None
-            and conv.padding_mode == "zeros" and torch.is_grad_enabled()
+            and conv.padding_mode == "zeros" and torch.is_grad_enabled() and _flip_dtypes_ok(conv, x)
             and (x.requires_grad or conv.weight.requires_grad))
 
 
@@ -315,7 +329,7 @@ class _Head1x1(torch.autograd.Function):
     def forward(ctx, x, weight, bias):
         lib = _lib.load()
         N, C, H, W = x.shape
-        x = x.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+        x = _lib.aligned(x.to(torch.bfloat16).contiguous(memory_format=torch.channels_last))  # 16-B rows
         w = weight.detach().to(torch.bfloat16).reshape(C).float()  # the bf16 operand, as fp32
         b = bias.detach().to(torch.bfloat16).float().reshape(1) if bias is not None else None
         y = torch.empty(N, 1, H, W, device=x.device, dtype=torch.bfloat16)
@@ -375,6 +389,7 @@ class _BnReluHead1(torch.autograd.Function):
         HW, P = H * W, N * H * W
         dev = x.device
         st = _lib.stream_handle(dev)
+        x = _lib.aligned(x)  # (the kernels read 16-B rows: a view at an odd storage offset is copied)
         groups = int(lib.lss_bn_groups(N, C, HW, norm.NHWC))
         f32 = dict(device=dev, dtype=torch.float32)
         partial = torch.empty(C, groups, 2, **f32)
@@ -432,7 +447,7 @@ def bn_relu_head1(bn: nn.BatchNorm2d, head: nn.Conv2d, x: torch.Tensor) -> torch
     BevEncode: training mode, channels-last bf16 under autocast), else bn_act + conv1x1."""
     C = x.shape[1] if x.dim() == 4 else 0
     ok = (USE_BN_HEAD and norm.USE_HIP_BN and USE_HIP_HEAD1 and bn.training and bn.affine and x.is_cuda
-          and x.dim() == 4 and x.dtype == torch.bfloat16 and x.is_contiguous(memory_format=torch.channels_last)
+          and norm.params_fp32(bn) and x.dim() == 4 and x.dtype == torch.bfloat16 and x.is_contiguous(memory_format=torch.channels_last)
           and head.out_channels == 1 and head.kernel_size == (1, 1) and head.stride == (1, 1) and head.groups == 1
           and C % 8 == 0 and 64 % (C // 8) == 0 and 256 % (C // 8) == 0 and _head1_eligible(head, x))
     if not ok:

@@ -72,10 +72,11 @@ class _BnAct(torch.autograd.Function):
         HW = H * W
         dev = x.device
         st = _lib.stream_handle(dev)
+        x = _lib.aligned(x)  # (a dense view at an odd storage offset: the vector loads need a copy)
         if residual is not None:
             residual = residual.to(x.dtype)
-            residual = residual.contiguous(memory_format=torch.channels_last if layout == NHWC else
-                                           torch.contiguous_format)
+            residual = _lib.aligned(residual.contiguous(memory_format=torch.channels_last if layout == NHWC else
+                                                        torch.contiguous_format))
         y = torch.empty_like(x)
         groups = int(lib.lss_bn_groups(N, C, HW, layout))
         f32 = dict(device=dev, dtype=torch.float32)
@@ -101,8 +102,8 @@ class _BnAct(torch.autograd.Function):
         act, layout, groups, has_res = ctx.conf
         N, C, H, W = x.shape
         dev = x.device
-        dy = dy.to(x.dtype).contiguous(memory_format=torch.channels_last if layout == NHWC else
-                                       torch.contiguous_format)
+        dy = _lib.aligned(dy.to(x.dtype).contiguous(memory_format=torch.channels_last if layout == NHWC else
+                                                    torch.contiguous_format))
         f32 = dict(device=dev, dtype=torch.float32)
         partial = torch.empty(C, groups, 2, **f32)
         coef = torch.empty(C, 2, **f32)
@@ -129,11 +130,19 @@ def _torch_bn_act(bn: nn.BatchNorm2d, x: torch.Tensor, act: str, residual: Optio
     return y
 
 
+def params_fp32(bn: nn.BatchNorm2d) -> bool:
+    """The lss_bn_* kernels read gamma / beta and update the running statistics as fp32 arrays (the
+    module as built, also under autocast); a module cast with ``bn.to(torch.bfloat16)`` / ``.half()`` /
+    ``.double()`` holds arrays of another element size and stays on the stock op."""
+    return all(t is None or (t.dtype == torch.float32 and t.is_contiguous())
+               for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var))
+
+
 def bn_act(bn: nn.BatchNorm2d, x: torch.Tensor, act: str = "none", residual: Optional[torch.Tensor] = None):
     """act(bn(x) [+ residual]) with act in {'none', 'relu', 'swish'}."""
     layout = _layout(x)
     use = (USE_HIP_BN and bn.training and x.is_cuda and x.dim() == 4 and layout is not None and bn.affine
-           and x.dtype in (torch.float32, torch.bfloat16)
+           and x.dtype in (torch.float32, torch.bfloat16) and params_fp32(bn)
            and (layout == NCHW or (x.shape[1] % 8 == 0 and 256 % (x.shape[1] // 8) == 0)))
     if not use:
         return _torch_bn_act(bn, x, act, residual)

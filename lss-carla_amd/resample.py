@@ -29,6 +29,7 @@ class _UpsampleCat(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, skip, Ho: int, Wo: int, chan_scale=None):
         lib = _lib.load()
+        x, skip = _lib.aligned(x), _lib.aligned(skip)  # (lss_upsample_* refuse pointers off 16 B)
         N, C1, Hi, Wi = x.shape
         C2 = skip.shape[1] if skip is not None else 0
         y = torch.empty(N, C2 + C1, Ho, Wo, device=x.device, dtype=torch.bfloat16,
@@ -44,7 +45,7 @@ class _UpsampleCat(torch.autograd.Function):
     def backward(ctx, dy):
         lib = _lib.load()
         N, Hi, Wi, C1, C2, Ho, Wo = ctx.geo
-        dy = dy.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+        dy = _lib.aligned(dy.to(torch.bfloat16).contiguous(memory_format=torch.channels_last))
         dx = torch.empty(N, C1, Hi, Wi, device=dy.device, dtype=torch.bfloat16, memory_format=torch.channels_last)
         (chan_scale,) = ctx.saved_tensors
         _lib.check(lib.lss_upsample_bwd2(_lib.ptr(dy), N, Hi, Wi, C1, C2, Ho, Wo, _lib.ptr(chan_scale), _lib.ptr(dx),

@@ -140,6 +140,59 @@ def test_bn_act_vs_fp64(N, C, H, W, layout, act, with_res, dtype):
     assert int(bn.num_batches_tracked) == 1
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("mode", ["cumulative", "untracked", "momentum0.1"])
+@pytest.mark.parametrize("N,C,H,W,layout", [(2, 16, 5, 7, "nchw"), (3, 24, 7, 9, "nchw"), (3, 16, 7, 9, "nhwc")])
+def test_bn_act_running_stat_modes_vs_fp64(N, C, H, W, layout, mode, dtype, monkeypatch):
+    """norm.running_args' other branches, over two consecutive steps on different batches: momentum=None
+    (cumulative average: factor 1 / num_batches_tracked, formed on the host), track_running_stats=False
+    (no running pointers, no counter) and an ordinary momentum applied twice. fp64 reference of the same
+    update; tolerances of test_bn_act_vs_fp64."""
+    g = torch.Generator().manual_seed(N * 1000 + C + H)
+    kw = {"cumulative": dict(momentum=None), "untracked": dict(track_running_stats=False),
+          "momentum0.1": dict(momentum=0.1)}[mode]
+    bn = torch.nn.BatchNorm2d(C, eps=1e-3, **kw).to(DEV).train()
+    tracked = mode != "untracked"
+    with torch.no_grad():
+        bn.weight.copy_(torch.rand(C, generator=g) + 0.5)
+        bn.bias.copy_(torch.randn(C, generator=g) * 0.1)
+        if tracked:
+            bn.running_mean.copy_(torch.randn(C, generator=g))
+            bn.running_var.copy_(torch.rand(C, generator=g) + 0.5)
+    rm = bn.running_mean.cpu().double() if tracked else None
+    rv = bn.running_var.cpu().double() if tracked else None
+    mf = torch.channels_last if layout == "nhwc" else torch.contiguous_format
+    tol = dict(rtol=1e-4, atol=1e-4) if dtype == torch.float32 else dict(rtol=2e-2, atol=3e-2)
+    gtol = dict(rtol=1e-3, atol=1e-2) if dtype == torch.float32 else dict(rtol=3e-2, atol=1.0)
+    launched = []
+    real = Nm._lib.check
+    monkeypatch.setattr(Nm._lib, "check", lambda code, what: (launched.append(what), real(code, what))[1])
+    for step in (1, 2):
+        x = (torch.randn(N, C, H, W, generator=g) * (1 + step) + 3 * step).to(dtype)
+        dy = torch.randn(N, C, H, W, generator=g).to(dtype)
+        bn.zero_grad(set_to_none=True)
+        xd = x.to(DEV).contiguous(memory_format=mf).requires_grad_(True)
+        y = Nm.bn_act(bn, xd, "swish")
+        y.backward(dy.to(DEV).contiguous(memory_format=mf))
+        mom = {"cumulative": 1.0 / step, "untracked": 0.0, "momentum0.1": 0.1}[mode]
+        xr = x.double().requires_grad_(True)
+        wr = bn.weight.detach().cpu().double().requires_grad_(True)
+        br = bn.bias.detach().cpu().double().requires_grad_(True)
+        yr = F.silu(F.batch_norm(xr, rm, rv, wr, br, training=True, momentum=mom, eps=bn.eps))  # rm, rv in place
+        yr.backward(dy.double())
+        torch.testing.assert_close(y.detach().cpu().double(), yr.detach(), **tol)
+        torch.testing.assert_close(xd.grad.cpu().double(), xr.grad, **tol)
+        torch.testing.assert_close(bn.weight.grad.cpu().double(), wr.grad, **gtol)
+        torch.testing.assert_close(bn.bias.grad.cpu().double(), br.grad, **gtol)
+        if tracked:
+            torch.testing.assert_close(bn.running_mean.cpu().double(), rm, rtol=1e-4, atol=1e-4)
+            torch.testing.assert_close(bn.running_var.cpu().double(), rv, rtol=1e-3, atol=1e-4)
+            assert int(bn.num_batches_tracked) == step
+    assert launched == ["lss_bn_fwd2", "lss_bn_bwd2"] * 2  # the kernels, not the stock fallback
+    if not tracked:
+        assert bn.running_mean is None and bn.running_var is None and bn.num_batches_tracked is None
+
+
 # ----------------------------------------------------------------------------- bilinear upsample + cat
 from lss_carla_amd import resample as R  # noqa: E402
 
@@ -217,6 +270,9 @@ SE_CASES = [  # (N, C, H, W, sq): MBConv blocks of the trunk at config-3 resolut
     (3, 96, 32, 88, 4),
     (6, 240, 16, 44, 10),
     (5, 1152, 4, 11, 48),
+    (2, 8, 2, 2, 1),        # sq = 1 (MBConv with in_f < 8) on the smallest plane the kernels take (HW = 4)
+    (1, 2048, 2, 2, 64),    # the limits squeeze_excite admits: C = 2048, sq = 64
+    (3, 72, 2, 6, 3),       # HW % 8 == 4, C past one 64-channel chunk, odd sq
 ]
 
 

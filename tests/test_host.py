@@ -296,3 +296,119 @@ def test_pointwise_conv_size_guard():
     assert E._pw_fits(48, 512, 105, 176)
     assert not E._pw_fits(4096, 1152, 192, 704)        # N * C * HW >= 2^31
     assert E._pw_fits(1, 2**20, 1, 2047) and not E._pw_fits(1, 2**20, 1, 2048)
+
+
+# ---- alignment backstop of the conv-stack C ABI (include/lss_convs.h): checked on the host before any
+# HIP call, so made-up addresses that are never dereferenced exercise it without a GPU
+_A = 0x10000  # a 16-B aligned fake address; arrays handed out 4 KiB apart
+_EINVAL = -1
+
+
+def _fake(i: int, off: int = 0) -> int:
+    return _A + 0x1000 * i + off
+
+
+def _bn_fwd(lib, x, y, dtype, layout, N, C, HW, res=None, gamma=None):
+    st = _fake(8)
+    return lib.lss_bn_fwd2(x, res, dtype, layout, N, C, HW, gamma or _fake(2), _fake(3), 1e-5, 0.1, _fake(4), _fake(5),
+                           _fake(6), 1, 1, _fake(7), st, st + 4 * C, st + 8 * C, st + 12 * C, y, None, None)
+
+
+def _bn_bwd(lib, dy, x, y, dx, dtype, layout, N, C, HW, dres=None):
+    st = _fake(8)
+    return lib.lss_bn_bwd2(dy, x, y, dtype, layout, N, C, HW, st + 8 * C, st + 12 * C, st, st + 4 * C, 1, 1, _fake(7),
+                           _fake(9), _fake(10), _fake(11), dx, dres, None, None)
+
+
+def test_bn_entry_points_refuse_bad_sizes_and_unaligned_pointers():
+    lib = _lib.load()
+    x, y, dy, dx = _fake(0), _fake(1), _fake(12), _fake(13)
+    F32, BF16, NCHW, NHWC = _lib.F32, _lib.BF16, _lib.NCHW, _lib.NHWC
+    # aligned pointers, bad sizes
+    for N, C, HW in ((0, 8, 24), (2, 0, 24), (2, 8, 0), (2, 8, -4), (1 << 15, 1 << 10, 1 << 6)):
+        assert _bn_fwd(lib, x, y, BF16, NCHW, N, C, HW) == _EINVAL
+        assert _bn_bwd(lib, dy, x, y, dx, BF16, NCHW, N, C, HW) == _EINVAL
+    # channels-last needs C % 8 == 0 (and 256 % (C / 8) == 0)
+    for C in (12, 4, 24):
+        assert _bn_fwd(lib, x, y, BF16, NHWC, 2, C, 15) == _EINVAL
+        assert _bn_bwd(lib, dy, x, y, dx, BF16, NHWC, 2, C, 15) == _EINVAL
+        assert lib.lss_bn_bwd_rank1(_fake(14), _fake(15), x, 2, C, 15, _fake(8) + 8 * C, _fake(8) + 12 * C, _fake(8),
+                                    _fake(8) + 4 * C, 1, 1, _fake(7), _fake(9), _fake(10), _fake(11), dx,
+                                    None) == _EINVAL
+    assert _bn_fwd(lib, x, y, 2, NCHW, 2, 8, 24) == _EINVAL  # unknown dtype
+    # good sizes, one activation pointer off the width the kernels pick for (dtype, layout, HW):
+    # bf16 NCHW HW % 8 == 0 -> 16 B; HW % 8 == 4 -> 8 B; fp32 HW % 4 == 0 -> 16 B; NHWC -> 16 B
+    cases = [(BF16, NCHW, 8, 24, (2, 4, 8)), (BF16, NCHW, 8, 12, (2, 4)), (F32, NCHW, 8, 24, (4, 8)),
+             (BF16, NHWC, 16, 15, (2, 4, 8)), (F32, NHWC, 16, 15, (4, 8)), (BF16, NCHW, 8, 15, (1,)),
+             (F32, NCHW, 8, 15, (2,))]
+    for dtype, layout, C, HW, offs in cases:
+        for off in offs:
+            assert _bn_fwd(lib, x + off, y, dtype, layout, 2, C, HW) == _EINVAL, (dtype, layout, HW, off)
+            assert _bn_fwd(lib, x, y + off, dtype, layout, 2, C, HW) == _EINVAL
+            assert _bn_fwd(lib, x, y, dtype, layout, 2, C, HW, res=_fake(14, off)) == _EINVAL
+            for k in range(5):
+                p = [dy, x, y, dx, _fake(14)]
+                p[k] += off
+                assert _bn_bwd(lib, p[0], p[1], p[2], p[3], dtype, layout, 2, C, HW, dres=p[4]) == _EINVAL, k
+    assert _bn_fwd(lib, x, y, BF16, NCHW, 2, 8, 24, gamma=_fake(2, 2)) == _EINVAL  # fp32 arrays: 4 B
+    st = _fake(8)
+    for k in (2, 16):  # x, dx of the rank-1 backward
+        a = [_fake(14), _fake(15), x, 2, 16, 15, st + 128, st + 192, st, st + 64, 1, 1, _fake(7), _fake(9), _fake(10),
+             _fake(11), dx, None]
+        a[k] += 2
+        assert lib.lss_bn_bwd_rank1(*a) == _EINVAL
+
+
+def test_se_and_head1_entry_points_refuse_bad_sizes_and_unaligned_pointers():
+    lib = _lib.load()
+    f = [_fake(i) for i in range(16)]
+
+    def se_fwd(x, y, N, C, HW, sq):
+        return lib.lss_se_fwd(x, N, C, HW, f[2], f[3], f[4], f[5], sq, f[6], f[7], f[8], f[9], y, None)
+
+    def se_bwd(dy, x, dx, N, C, HW, sq):
+        return lib.lss_se_bwd(dy, x, N, C, HW, f[2], f[4], sq, f[7], f[9], f[10], f[11], f[12], f[13], f[14], dx, None)
+
+    for N, C, HW, sq in ((2, 8, 6, 2), (2, 2056, 4, 2), (2, 8, 8, 65), (0, 8, 8, 2), (2, 8, 8, 0)):  # bad sizes
+        assert se_fwd(f[0], f[1], N, C, HW, sq) == _EINVAL
+        assert se_bwd(f[15], f[0], f[1], N, C, HW, sq) == _EINVAL
+    for off in (2, 4):  # four bf16 per access: 8 B
+        assert se_fwd(f[0] + off, f[1], 2, 8, 8, 2) == _EINVAL and se_fwd(f[0], f[1] + off, 2, 8, 8, 2) == _EINVAL
+        for k in range(3):
+            p = [f[15], f[0], f[1]]
+            p[k] += off
+            assert se_bwd(p[0], p[1], p[2], 2, 8, 8, 2) == _EINVAL
+
+    for P, C in ((0, 64), (10, 12), (10, 0), (10, 24 * 8), (10, 1024)):  # rows of C / 8 16-B vectors, 64 % (C / 8) == 0
+        assert lib.lss_head1_fwd2(f[0], f[2], None, P, C, None, f[1], None) == _EINVAL
+        assert lib.lss_head1_bwd2(f[0], f[3], f[2], P, C, None, f[1], f[4], None) == _EINVAL
+    for off in (2, 4, 8):
+        assert lib.lss_head1_fwd2(f[0] + off, f[2], None, 10, 64, None, f[1], None) == _EINVAL
+        assert lib.lss_head1_fwd(f[0] + off, f[2], None, 10, 64, f[1], None) == _EINVAL
+        assert lib.lss_head1_bwd2(f[0] + off, f[3], f[2], 10, 64, None, f[1], f[4], None) == _EINVAL
+        assert lib.lss_head1_bwd2(f[0], f[3], f[2], 10, 64, None, f[1] + off, f[4], None) == _EINVAL
+        assert lib.lss_head1_bwd(f[0], f[3], f[2], 10, 64, f[1] + off, f[4], None) == _EINVAL
+    assert lib.lss_head1_fwd2(f[0], f[2], None, 10, 64, None, f[1] + 1, None) == _EINVAL  # y / dy: bf16 elements
+    assert lib.lss_head1_bwd2(f[0], f[3] + 1, f[2], 10, 64, None, f[1], f[4], None) == _EINVAL
+
+
+def test_dwconv_entry_points_refuse_bad_sizes_and_unaligned_pointers():
+    lib = _lib.load()
+    f = [_fake(i) for i in range(8)]
+    good = (2, 8, 6, 8, 3, 1, 1, 1, 6, 8)  # N, C, Hi, Wi, K, stride, pad_top, pad_left, Ho, Wo
+
+    def calls(x, y, w, geo, dtype=_lib.BF16):
+        N = geo[0]
+        return (lib.lss_dwconv_fwd(x, dtype, w, *geo, y, None),
+                lib.lss_dwconv_bwd_data(y, dtype, w, *geo, x, None),
+                lib.lss_dwconv_bwd_weight(x, y, dtype, *geo, N, f[3], None),
+                lib.lss_dwconv_bwd_weight2(x, y, dtype, *geo, N, f[3], f[4], f[5], None))
+
+    for bad in ((2, 8, 6, 8, 4, 1, 1, 1, 6, 8), (2, 8, 6, 8, 3, 3, 1, 1, 6, 8), (0, 8, 6, 8, 3, 1, 1, 1, 6, 8),
+                (2, 8, 6, 8, 3, 1, 1, 1, 0, 8), (1 << 12, 1 << 12, 16, 16, 3, 1, 1, 1, 16, 16)):
+        assert calls(f[0], f[1], f[2], bad) == (_EINVAL,) * 4, bad
+    assert calls(f[0], f[1], f[2], good, dtype=2) == (_EINVAL,) * 4
+    for off in (2, 4, 8):
+        assert calls(f[0] + off, f[1], f[2], good) == (_EINVAL,) * 4
+        assert calls(f[0], f[1] + off, f[2], good) == (_EINVAL,) * 4
+        assert calls(f[0] + off, f[1], f[2], good, dtype=_lib.F32) == (_EINVAL,) * 4

@@ -78,6 +78,28 @@ int lss_head1_fwd2(const void* x, const float* w, const float* bias, int32_t P, 
 int lss_head1_bwd2(const void* x, const void* dy, const float* w, int32_t P, int32_t C, const float* bn_stats,
                    void* dx, float* partial, void* stream);
 
+/* (ABI 25) The same head with K = 2..8 output channels (a multi-class BevEncode, outC = K), x as above:
+ * channels-last bf16 rows (P, C), P = N * HW, C % 8 == 0 and 64 % (C / 8) == 0. The logits y and their
+ * gradient dy are NCHW contiguous (N, K, H, W) bf16 -- the layout the loss, the metric and the labels use --
+ * so row r = n * HW + q holds its K values at (n * K + k) * HW + q; HW and P need not be multiples of
+ * anything (a block of rows may straddle an image boundary).
+ *   y[n, k, q] = bf16(sum_c in[r, c] * w[k, c] + bias[k])    w (K, C) fp32 holding bf16-rounded weights,
+ *                                                            bias K device floats, nullable
+ *   dx[r, c]   = bf16(sum_k dy[n, k, q] * w[k, c])           fp32, k ascending, rounded once; always written
+ *   partial    (lss_head1_blocks(P), K, C + 1) fp32: per block of rows, sum_r dy[r, k] * in[r, c] and
+ *              (column C) sum_r dy[r, k]; the caller sums the blocks (fixed order)
+ * in = x, or with bn_stats (a batch norm's saved (4, C) statistics, as lss_head1_fwd2)
+ * bf16(relu(fmaf(x, scale, shift))) of the batch norm's INPUT x: the normalised map is never written, and
+ * dx is then the gradient of that map (lss_bn_bwd2's NHWC path with y = NULL takes it from there). Per
+ * channel k the arithmetic and its order are lss_head1_*'s: with w[k] = w1, bias[k] = b1 channel k of y is
+ * lss_head1_fwd2's output bit for bit, and a dy that is zero outside channel k gives lss_head1_bwd2's dx
+ * and partials. Alignment: x and dx 16 B; y and dy by element (2 B). One launch each; LSS_CONV_EINVAL
+ * (before any launch) for K outside 2..8, P % HW != 0 or a pointer that misses its alignment. */
+int lss_headk_fwd(const void* x, const float* w, const float* bias, int32_t P, int32_t HW, int32_t C, int32_t K,
+                  const float* bn_stats, void* y, void* stream);
+int lss_headk_bwd(const void* x, const void* dy, const float* w, int32_t P, int32_t HW, int32_t C, int32_t K,
+                  const float* bn_stats, void* dx, float* partial, void* stream);
+
 /* Weight gradient of a 1x1 convolution (no bias, stride 1) over NCHW contiguous bf16 activations:
  * dw (Cout, Cin) = sum over n < N, q < HW of dy[n][co][q] * x[n][ci][q], fp32 accumulation, written as
  * dw_dtype (LSS_CONV_BF16: rounded once; LSS_CONV_F32). HW % 4 == 0, 8-B aligned x / dy. workspace:
@@ -154,6 +176,25 @@ int lss_bce_logits_bwd(const void* grad, int32_t dtype, int64_t n, const float* 
 int lss_bce_iou_accum(const void* x, int32_t dtype, const float* target, int64_t per_sample, int32_t batch,
                       const int32_t* n_valid, float pos_weight, double* totals, void* partial, void* stream);
 int64_t lss_bce_iou_partial_bytes(int64_t n);
+
+/* (ABI 25) Per-class forms for logits (N, K, H, W) contiguous, plane = H * W: element i takes
+ * pw = pos_weight[(i / plane) % K], K floats in DEVICE memory (a captured graph replays with the current
+ * weights; BCEWithLogitsLoss(pos_weight = w.view(K, 1, 1)), mean over all n). plane need not be a multiple
+ * of 8: the weight is looked up per element. Otherwise lss_bce_logits -- same partition, per-element
+ * expression, fold, alignment, scratch (lss_bce_partials(n)) and two launches; with K equal weights, its
+ * loss and grad bit for bit. The backward is lss_bce_logits_bwd. */
+int lss_bce_logits_pc(const void* x, int32_t dtype, const float* target, int64_t n, int64_t plane, int32_t K,
+                      const float* pos_weight, float* partial, float* loss, void* grad, void* stream);
+/* lss_bce_iou_accum with the counts kept per class (per_sample = K * plane, K <= 32):
+ *   totals[0] += sum of l(x, t) / per_sample,  totals[1 + k] += intersection of class k,
+ *   totals[1 + K + k] += union of class k      (1 + 2 K doubles)
+ * partial: lss_bce_iou_pc_partial_bytes(batch * per_sample, K) bytes, 8-B aligned. Same n_valid masking,
+ * same fixed-order sums (integer counts, fp64 loss), two launches, capturable; K = 1 gives
+ * lss_bce_iou_accum's three totals bit for bit. */
+int lss_bce_iou_accum_pc(const void* x, int32_t dtype, const float* target, int64_t per_sample, int32_t batch,
+                         const int32_t* n_valid, int64_t plane, int32_t K, const float* pos_weight, double* totals,
+                         void* partial, void* stream);
+int64_t lss_bce_iou_pc_partial_bytes(int64_t n, int32_t K);
 
 /* out[c] = sum over (n, pixel) of x[n][c][pixel] (fp32, fixed order), x (N, C, HW) NCHW fp32 or bf16: the
  * bias gradient of the fused lift's depthnet conv (src/models.py:47) from d(logits). One launch. */

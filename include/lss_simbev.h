@@ -52,6 +52,17 @@ int lss_simbev_images(const uint8_t* src, int32_t n, int32_t src_h, int32_t src_
 int lss_simbev_vehicle_mask(const uint8_t* bev, int32_t n, int32_t n_classes, int32_t X, int32_t Y, float* out,
                             void* stream);
 
+/* (ABI 25) BEV labels by class group, for a multi-class head: out (n, K, X, Y) fp32, NCHW contiguous,
+ *   out[b, k, i, j] = any over the channels c of group k of (bev[b, c, X-1-i, j] > 0)
+ * -- get_binimg's merge and np.flipud, applied per group. group_bits: K bit masks over the npz channels in
+ * HOST memory (bit c = channel c), read here and passed to the kernel by value (no device allocation);
+ * 1 <= K <= LSS_SIMBEV_MAX_GROUPS, n_classes <= 32, every mask non-zero and within n_classes, else -1.
+ * One launch, coalesced along j; a pixel reads each channel some group names once, for all K groups.
+ * K = 1, group_bits = {0xE} gives lss_simbev_vehicle_mask's output. */
+#define LSS_SIMBEV_MAX_GROUPS 8
+int lss_simbev_class_masks(const uint8_t* bev, int32_t n, int32_t n_classes, int32_t X, int32_t Y,
+                           const uint32_t* group_bits, int32_t K, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

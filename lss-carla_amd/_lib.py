@@ -18,7 +18,7 @@ DEBUG_LIB_PATH = os.path.join(_HERE, "liblss_hip_debug.so")  # LSS_DEBUG=1: devi
 
 F32, BF16 = 0, 1
 NCHW, NHWC = 0, 1
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 
 class Dims(ctypes.Structure):
@@ -84,6 +84,7 @@ SIGNATURES = {
     "lss_resample_coeffs": (ctypes.c_int, [_i32, _i32, _p]),
     "lss_simbev_images": (ctypes.c_int, [_p, _i32, _i32, _i32, _p, _p, _i32, _i32, _p, _p]),
     "lss_simbev_vehicle_mask": (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _p, _p]),
+    "lss_simbev_class_masks": (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _p, _i32, _p, _p]),
     # include/lss_convs.h (conv-stack kernels, same library)
     "lss_dwconv_fwd": (ctypes.c_int, [_p, _i32, _p] + [_i32] * 10 + [_p, _p]),
     "lss_dwconv_bwd_data": (ctypes.c_int, [_p, _i32, _p] + [_i32] * 10 + [_p, _p]),
@@ -94,6 +95,12 @@ SIGNATURES = {
     "lss_head1_bwd": (ctypes.c_int, [_p, _p, _p, _i32, _i32, _p, _p, _p]),
     "lss_head1_fwd2": (ctypes.c_int, [_p, _p, _p, _i32, _i32, _p, _p, _p]),
     "lss_head1_bwd2": (ctypes.c_int, [_p, _p, _p, _i32, _i32, _p, _p, _p, _p]),
+    "lss_headk_fwd": (ctypes.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p]),
+    "lss_headk_bwd": (ctypes.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p]),
+    "lss_bce_logits_pc": (ctypes.c_int, [_p, _i32, _p, ctypes.c_int64, ctypes.c_int64, _i32, _p, _p, _p, _p, _p]),
+    "lss_bce_iou_accum_pc": (ctypes.c_int, [_p, _i32, _p, ctypes.c_int64, _i32, _p, ctypes.c_int64, _i32, _p, _p, _p,
+                                            _p]),
+    "lss_bce_iou_pc_partial_bytes": (ctypes.c_int64, [ctypes.c_int64, _i32]),
     "lss_bn_bwd_rank1": (ctypes.c_int, [_p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _i32, _i32, _p, _p, _p, _p, _p,
                                         _p]),
     "lss_scale_add": (ctypes.c_int, [_p, _p, ctypes.c_float, _p, ctypes.c_int64, ctypes.c_int64, _p, _p]),

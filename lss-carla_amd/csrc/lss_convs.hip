@@ -1296,6 +1296,172 @@ __global__ __launch_bounds__(kBlock) void k_head1_bwd(const uint4* __restrict__ 
         partial[(size_t)blockIdx.x * (C + 1) + c] = ((s_part[0][c] + s_part[1][c]) + s_part[2][c]) + s_part[3][c];
 }
 
+// ---- The same 1x1 convolution to K = 2..8 output channels (a multi-class BevEncode: up2.4 with outC = K).
+// Rows in, K NCHW planes out: y / dy are (N, K, H, W) contiguous, so a block's 256 rows x K values cross
+// LDS and reach memory as K runs along the pixel axis (a block may straddle an image boundary: row r is
+// pixel q = r % HW of image n = r / HW, at (n K + k) HW + q). Per channel k the arithmetic is k_head1_*'s,
+// instruction for instruction: the 8 fmas in channel order, the same butterflies, the same fold of the
+// waves -- the lane keeps its 8 channels x K weights in registers and reads each row once for all K.
+template <int LPR, int K>
+__global__ __launch_bounds__(kBlock) void k_headk_fwd(const uint4* __restrict__ x, const float* __restrict__ w,
+                                                      const float* __restrict__ bias, int P, int HW,
+                                                      bf16* __restrict__ y, const float* __restrict__ bnst) {
+    constexpr int RPI = kWave / LPR;
+    constexpr int C = LPR * 8;
+    __shared__ bf16 s_y[K][kHeadRows];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int col = lane % LPR, sub = lane / LPR;
+    float wv[K][8], sc[8], sh[8], b[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) wv[k][i] = w[k * C + col * 8 + i];
+        b[k] = bias ? bias[k] : 0.f;
+    }
+    const bool bn = bnst != nullptr;
+    head_bn8(bnst, C, col * 8, sc, sh);
+    const int l0 = wave * (kHeadRows / 4);
+    const int r0 = blockIdx.x * kHeadRows + l0;
+#pragma unroll 4
+    for (int it = 0; it < kHeadRows / 4 / RPI; ++it) {
+        const int r = r0 + it * RPI + sub;
+        float acc[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) acc[k] = 0.f;
+        if (r < P) {
+            const uint4 v = x[(size_t)r * LPR + col];
+            const unsigned u[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float lo = head_in(__uint_as_float(u[i] << 16), bn, sc[2 * i], sh[2 * i]);
+                const float hi = head_in(__uint_as_float(u[i] & 0xFFFF0000u), bn, sc[2 * i + 1], sh[2 * i + 1]);
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    acc[k] = fmaf(lo, wv[k][2 * i], acc[k]);
+                    acc[k] = fmaf(hi, wv[k][2 * i + 1], acc[k]);
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+#pragma unroll
+            for (int o = LPR / 2; o > 0; o >>= 1) acc[k] += __shfl_xor(acc[k], o, kWave);
+        }
+        if (col == 0) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) s_y[k][l0 + it * RPI + sub] = __float2bfloat16(acc[k] + b[k]);
+        }
+    }
+    __syncthreads();
+    const int r = blockIdx.x * kHeadRows + threadIdx.x;  // thread = row: each plane's run is contiguous in q
+    if (r < P) {
+        const int n = r / HW, q = r - n * HW;
+        bf16* o = y + (size_t)n * K * HW + q;
+#pragma unroll
+        for (int k = 0; k < K; ++k) o[(size_t)k * HW] = s_y[k][threadIdx.x];
+    }
+}
+
+// dx[r, c] = bf16(sum_k dy[r, k] w[k, c]) (fp32, k ascending); partial[block][k][c] = sum over the block's
+// rows of dy[r, k] in[r, c], partial[block][k][C] = sum of dy[r, k] -- k_head1_bwd's row partition and
+// reduction order per channel k.
+template <int LPR, int K>
+__global__ __launch_bounds__(kBlock) void k_headk_bwd(const uint4* __restrict__ x, const bf16* __restrict__ dy,
+                                                      const float* __restrict__ w, int P, int HW,
+                                                      uint4* __restrict__ dx, float* __restrict__ partial,
+                                                      const float* __restrict__ bnst) {
+    constexpr int RPI = kWave / LPR;
+    constexpr int C = LPR * 8;
+    __shared__ float s_dy[K][kHeadRows];
+    __shared__ float s_part[K][C + 1];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int col = lane % LPR, sub = lane / LPR;
+    {
+        const int r = blockIdx.x * kHeadRows + threadIdx.x;
+        const int n = r < P ? r / HW : 0, q = r < P ? r - n * HW : 0;
+        const bf16* g = dy + (size_t)n * K * HW + q;
+#pragma unroll
+        for (int k = 0; k < K; ++k) s_dy[k][threadIdx.x] = r < P ? __bfloat162float(g[(size_t)k * HW]) : 0.f;
+    }
+    float wv[K][8], acc[K][8], dsum[K], sc[8], sh[8];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            wv[k][i] = w[k * C + col * 8 + i];
+            acc[k][i] = 0.f;
+        }
+        dsum[k] = 0.f;
+    }
+    const bool bn = bnst != nullptr;
+    head_bn8(bnst, C, col * 8, sc, sh);
+    const int l0 = wave * (kHeadRows / 4);
+    const int r0 = blockIdx.x * kHeadRows + l0;
+    __syncthreads();
+#pragma unroll 2
+    for (int it = 0; it < kHeadRows / 4 / RPI; ++it) {
+        const int l = l0 + it * RPI + sub;
+        const int r = r0 + it * RPI + sub;
+        if (r < P) {
+            float g[K];
+#pragma unroll
+            for (int k = 0; k < K; ++k) g[k] = s_dy[k][l];
+            const uint4 v = x[(size_t)r * LPR + col];
+            const unsigned u[4] = {v.x, v.y, v.z, v.w};
+            unsigned o[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float lo = head_in(__uint_as_float(u[i] << 16), bn, sc[2 * i], sh[2 * i]);
+                const float hi = head_in(__uint_as_float(u[i] & 0xFFFF0000u), bn, sc[2 * i + 1], sh[2 * i + 1]);
+                float da = g[0] * wv[0][2 * i], dc = g[0] * wv[0][2 * i + 1];
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    acc[k][2 * i] = fmaf(g[k], lo, acc[k][2 * i]);
+                    acc[k][2 * i + 1] = fmaf(g[k], hi, acc[k][2 * i + 1]);
+                    if (k > 0) {
+                        da = fmaf(g[k], wv[k][2 * i], da);
+                        dc = fmaf(g[k], wv[k][2 * i + 1], dc);
+                    }
+                }
+                const bf16 a = __float2bfloat16(da), c = __float2bfloat16(dc);
+                o[i] = (unsigned)*reinterpret_cast<const unsigned short*>(&a) |
+                       ((unsigned)*reinterpret_cast<const unsigned short*>(&c) << 16);
+            }
+            dx[(size_t)r * LPR + col] = make_uint4(o[0], o[1], o[2], o[3]);
+            if (col == 0) {
+#pragma unroll
+                for (int k = 0; k < K; ++k) dsum[k] += g[k];
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+#pragma unroll
+            for (int off = LPR; off < kWave; off <<= 1) acc[k][i] += __shfl_xor(acc[k][i], off, kWave);
+#pragma unroll
+        for (int off = LPR; off < kWave; off <<= 1) dsum[k] += __shfl_xor(dsum[k], off, kWave);
+    }
+    // the waves in order into one LDS copy, ((w0 + w1) + w2) + w3 as k_head1_bwd folds its four
+    for (int v = 0; v < kBlock / kWave; ++v) {
+        if (wave == v && sub == 0) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    float* p = &s_part[k][col * 8 + i];
+                    *p = v == 0 ? acc[k][i] : *p + acc[k][i];
+                }
+                if (col == 0) s_part[k][C] = v == 0 ? dsum[k] : s_part[k][C] + dsum[k];
+            }
+        }
+        __syncthreads();
+    }
+    for (int e = threadIdx.x; e < K * (C + 1); e += kBlock)
+        partial[(size_t)blockIdx.x * K * (C + 1) + e] = (&s_part[0][0])[e];
+}
+
 // ----------------------------------------------------------------------------- per-sample scale (+ add)
 // y = bf16(x * scale[n] (+ r)) over sample-major bf16 tensors, scale[n] from the sample's draw, 8 elements (16 B) per thread: the
 // MBConv residual with stochastic depth (efficientnet_pytorch drop_connect, x / keep * mask +
@@ -1986,6 +2152,176 @@ __global__ __launch_bounds__(kBlock) void k_bce_iou_fold(const BceIouPartial* __
         totals[2] += (double)u;
     }
 }
+
+// ---- The per-class forms (multi-class BEV: logits (N, K, H, W) contiguous, plane = H W): element i belongs
+// to class (i / plane) % K and takes pos_weight[class] from device memory (a captured graph replays with
+// the current weights). A thread's 8 elements may cross a plane boundary (plane % 8 != 0), so the class is
+// walked per element: one division per thread, then increments. Partition, per-element expression and
+// folds are k_bce_fwd's / k_bce_iou's, so equal weights (K = 1 for the metrics) give the same bits.
+struct ClassWalk {
+    long long rem, plane;  // position inside the plane
+    int k, K;
+    __device__ ClassWalk(long long i0, long long plane_, int K_) : plane(plane_), K(K_) {
+        const long long p = i0 / plane_;
+        rem = i0 - p * plane_;
+        k = (int)(p % K_);
+    }
+    __device__ __forceinline__ void next() {
+        if (++rem == plane) {
+            rem = 0;
+            k = k + 1 == K ? 0 : k + 1;
+        }
+    }
+};
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_bce_fwd_pc(const T* __restrict__ x, const float* __restrict__ t,
+                                                       long long n, long long plane, int K,
+                                                       const float* __restrict__ pwc, float inv_n,
+                                                       float* __restrict__ partial, T* __restrict__ grad) {
+    __shared__ float s_w[kBlock / kWave];
+    const long long i0 = ((long long)blockIdx.x * kBlock + threadIdx.x) * kBceVpt;
+    float xv[kBceVpt], tv[kBceVpt], gv[kBceVpt];
+    const bool full = i0 + kBceVpt <= n;
+    if (full) {
+        ldv8(x + i0, xv);
+        const float4 a = *reinterpret_cast<const float4*>(t + i0), b = *reinterpret_cast<const float4*>(t + i0 + 4);
+        tv[0] = a.x; tv[1] = a.y; tv[2] = a.z; tv[3] = a.w; tv[4] = b.x; tv[5] = b.y; tv[6] = b.z; tv[7] = b.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < kBceVpt; ++j) {
+            xv[j] = i0 + j < n ? ld(x + i0 + j) : 0.f;
+            tv[j] = i0 + j < n ? t[i0 + j] : 0.f;
+        }
+    }
+    ClassWalk cw(i0, plane, K);
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < kBceVpt; ++j) {
+        const float xx = xv[j], tt = tv[j];
+        const float pw = pwc[cw.k];
+        cw.next();
+        const float lw = fmaf(pw - 1.f, tt, 1.f);
+        const float e = expf(-fabsf(xx));
+        const float l = (1.f - tt) * xx + lw * (log1pf(e) + fmaxf(-xx, 0.f));
+        const float sp = 1.f / (1.f + e), sn = e / (1.f + e);  // sigmoid(|x|), sigmoid(-|x|)
+        const float sx = xx >= 0.f ? sp : sn, smx = xx >= 0.f ? sn : sp;
+        gv[j] = ((1.f - tt) * sx - pw * tt * smx) * inv_n;
+        if (i0 + j < n) s += l;
+    }
+    if (full) stv8(grad + i0, gv);
+    else {
+#pragma unroll
+        for (int j = 0; j < kBceVpt; ++j)
+            if (i0 + j < n) st1(grad + i0 + j, gv[j]);
+    }
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, kWave);
+    if ((threadIdx.x & (kWave - 1)) == 0) s_w[threadIdx.x / kWave] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float b = 0.f;
+#pragma unroll
+        for (int w = 0; w < kBlock / kWave; ++w) b += s_w[w];
+        partial[blockIdx.x] = b;
+    }
+}
+
+// Block record of the per-class metrics: partial = nb doubles (the loss terms, k_bce_iou's fp64 sum), then
+// nb x 2K int32 (intersection counts of the K classes, then union counts). A thread counts a run of one class
+// in registers and adds it to the block's LDS counters when the class changes (integer adds: any order).
+constexpr int kIouMaxClasses = 32;
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_bce_iou_pc(const T* __restrict__ x, const float* __restrict__ t,
+                                                       long long per_sample, int batch, const int* __restrict__ n_valid,
+                                                       long long plane, int K, const float* __restrict__ pwc, int vec,
+                                                       double* __restrict__ ploss, int* __restrict__ pcount) {
+    __shared__ double s_l[kBlock / kWave];
+    __shared__ int s_c[2 * kIouMaxClasses];
+    if (threadIdx.x < 2 * K) s_c[threadIdx.x] = 0;
+    __syncthreads();
+    int nv = n_valid ? n_valid[0] : batch;
+    nv = nv < 0 ? 0 : (nv > batch ? batch : nv);
+    const long long limit = (long long)nv * per_sample;
+    const long long i0 = ((long long)blockIdx.x * kBlock + threadIdx.x) * kBceVpt;
+    double s = 0.0;
+    if (i0 < limit) {
+        float xv[kBceVpt], tv[kBceVpt];
+        if (vec && i0 + kBceVpt <= limit) {
+            ldv8(x + i0, xv);
+            const float4 a = *reinterpret_cast<const float4*>(t + i0), b = *reinterpret_cast<const float4*>(t + i0 + 4);
+            tv[0] = a.x; tv[1] = a.y; tv[2] = a.z; tv[3] = a.w; tv[4] = b.x; tv[5] = b.y; tv[6] = b.z; tv[7] = b.w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < kBceVpt; ++j) {
+                xv[j] = i0 + j < limit ? ld(x + i0 + j) : 0.f;
+                tv[j] = i0 + j < limit ? t[i0 + j] : 0.f;
+            }
+        }
+        ClassWalk cw(i0, plane, K);
+        int ni = 0, nu = 0;
+#pragma unroll
+        for (int j = 0; j < kBceVpt; ++j) {
+            const float xx = xv[j], tt = tv[j];
+            const int k = cw.k;
+            const float pw = pwc[k];
+            cw.next();
+            const float lw = fmaf(pw - 1.f, tt, 1.f);
+            const float e = expf(-fabsf(xx));
+            const float l = (1.f - tt) * xx + lw * (log1pf(e) + fmaxf(-xx, 0.f));
+            if (i0 + j < limit) {
+                s += (double)l;
+                const bool p = xx > 0.f, q = tt != 0.f;
+                ni += (p && q) ? 1 : 0;
+                nu += (p || q) ? 1 : 0;
+            }
+            if (j == kBceVpt - 1 || cw.k != k) {  // the run of class k ends here
+                if (ni) atomicAdd(&s_c[k], ni);
+                if (nu) atomicAdd(&s_c[K + k], nu);
+                ni = nu = 0;
+            }
+        }
+    }
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, kWave);
+    if ((threadIdx.x & (kWave - 1)) == 0) s_l[threadIdx.x / kWave] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double l = 0.0;
+#pragma unroll
+        for (int w = 0; w < kBlock / kWave; ++w) l += s_l[w];
+        ploss[blockIdx.x] = l;
+    }
+    if (threadIdx.x < 2 * K) pcount[(size_t)blockIdx.x * 2 * K + threadIdx.x] = s_c[threadIdx.x];
+}
+
+// totals[0] += the loss records folded as k_bce_iou_fold folds them; totals[1 + k] += intersection of class k,
+// totals[1 + K + k] += its union (wave w sums the counters w, w + 4, ... over the blocks: integers).
+__global__ __launch_bounds__(kBlock) void k_bce_iou_fold_pc(const double* __restrict__ ploss,
+                                                            const int* __restrict__ pcount, int nb, int K,
+                                                            double per_sample, double* __restrict__ totals) {
+    __shared__ double s_l[kBlock / kWave];
+    double s = 0.0;
+    for (int b = threadIdx.x; b < nb; b += kBlock) s += ploss[b];
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, kWave);
+    if ((threadIdx.x & (kWave - 1)) == 0) s_l[threadIdx.x / kWave] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double l = 0.0;
+#pragma unroll
+        for (int w = 0; w < kBlock / kWave; ++w) l += s_l[w];
+        totals[0] += l / per_sample;
+    }
+    const int lane = threadIdx.x & (kWave - 1);
+    for (int c = threadIdx.x / kWave; c < 2 * K; c += kBlock / kWave) {
+        long long a = 0;
+        for (int b = lane; b < nb; b += kWave) a += pcount[(size_t)b * 2 * K + c];
+#pragma unroll
+        for (int o = kWave / 2; o > 0; o >>= 1) a += __shfl_xor(a, o, kWave);
+        if (lane == 0) totals[1 + c] += (double)a;
+    }
+}
 }  // namespace
 
 extern "C" {
@@ -2046,6 +2382,64 @@ int lss_head1_bwd2(const void* x, const void* dy, const float* w, int32_t P, int
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
 }
+
+namespace {
+bool headk_args_ok(int32_t P, int32_t HW, int32_t C, int32_t K) {
+    return P > 0 && HW > 0 && P % HW == 0 && C > 0 && C % 8 == 0 && 64 % (C / 8) == 0 && K >= 2 && K <= 8;
+}
+// the <lanes per row, K> instance: LSS_HEADK(L, K) launches it
+#define LSS_HEADK_K(L)          \
+    switch (K) {                \
+        case 2: LSS_HEADK(L, 2); break; \
+        case 3: LSS_HEADK(L, 3); break; \
+        case 4: LSS_HEADK(L, 4); break; \
+        case 5: LSS_HEADK(L, 5); break; \
+        case 6: LSS_HEADK(L, 6); break; \
+        case 7: LSS_HEADK(L, 7); break; \
+        default: LSS_HEADK(L, 8); break; \
+    }
+#define LSS_HEADK_DISPATCH()                  \
+    switch (C / 8) {                          \
+        case 16: LSS_HEADK_K(16); break;      \
+        case 8: LSS_HEADK_K(8); break;        \
+        case 32: LSS_HEADK_K(32); break;      \
+        case 64: LSS_HEADK_K(64); break;      \
+        case 4: LSS_HEADK_K(4); break;        \
+        case 2: LSS_HEADK_K(2); break;        \
+        case 1: LSS_HEADK_K(1); break;        \
+        default: return LSS_CONV_EINVAL;      \
+    }
+}  // namespace
+
+int lss_headk_fwd(const void* x, const float* w, const float* bias, int32_t P, int32_t HW, int32_t C, int32_t K,
+                  const float* bn_stats, void* y, void* stream) {
+    if (!x || !w || !y || !headk_args_ok(P, HW, C, K)) return LSS_CONV_EINVAL;
+    if (!aligned16(x) || (reinterpret_cast<uintptr_t>(y) & 1)) return LSS_CONV_EINVAL;  // uint4 rows; y by element
+    const dim3 gr(lss_head1_blocks(P)), bl(kBlock);
+    hipStream_t s = (hipStream_t)stream;
+#define LSS_HEADK(L, KK) \
+    hipLaunchKernelGGL((k_headk_fwd<L, KK>), gr, bl, 0, s, (const uint4*)x, w, bias, P, HW, (bf16*)y, bn_stats)
+    LSS_HEADK_DISPATCH()
+#undef LSS_HEADK
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+int lss_headk_bwd(const void* x, const void* dy, const float* w, int32_t P, int32_t HW, int32_t C, int32_t K,
+                  const float* bn_stats, void* dx, float* partial, void* stream) {
+    if (!x || !dy || !w || !dx || !partial || !headk_args_ok(P, HW, C, K)) return LSS_CONV_EINVAL;
+    if (!aligned16(x, dx) || (reinterpret_cast<uintptr_t>(dy) & 1)) return LSS_CONV_EINVAL;
+    const dim3 gr(lss_head1_blocks(P)), bl(kBlock);
+    hipStream_t s = (hipStream_t)stream;
+#define LSS_HEADK(L, KK)                                                                                             \
+    hipLaunchKernelGGL((k_headk_bwd<L, KK>), gr, bl, 0, s, (const uint4*)x, (const bf16*)dy, w, P, HW, (uint4*)dx, \
+                       partial, bn_stats)
+    LSS_HEADK_DISPATCH()
+#undef LSS_HEADK
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+#undef LSS_HEADK_DISPATCH
+#undef LSS_HEADK_K
 
 // split count of lss_pw_wrw: about 512 blocks (2 per CU) and >= 2 K steps per wave, at most
 // kPwMaxSplit, and the fp32 partials at most half the activation bytes (or one split)
@@ -2383,5 +2777,60 @@ int lss_bce_iou_accum(const void* x, int32_t dtype, const float* target, int64_t
 }
 
 int64_t lss_bce_partials(int64_t n) { return (n + (int64_t)kBlock * kBceVpt - 1) / ((int64_t)kBlock * kBceVpt); }
+
+int lss_bce_logits_pc(const void* x, int32_t dtype, const float* target, int64_t n, int64_t plane, int32_t K,
+                      const float* pos_weight, float* partial, float* loss, void* grad, void* stream) {
+    const int esz = dtype == LSS_CONV_BF16 ? 2 : dtype == LSS_CONV_F32 ? 4 : 0;
+    if (!x || !target || !pos_weight || !partial || !loss || !grad || !esz || n <= 0 || plane <= 0 || K <= 0 ||
+        ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(grad)) & 15) ||
+        (reinterpret_cast<uintptr_t>(target) & 15))
+        return LSS_CONV_EINVAL;
+    const long long nb = (n + (long long)kBlock * kBceVpt - 1) / ((long long)kBlock * kBceVpt);
+    if (nb > INT_MAX) return LSS_CONV_EINVAL;
+    const float inv_n = 1.0f / (float)n;
+    hipStream_t s = (hipStream_t)stream;
+    if (esz == 2)
+        hipLaunchKernelGGL(k_bce_fwd_pc<bf16>, dim3((unsigned)nb), dim3(kBlock), 0, s, (const bf16*)x, target,
+                           (long long)n, (long long)plane, (int)K, pos_weight, inv_n, partial, (bf16*)grad);
+    else
+        hipLaunchKernelGGL(k_bce_fwd_pc<float>, dim3((unsigned)nb), dim3(kBlock), 0, s, (const float*)x, target,
+                           (long long)n, (long long)plane, (int)K, pos_weight, inv_n, partial, (float*)grad);
+    hipLaunchKernelGGL(k_bce_total, dim3(1), dim3(kWave), 0, s, partial, (int)nb, inv_n, loss);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+int64_t lss_bce_iou_pc_partial_bytes(int64_t n, int32_t K) {
+    return n <= 0 || K <= 0 ? 0 : lss_bce_partials(n) * (int64_t)(sizeof(double) + 2 * (size_t)K * sizeof(int));
+}
+
+int lss_bce_iou_accum_pc(const void* x, int32_t dtype, const float* target, int64_t per_sample, int32_t batch,
+                         const int32_t* n_valid, int64_t plane, int32_t K, const float* pos_weight, double* totals,
+                         void* partial, void* stream) {
+    const int esz = dtype == LSS_CONV_BF16 ? 2 : dtype == LSS_CONV_F32 ? 4 : 0;
+    if (!x || !target || !pos_weight || !totals || !partial || !esz || per_sample <= 0 || batch <= 0 || plane <= 0 ||
+        K <= 0 || K > kIouMaxClasses || per_sample != plane * K || per_sample > LLONG_MAX / batch ||
+        (reinterpret_cast<uintptr_t>(partial) & 7) || (reinterpret_cast<uintptr_t>(totals) & 7))
+        return LSS_CONV_EINVAL;
+    const long long n = (long long)per_sample * batch;
+    const long long nb = (n + (long long)kBlock * kBceVpt - 1) / ((long long)kBlock * kBceVpt);
+    if (nb > INT_MAX) return LSS_CONV_EINVAL;
+    const int vec = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(target)) & 15) == 0;
+    hipStream_t s = (hipStream_t)stream;
+    double* pl = (double*)partial;
+    int* pc = (int*)(pl + nb);
+    if (esz == 2)
+        hipLaunchKernelGGL(k_bce_iou_pc<bf16>, dim3((unsigned)nb), dim3(kBlock), 0, s, (const bf16*)x, target,
+                           (long long)per_sample, (int)batch, (const int*)n_valid, (long long)plane, (int)K, pos_weight,
+                           vec, pl, pc);
+    else
+        hipLaunchKernelGGL(k_bce_iou_pc<float>, dim3((unsigned)nb), dim3(kBlock), 0, s, (const float*)x, target,
+                           (long long)per_sample, (int)batch, (const int*)n_valid, (long long)plane, (int)K, pos_weight,
+                           vec, pl, pc);
+    hipLaunchKernelGGL(k_bce_iou_fold_pc, dim3(1), dim3(kBlock), 0, s, (const double*)pl, (const int*)pc, (int)nb, (int)K,
+                       (double)per_sample, totals);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
 
 }  // extern "C"

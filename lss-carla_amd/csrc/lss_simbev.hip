@@ -133,6 +133,32 @@ __global__ __launch_bounds__(kThreads) void k_vehicle_mask(const uint8_t* __rest
     out[i] = v ? 1.0f : 0.0f;
 }
 
+// K class groups of one BEV, flipud per group: out[b, k, i, j] = any(bev[b, c, X-1-i, j] > 0 for c in group k).
+// Thread = pixel (consecutive threads along j: coalesced byte reads and fp32 writes); it reads each channel
+// some group names once, as a bit of `set`, and writes its K values, one per output plane. The groups are
+// bit masks over the channels, passed in the kernel arguments.
+struct ClassGroups {
+    uint32_t bits[LSS_SIMBEV_MAX_GROUPS];
+};
+__global__ __launch_bounds__(kThreads) void k_class_masks(const uint8_t* __restrict__ bev, int ncls, int X, int Y,
+                                                          long total, ClassGroups groups, uint32_t used, int K,
+                                                          float* __restrict__ out) {
+    const long i = (long)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= total) return;
+    const long XY = (long)X * Y;
+    const long b = i / XY;
+    const long r = i - b * XY;
+    const int row = (int)(r / Y), col = (int)(r - (long)row * Y);
+    const uint8_t* s = bev + (size_t)b * ncls * XY + (size_t)(X - 1 - row) * Y + col;
+    uint32_t set = 0;
+    for (int c = 0; c < ncls; ++c)
+        if ((used >> c) & 1u) set |= (s[(size_t)c * XY] > 0 ? 1u : 0u) << c;
+    float* o = out + (size_t)b * K * XY + r;
+#pragma unroll
+    for (int k = 0; k < LSS_SIMBEV_MAX_GROUPS; ++k)
+        if (k < K) o[(size_t)k * XY] = (set & groups.bits[k]) ? 1.0f : 0.0f;
+}
+
 // ---- host: Pillow's bicubic coefficient tables (Resample.c precompute_coeffs / normalize_coeffs_8bpc)
 double bicubic_filter(double x) {
     const double a = -0.5;
@@ -212,6 +238,26 @@ int lss_simbev_vehicle_mask(const uint8_t* bev, int32_t n, int32_t n_classes, in
     const long total = (long)n * X * Y;
     hipLaunchKernelGGL(k_vehicle_mask, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0,
                        (hipStream_t)stream, bev, n_classes, X, Y, total, out);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+int lss_simbev_class_masks(const uint8_t* bev, int32_t n, int32_t n_classes, int32_t X, int32_t Y,
+                           const uint32_t* group_bits, int32_t K, float* out, void* stream) {
+    if (!bev || !out || !group_bits || n <= 0 || n_classes <= 0 || n_classes > 32 || X <= 0 || Y <= 0 || K <= 0 ||
+        K > LSS_SIMBEV_MAX_GROUPS)
+        return -1;
+    const uint32_t valid = n_classes == 32 ? 0xFFFFFFFFu : ((1u << n_classes) - 1u);
+    ClassGroups g{};
+    uint32_t used = 0;
+    for (int k = 0; k < K; ++k) {
+        if (group_bits[k] == 0 || (group_bits[k] & ~valid)) return -1;  // an empty group, a channel out of range
+        g.bits[k] = group_bits[k];
+        used |= group_bits[k];
+    }
+    const long total = (long)n * X * Y;
+    hipLaunchKernelGGL(k_class_masks, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+                       (hipStream_t)stream, bev, n_classes, X, Y, total, g, used, K, out);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
 }

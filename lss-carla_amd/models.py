@@ -442,17 +442,165 @@ class _BnReluHead1(torch.autograd.Function):
         return dx, dgamma, dbeta, dw, db, None
 
 
-def bn_relu_head1(bn: nn.BatchNorm2d, head: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
-    """head(relu(bn(x))) with head a 1x1 conv to one channel: _BnReluHead1 where eligible (the benched
-    BevEncode: training mode, channels-last bf16 under autocast), else bn_act + conv1x1."""
+# BevEncode's last conv with 2..8 output channels (a multi-class model, outC = K) on lss_headk_*; off: the
+# generic path (bn_act + F.linear), which writes the normalised map and runs the small-M weight-gradient GEMM
+USE_HIP_HEADK = True
+HEADK_MAX = 8
+
+
+def logits_head(conv: nn.Conv2d) -> nn.Conv2d:
+    """Mark a 1x1 conv as a model's logits head (BevEncode marks its last conv): conv1x1 / bn_relu_head1 may
+    then return its output NCHW contiguous from lss_headk_* instead of the channels-last-strided result
+    of the generic path. Same values either way; an unmarked conv keeps conv1x1's documented result, strides
+    included (tests/test_gpu_dispatch.py pins it for a two-output conv)."""
+    conv.lss_logits_head = True
+    return conv
+
+
+def _headk_eligible(conv: nn.Conv2d, x: torch.Tensor) -> bool:
+    """_head1_eligible's conditions for 2 <= out_channels <= 8, on a conv marked by logits_head."""
     C = x.shape[1] if x.dim() == 4 else 0
-    ok = (USE_BN_HEAD and norm.USE_HIP_BN and USE_HIP_HEAD1 and bn.training and bn.affine and x.is_cuda
-          and norm.params_fp32(bn) and x.dim() == 4 and x.dtype == torch.bfloat16 and x.is_contiguous(memory_format=torch.channels_last)
-          and head.out_channels == 1 and head.kernel_size == (1, 1) and head.stride == (1, 1) and head.groups == 1
-          and C % 8 == 0 and 64 % (C // 8) == 0 and 256 % (C // 8) == 0 and _head1_eligible(head, x))
-    if not ok:
-        return conv1x1(head, bn_act(bn, x, "relu"))
-    return _BnReluHead1.apply(x, bn.weight, bn.bias, head.weight, head.bias, bn)
+    bf16 = x.dtype == torch.bfloat16 or (torch.is_autocast_enabled("cuda")
+                                          and torch.get_autocast_dtype("cuda") == torch.bfloat16)
+    return (USE_HIP_HEADK and getattr(conv, "lss_logits_head", False) and 2 <= conv.out_channels <= HEADK_MAX
+            and x.is_cuda and x.dim() == 4 and bf16
+            and C % 8 == 0 and C // 8 > 0 and 64 % (C // 8) == 0
+            and x.is_contiguous(memory_format=torch.channels_last))
+
+
+def _headk_params(weight, bias, K, C):
+    """The head's bf16 operands as fp32 arrays ((K, C) and (K,)), as _Head1x1 takes its own."""
+    w = weight.detach().to(torch.bfloat16).reshape(K, C).float().contiguous()
+    b = bias.detach().to(torch.bfloat16).float().reshape(K).contiguous() if bias is not None else None
+    return w, b
+
+
+def _headk_param_grads(part, K, C, wshape):
+    """(dW (wshape), db (K,)) fp32 from lss_headk_bwd's per-block partials, the blocks summed in order."""
+    tot = part.sum(0)  # (K, C + 1)
+    return tot[:, :C].reshape(wshape), tot[:, C]
+
+
+class _HeadKx1(torch.autograd.Function):
+    """A 1x1 conv to K = 2..8 output channels over channels-last bf16 maps on lss_headk_* (include/lss_convs.h):
+    _Head1x1 for a multi-class head. The logits come back NCHW contiguous (N, K, H, W), the layout the loss,
+    the metrics and the labels use; one pass over the input each way for all K channels."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.bfloat16)
+    def forward(ctx, x, weight, bias):
+        lib = _lib.load()
+        N, C, H, W = x.shape
+        K = weight.shape[0]
+        x = _lib.aligned(x.to(torch.bfloat16).contiguous(memory_format=torch.channels_last))  # 16-B rows
+        w, b = _headk_params(weight, bias, K, C)
+        y = torch.empty(N, K, H, W, device=x.device, dtype=torch.bfloat16)
+        _lib.check(lib.lss_headk_fwd(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), N * H * W, H * W, C, K, None, _lib.ptr(y),
+                                     _lib.stream_handle(x.device)), "lss_headk_fwd")
+        ctx.save_for_backward(x, w)
+        ctx.meta = (weight.shape, weight.dtype, None if bias is None else bias.dtype)
+        return y
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, dy):
+        lib = _lib.load()
+        x, w = ctx.saved_tensors
+        wshape, wdtype, bdtype = ctx.meta
+        N, C, H, W = x.shape
+        K, P = w.shape[0], N * H * W
+        dy = dy.to(torch.bfloat16).contiguous()
+        dx = torch.empty_like(x)  # channels-last, as x
+        part = torch.empty(int(lib.lss_head1_blocks(P)), K, C + 1, device=x.device, dtype=torch.float32)
+        _lib.check(lib.lss_headk_bwd(_lib.ptr(x), _lib.ptr(dy), _lib.ptr(w), P, H * W, C, K, None, _lib.ptr(dx),
+                                     _lib.ptr(part), _lib.stream_handle(x.device)), "lss_headk_bwd")
+        dw, db = _headk_param_grads(part, K, C, wshape)
+        return dx, dw.to(wdtype), db.to(bdtype) if bdtype is not None else None
+
+
+class _BnReluHeadK(torch.autograd.Function):
+    """conv1x1_to_K_channels(relu(bn(x))) for channels-last bf16 maps in training mode, K = 2..8 -- _BnReluHead1
+    for a multi-class head, the normalised map never written in the forward: lss_bn_fwd2 with y = NULL
+    (statistics, running stats), then lss_headk_fwd applies scale / shift / ReLU to each value as it reads x;
+    backward: lss_headk_bwd (head weight / bias partials from the recomputed map, and the map's gradient dx),
+    then lss_bn_bwd2's channels-last path with y = NULL reading that dx (no rank-K form of lss_bn_bwd_rank1)."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda")
+    def forward(ctx, x, gamma, beta, hw, hb, bn: nn.BatchNorm2d):
+        lib = _lib.load()
+        N, C, H, W = x.shape
+        K = hw.shape[0]
+        HW, P = H * W, N * H * W
+        dev = x.device
+        st = _lib.stream_handle(dev)
+        x = _lib.aligned(x)
+        groups = int(lib.lss_bn_groups(N, C, HW, norm.NHWC))
+        f32 = dict(device=dev, dtype=torch.float32)
+        partial = torch.empty(C, groups, 2, **f32)
+        stats = torch.empty(4, C, **f32)  # save_mean, save_rstd, scale, shift
+        momentum, counter, rm, rv = norm.running_args(bn)
+        _lib.check(lib.lss_bn_fwd2(_lib.ptr(x), None, _lib.BF16, norm.NHWC, N, C, HW, _lib.ptr(gamma), _lib.ptr(beta),
+                                   float(bn.eps), float(momentum), _lib.ptr(rm), _lib.ptr(rv), _lib.ptr(counter),
+                                   norm.ACT["relu"], groups, _lib.ptr(partial), _lib.ptr(stats[0]), _lib.ptr(stats[1]),
+                                   _lib.ptr(stats[2]), _lib.ptr(stats[3]), None, None, st), "lss_bn_fwd2")
+        w, b = _headk_params(hw, hb, K, C)
+        y = torch.empty(N, K, H, W, device=dev, dtype=torch.bfloat16)
+        _lib.check(lib.lss_headk_fwd(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), P, HW, C, K, _lib.ptr(stats), _lib.ptr(y),
+                                     st), "lss_headk_fwd")
+        ctx.save_for_backward(x, stats, w)
+        # parameter-gradient dtypes under autocast: as _BnReluHead1 (bf16-rounded, then the parameter's)
+        cast = torch.is_autocast_enabled("cuda")
+        ctx.meta = (groups, hw.shape, torch.bfloat16 if cast else hw.dtype, hw.dtype,
+                    None if hb is None else (torch.bfloat16 if cast else hb.dtype), None if hb is None else hb.dtype)
+        return y
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, dout):
+        lib = _lib.load()
+        x, stats, w = ctx.saved_tensors
+        groups, wshape, wdtype, wdtype_out, bdtype, bdtype_out = ctx.meta
+        N, C, H, W = x.shape
+        K, P = w.shape[0], N * H * W
+        dev = x.device
+        st = _lib.stream_handle(dev)
+        dout = dout.to(torch.bfloat16).contiguous()
+        dmap = torch.empty_like(x)  # the gradient of relu(bn(x)), channels-last
+        part = torch.empty(int(lib.lss_head1_blocks(P)), K, C + 1, device=dev, dtype=torch.float32)
+        _lib.check(lib.lss_headk_bwd(_lib.ptr(x), _lib.ptr(dout), _lib.ptr(w), P, H * W, C, K, _lib.ptr(stats),
+                                     _lib.ptr(dmap), _lib.ptr(part), st), "lss_headk_bwd")
+        dw, db = _headk_param_grads(part, K, C, wshape)
+        dw = dw.to(wdtype).to(wdtype_out)
+        db = db.to(bdtype).to(bdtype_out) if bdtype is not None else None
+        f32 = dict(device=dev, dtype=torch.float32)
+        partial = torch.empty(C, groups, 2, **f32)
+        coef = torch.empty(C, 2, **f32)
+        dgamma = torch.empty(C, **f32)
+        dbeta = torch.empty(C, **f32)
+        dx = torch.empty_like(x)
+        _lib.check(lib.lss_bn_bwd2(_lib.ptr(dmap), _lib.ptr(x), None, _lib.BF16, norm.NHWC, N, C, H * W,
+                                   _lib.ptr(stats[2]), _lib.ptr(stats[3]), _lib.ptr(stats[0]), _lib.ptr(stats[1]),
+                                   norm.ACT["relu"], groups, _lib.ptr(partial), _lib.ptr(coef), _lib.ptr(dgamma),
+                                   _lib.ptr(dbeta), _lib.ptr(dx), None, _lib.ptr(norm._sync(dev)), st), "lss_bn_bwd2")
+        return dx, dgamma, dbeta, dw, db, None
+
+
+def bn_relu_head1(bn: nn.BatchNorm2d, head: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
+    """head(relu(bn(x))) with head a 1x1 conv: to one channel, _BnReluHead1 where eligible (the benched
+    BevEncode: training mode, channels-last bf16 under autocast); to 2..8 channels, _BnReluHeadK under the
+    same conditions when the head is marked as the model's logits head (logits_head); else bn_act + conv1x1."""
+    C = x.shape[1] if x.dim() == 4 else 0
+    common = (USE_BN_HEAD and norm.USE_HIP_BN and bn.training and bn.affine and x.is_cuda
+              and norm.params_fp32(bn) and x.dim() == 4 and x.dtype == torch.bfloat16
+              and x.is_contiguous(memory_format=torch.channels_last)
+              and head.kernel_size == (1, 1) and head.stride == (1, 1) and head.groups == 1
+              and C % 8 == 0 and 64 % (C // 8) == 0 and 256 % (C // 8) == 0)
+    if common and USE_HIP_HEAD1 and head.out_channels == 1 and _head1_eligible(head, x):
+        return _BnReluHead1.apply(x, bn.weight, bn.bias, head.weight, head.bias, bn)
+    if common and head.padding in ((0, 0), "valid") and _headk_eligible(head, x):
+        return _BnReluHeadK.apply(x, bn.weight, bn.bias, head.weight, head.bias, bn)
+    return conv1x1(head, bn_act(bn, x, "relu"))
 
 
 class _Subsample(torch.autograd.Function):
@@ -489,6 +637,8 @@ def conv1x1(conv: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
     s = conv.stride[0]
     if s == 1 and _head1_eligible(conv, x):
         return _Head1x1.apply(x, conv.weight, conv.bias)
+    if s == 1 and _headk_eligible(conv, x):
+        return _HeadKx1.apply(x, conv.weight, conv.bias)
     if s > 1:
         x = _Subsample.apply(x, s)
     w = conv.weight.reshape(conv.out_channels, conv.in_channels)
@@ -543,7 +693,7 @@ class BevEncode(nn.Module):
             nn.Conv2d(256, 128, kernel_size=3, padding=1, bias=False),
             nn.BatchNorm2d(128),
             nn.ReLU(inplace=True),
-            nn.Conv2d(128, outC, kernel_size=1, padding=0),
+            logits_head(nn.Conv2d(128, outC, kernel_size=1, padding=0)),
         )
 
     def forward(self, x):

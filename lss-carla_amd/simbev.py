@@ -11,7 +11,8 @@ Where the work runs:
                              post-homography arithmetic (torch, src/tools.py:130-142), the BEV npz read
   device (main process)      ``lss_simbev_images``: Image.resize (bicubic) -> crop -> flip -> rotate
                              -> ToTensor -> Normalize per camera, bit for bit with Pillow / torchvision;
-                             ``lss_simbev_vehicle_mask``: classes 1-3 merged + np.flipud
+                             ``lss_simbev_vehicle_mask``: classes 1-3 merged + np.flipud (or, with
+                             ``label_groups``, ``lss_simbev_class_masks``: one label channel per group)
 So a training step at hundreds of frames/s is not bound by PIL's per-camera resampling on the CPU:
 the workers only decode. The loader yields device tensors; the reference's ``.to(device)`` calls in
 train_simbev.py become no-ops.
@@ -242,6 +243,57 @@ def vehicle_masks(bev_u8: torch.Tensor, out=None) -> torch.Tensor:
     return out
 
 
+MAX_LABEL_GROUPS = 8  # LSS_SIMBEV_MAX_GROUPS of include/lss_simbev.h
+
+
+def group_bits(label_groups, n_classes: int = 32) -> List[int]:
+    """One bit mask over the npz channels per group of ``label_groups`` (a list of lists of channel
+    indices); raises ValueError for an empty list, an empty group or a channel outside [0, n_classes)."""
+    groups = [list(g) for g in label_groups]
+    if not 1 <= len(groups) <= MAX_LABEL_GROUPS:
+        raise ValueError(f"label_groups: 1..{MAX_LABEL_GROUPS} groups, got {len(groups)}")
+    bits = []
+    for g in groups:
+        if not g:
+            raise ValueError(f"label_groups {groups}: an empty group")
+        m = 0
+        for c in g:
+            if int(c) != c or not 0 <= int(c) < n_classes:
+                raise ValueError(f"label_groups {groups}: channel {c!r} is outside 0..{n_classes - 1}")
+            m |= 1 << int(c)
+        bits.append(m)
+    return bits
+
+
+def class_masks(bev_u8: torch.Tensor, label_groups=None, out=None) -> torch.Tensor:
+    """(n, C, X, Y) uint8 device BEV maps -> (n, K, X, Y) fp32 labels, one channel per group of
+    ``label_groups`` (K lists of npz channel indices): out[:, k] = flipud(any(bev[:, c] > 0 for c in group
+    k)), ``lss_simbev_class_masks``. None: the reference's single vehicle mask [[1, 2, 3]] through
+    ``vehicle_masks``, as before. out: a contiguous fp32 device tensor of n * K * X * Y elements to write."""
+    if label_groups is None:
+        return vehicle_masks(bev_u8, out=out)
+    if not bev_u8.is_cuda:
+        raise RuntimeError("lss_carla_amd.simbev: BEV maps must be on the MI355X (no CPU fallback)")
+    if bev_u8.dtype == torch.bool:
+        bev_u8 = bev_u8.view(torch.uint8)
+    if bev_u8.dtype != torch.uint8:
+        bev_u8 = (bev_u8 > 0).to(torch.uint8)
+    n, C, X, Y = bev_u8.shape
+    bits = group_bits(label_groups)  # (the channel range is the kernel entry's check: it knows C)
+    K = len(bits)
+    if out is None:
+        out = torch.empty(n, K, X, Y, device=bev_u8.device, dtype=torch.float32)
+    elif not (out.is_cuda and out.device == bev_u8.device and out.dtype == torch.float32 and out.is_contiguous()
+              and out.numel() == n * K * X * Y):
+        raise RuntimeError(f"out= must be a contiguous fp32 device tensor of {(n, K, X, Y)}")
+    b = bev_u8.contiguous()
+    host = (ctypes.c_uint32 * K)(*bits)
+    _lib.check(_lib.load().lss_simbev_class_masks(_lib.ptr(b), n, C, X, Y, ctypes.cast(host, ctypes.c_void_p), K,
+                                                  _lib.ptr(out), _lib.stream_handle(b.device)),
+               "lss_simbev_class_masks")
+    return out
+
+
 # ----------------------------------------------------------------------------- dataset (host side)
 class SimBEVDataset(torch.utils.data.Dataset):
     """src/data_simbev.py:23-265: same layout (SimBEV_cvt_label/scene_*/yaw0pitch0/meta.json, 80/20
@@ -349,9 +401,10 @@ def worker_rnd_init(x):
     np.random.seed(13 + x)  # src/data_simbev.py:310-312
 
 
-def finish_batch(batch, final_dim, device):
+def finish_batch(batch, final_dim, device, label_groups=None):
     """A collated raw batch -> the reference's (imgs, rots, trans, intrins, post_rots, post_trans,
-    [lidar,] binimgs) on `device`, the pixel work done by the HIP kernels."""
+    [lidar,] binimgs) on `device`, the pixel work done by the HIP kernels. label_groups: K lists of BEV
+    channels -> binimgs (B, K, X, Y) (class_masks); None: the reference's vehicle mask, (B, 1, X, Y)."""
     imgs_u8, rots, trans, intrins, post_rots, post_trans, aug, rot = batch[:8]
     rest = batch[8:]
     B, N = imgs_u8.shape[:2]
@@ -369,15 +422,16 @@ def finish_batch(batch, final_dim, device):
     out[4]._lss_host, out[4]._lss_host_version = post_rots, out[4]._version
     for t in rest[:-1]:
         out.append(t)  # lidar placeholder (VizData)
-    out.append(vehicle_masks(rest[-1].to(device, non_blocking=True)))
+    out.append(class_masks(rest[-1].to(device, non_blocking=True), label_groups))
     return tuple(out)
 
 
 class DeviceLoader:
     """Iterates a DataLoader of raw samples and yields finished device batches (finish_batch)."""
 
-    def __init__(self, loader, final_dim, device):
+    def __init__(self, loader, final_dim, device, label_groups=None):
         self.loader, self.final_dim, self.device = loader, final_dim, torch.device(device)
+        self.label_groups = label_groups
         self.dataset = loader.dataset
         self.batch_size = loader.batch_size
 
@@ -386,11 +440,15 @@ class DeviceLoader:
 
     def __iter__(self):
         for batch in self.loader:
-            yield finish_batch(batch, self.final_dim, self.device)
+            yield finish_batch(batch, self.final_dim, self.device, self.label_groups)
 
 
-def compile_data(version, dataroot, data_aug_conf, grid_conf, bsz, nworkers, parser_name, device="cuda"):
-    """src/data_simbev.py:315-354 with the same loaders' settings; returns DeviceLoaders."""
+def compile_data(version, dataroot, data_aug_conf, grid_conf, bsz, nworkers, parser_name, device="cuda",
+                 label_groups=None):
+    """src/data_simbev.py:315-354 with the same loaders' settings; returns DeviceLoaders. label_groups: the
+    BEV channel groups of a multi-class model's labels (finish_batch); None: the reference's vehicle mask."""
+    if label_groups is not None:
+        group_bits(label_groups)  # a bad group list fails here, not in the first batch
     parser = {"vizdata": VizData, "segmentationdata": SegmentationData}[parser_name]
     traindata = parser(dataroot, is_train=True, data_aug_conf=data_aug_conf, grid_conf=grid_conf)
     valdata = parser(dataroot, is_train=False, data_aug_conf=data_aug_conf, grid_conf=grid_conf)
@@ -399,4 +457,4 @@ def compile_data(version, dataroot, data_aug_conf, grid_conf, bsz, nworkers, par
     valloader = torch.utils.data.DataLoader(valdata, batch_size=bsz, shuffle=False, num_workers=nworkers,
                                             pin_memory=True)
     fd = data_aug_conf["final_dim"]
-    return DeviceLoader(trainloader, fd, device), DeviceLoader(valloader, fd, device)
+    return DeviceLoader(trainloader, fd, device, label_groups), DeviceLoader(valloader, fd, device, label_groups)

@@ -6,14 +6,15 @@ are valid. ``BatchStager`` owns those tensors and fills them from the raw batche
 ``simbev.compile_data``'s DataLoader (``DeviceLoader.loader``), one batch ahead of the step:
 
   stage(raw)   on the staging stream: H2D copies of the uint8 images / BEV and of the rig, then
-               ``lss_simbev_images`` and ``lss_simbev_vehicle_mask`` straight into the next of two slots;
+               ``lss_simbev_images`` and ``lss_simbev_vehicle_mask`` (``lss_simbev_class_masks`` with
+               ``label_groups``) straight into the next of two slots;
                an event marks the slot ready. Batch k+1 is staged while step k runs.
   commit()     on the current stream: wait for the oldest staged slot's event, copy slot -> static tensors
                (device to device), ``HostInverses.update`` with the slot's host post_rots / intrins, set
                ``n_valid``; an event marks the slot consumed (the staging stream waits for it before it
                writes the slot again).
 
-Stream rules. The staging stream runs copies and the two simbev kernels only -- no plan, batch-norm or
+Stream rules. The staging stream runs copies and the simbev kernels only -- no plan, batch-norm or
 depthwise kernel: their persistent workspaces (norm._sync, ops._PlanWorkspace) belong to one stream.
 What ``stage`` allocates (the kernels' parameter block, a table concatenation) and the host batch its
 copies read stay referenced until the slot's event has completed. Neither method synchronises the
@@ -31,7 +32,7 @@ from . import ops, simbev
 
 
 class _Slot:
-    def __init__(self, B, N, fH, fW, src_hw, X, Y, dev):
+    def __init__(self, B, N, fH, fW, src_hw, K, X, Y, dev):
         H, W = int(src_hw[0]), int(src_hw[1])
         self.u8 = torch.empty(B * N, H, W, 3, device=dev, dtype=torch.uint8)
         self.bev_u8 = None  # (B, classes, X, Y): sized by the first batch
@@ -41,7 +42,7 @@ class _Slot:
         self.intrins = torch.zeros(B, N, 3, 3, device=dev)
         self.post_rots = torch.zeros(B, N, 3, 3, device=dev)
         self.post_trans = torch.zeros(B, N, 3, device=dev)
-        self.binimgs = torch.zeros(B, 1, X, Y, device=dev, dtype=torch.float32)
+        self.binimgs = torch.zeros(B, K, X, Y, device=dev, dtype=torch.float32)
         self.host_post_rots = None
         self.host_intrins = None
         self.b = 0
@@ -53,7 +54,10 @@ class _Slot:
 class BatchStager:
     RIG = ("rots", "trans", "intrins", "post_rots", "post_trans")
 
-    def __init__(self, final_dim: Sequence[int], B: int, N: int, src_hw: Sequence[int], grid: dict, device):
+    def __init__(self, final_dim: Sequence[int], B: int, N: int, src_hw: Sequence[int], grid: dict, device,
+                 label_groups=None):
+        """label_groups: K lists of BEV channels, one label channel each (simbev.class_masks): ``binimgs`` and
+        both slots are (B, K, X, Y); None: the reference's vehicle mask, K = 1."""
         dev = torch.device(device)
         if dev.type != "cuda":
             raise RuntimeError("BatchStager: the static tensors live on the MI355X (no CPU fallback)")
@@ -66,14 +70,18 @@ class BatchStager:
         self.rots, self.intrins, self.post_rots = (eye.clone() for _ in range(3))
         self.trans = torch.zeros(B, N, 3, device=dev)
         self.post_trans = torch.zeros(B, N, 3, device=dev)
-        self.binimgs = torch.zeros(B, 1, X, Y, device=dev, dtype=torch.float32)
+        if label_groups is not None:
+            simbev.group_bits(label_groups)
+        self.label_groups = None if label_groups is None else [list(g) for g in label_groups]
+        K = 1 if label_groups is None else len(self.label_groups)
+        self.binimgs = torch.zeros(B, K, X, Y, device=dev, dtype=torch.float32)
         self.n_valid = torch.full((1,), B, device=dev, dtype=torch.int32)
         self.hinv = ops.HostInverses(B * N, dev)
         # the host rig HostInverses inverts: samples past a partial batch keep their previous matrices
         self._host_post_rots = torch.eye(3).repeat(B, N, 1, 1)
         self._host_intrins = torch.eye(3).repeat(B, N, 1, 1)
         self.stream = torch.cuda.Stream(dev)
-        self._slots = [_Slot(B, N, fH, fW, src_hw, X, Y, dev) for _ in range(2)]
+        self._slots = [_Slot(B, N, fH, fW, src_hw, K, X, Y, dev) for _ in range(2)]
         self._next = 0
         self._staged: deque = deque()   # slots staged and not yet committed, oldest first
         self._retired: List[tuple] = []  # (event, tensors) of reused slots whose event had not completed
@@ -121,7 +129,7 @@ class BatchStager:
             for name, t in zip(self.RIG, (rots, trans, intrins, post_rots, post_trans)):
                 getattr(slot, name)[:b].copy_(t, non_blocking=True)
             simbev.augment_images(slot.u8[:b * N], augs, self.final_dim, out=slot.imgs[:b], keep=keep)
-            simbev.vehicle_masks(slot.bev_u8[:b], out=slot.binimgs[:b])
+            simbev.class_masks(slot.bev_u8[:b], self.label_groups, out=slot.binimgs[:b])
             slot.ready = torch.cuda.Event()
             slot.ready.record(st)
         slot.host_post_rots, slot.host_intrins, slot.b, slot.keep = post_rots, intrins, b, keep

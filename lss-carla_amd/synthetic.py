@@ -147,12 +147,14 @@ def make_labels(B: int, X: int, Y: int, seed: int = 0) -> torch.Tensor:
 
 
 def make_simbev_tree(root, n_scenes: int, per_scene: int, H: int = IMG_H, W: int = IMG_W, seed: int = 0,
-                     n_classes: int = 8, X: int = 200, Y: int = 200, quality: int = 90) -> int:
+                     n_classes: int = 8, X: int = 200, Y: int = 200, quality: int = 90,
+                     box_classes: Sequence[int] = (1, 2, 3)) -> int:
     """Write a synthetic dataset with SimBEV's layout (src/data_simbev.py:40-75) under ``root``:
     ``SimBEV_cvt_label/scene_XXXX/yaw0pitch0/meta.json`` (per sample: six JPEG paths, the §8d rig's
     intrinsics / 4x4 extrinsics, the BEV file) + ``bev_*.npz`` ((n_classes, X, Y) uint8 under "bev", a few
-    vehicle boxes in classes 1-3), and ``sweeps/RGB-CAM_*/`` H x W JPEGs of smooth random content (so a
-    decode costs what a photograph's does). The loader's 80/20 scene split applies. Returns the sample count."""
+    boxes in the channels ``box_classes``, by default the vehicle classes 1-3), and ``sweeps/RGB-CAM_*/``
+    H x W JPEGs of smooth random content (so a decode costs what a photograph's does). The loader's 80/20
+    scene split applies. Returns the sample count."""
     import json
     import os
 
@@ -161,6 +163,9 @@ def make_simbev_tree(root, n_scenes: int, per_scene: int, H: int = IMG_H, W: int
 
     from .simbev import CAMERA_ORDER
 
+    box_classes = tuple(int(c) for c in box_classes)
+    if not box_classes or not all(0 <= c < n_classes for c in box_classes):
+        raise ValueError(f"box_classes {box_classes}: channels of a {n_classes}-class BEV")
     rng = np.random.default_rng(seed)
     rig = make_rig(1, 6, (H, W), seed=seed)
     extr = np.tile(np.eye(4), (6, 1, 1))
@@ -187,7 +192,9 @@ def make_simbev_tree(root, n_scenes: int, per_scene: int, H: int = IMG_H, W: int
                 paths.append(rel)
             bev = np.zeros((n_classes, X, Y), dtype=np.uint8)
             for _ in range(12):
-                cls = int(rng.integers(1, 4))
+                # (the default keeps its original draw, so default trees stay byte-identical)
+                cls = int(rng.integers(1, 4)) if box_classes == (1, 2, 3) else \
+                    box_classes[int(rng.integers(0, len(box_classes)))]
                 x0, y0 = int(rng.integers(0, X - 10)), int(rng.integers(0, Y - 5))
                 bev[cls, x0:x0 + 9, y0:y0 + 4] = 1
             np.savez_compressed(os.path.join(d, f"bev_{tok}.npz"), bev=bev)

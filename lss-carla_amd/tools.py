@@ -100,6 +100,37 @@ class _BceLogits(torch.autograd.Function):
         return dx, None, None
 
 
+def is_scalar_weight(w) -> bool:
+    """One pos_weight for every class (a number, a numpy scalar or a 0-d tensor: what float() took before
+    per-class weights existed), as opposed to a sequence / tensor of K."""
+    return isinstance(w, (int, float)) or getattr(w, "ndim", None) == 0
+
+
+class _BceLogitsPerClass(torch.autograd.Function):
+    """_BceLogits with one positive-class weight per channel of (N, K, H, W) logits, ``lss_bce_logits_pc``:
+    the K weights are a device buffer the kernel indexes by (i / (H W)) % K."""
+
+    @staticmethod
+    def forward(ctx, x, target, pos_weight: torch.Tensor):
+        from . import _lib
+        lib = _lib.load()
+        n = x.numel()
+        K = x.shape[1]
+        partial = torch.empty(int(lib.lss_bce_partials(n)), device=x.device, dtype=torch.float32)
+        loss = torch.empty((), device=x.device, dtype=torch.float32)
+        grad = torch.empty_like(x)
+        _lib.check(lib.lss_bce_logits_pc(_lib.ptr(x), _lib.dtype_code(x.dtype), _lib.ptr(target), n,
+                                         n // (x.shape[0] * K), K, _lib.ptr(pos_weight), _lib.ptr(partial),
+                                         _lib.ptr(loss), _lib.ptr(grad), _lib.stream_handle(x.device)),
+                   "lss_bce_logits_pc")
+        ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        return _BceLogits.backward(ctx, g)
+
+
 class SimpleLoss(torch.nn.Module):
     """BCE-with-logits with a positive-class weight (src/tools.py:222-230).
 
@@ -110,17 +141,38 @@ class SimpleLoss(torch.nn.Module):
 
     computes_in_fp32 = True  # callers may pass bf16 logits without casting them first (train_step)
 
-    def __init__(self, pos_weight: float):
+    def __init__(self, pos_weight):
+        """pos_weight: a float, or a sequence of K floats -- one weight per class of (N, K, H, W) logits
+        (``BCEWithLogitsLoss(pos_weight=w.view(K, 1, 1))``; on the fused path ``lss_bce_logits_pc`` reads
+        them from the module's device buffer ``pos_weight_classes``, so they can be changed in place
+        under a captured graph)."""
         super().__init__()
-        self.loss_fn = torch.nn.BCEWithLogitsLoss(pos_weight=torch.tensor([float(pos_weight)]))
-        self.pos_weight_value = float(pos_weight)
+        if is_scalar_weight(pos_weight):
+            self.loss_fn = torch.nn.BCEWithLogitsLoss(pos_weight=torch.tensor([float(pos_weight)]))
+            self.pos_weight_value = float(pos_weight)
+            self.pos_weight_classes = None
+        else:
+            w = torch.as_tensor([float(v) for v in pos_weight], dtype=torch.float32)
+            if w.numel() == 0:
+                raise ValueError("SimpleLoss: pos_weight is an empty sequence")
+            self.loss_fn = torch.nn.BCEWithLogitsLoss(pos_weight=w.view(-1, 1, 1))
+            self.pos_weight_value = None
+            self.register_buffer("pos_weight_classes", w.clone(), persistent=False)
 
     def forward(self, ypred, ytgt):
+        pc = self.pos_weight_classes
+        if pc is not None and not (ypred.dim() == 4 and ypred.shape[1] == pc.numel()):
+            raise RuntimeError(f"SimpleLoss: {pc.numel()} class weights for logits {tuple(ypred.shape)}")
         if (ypred.is_cuda and ypred.dtype in (torch.float32, torch.bfloat16) and ytgt.dtype == torch.float32
                 and ytgt.device == ypred.device and ytgt.shape == ypred.shape and ypred.is_contiguous()
                 and ytgt.is_contiguous() and ypred.data_ptr() % 16 == 0 and ytgt.data_ptr() % 16 == 0
                 and ypred.numel() > 0):
-            return _BceLogits.apply(ypred, ytgt, self.pos_weight_value)
+            if pc is None:
+                return _BceLogits.apply(ypred, ytgt, self.pos_weight_value)
+            if pc.device == ypred.device and pc.dtype == torch.float32:
+                return _BceLogitsPerClass.apply(ypred, ytgt, pc)
+        if pc is not None:  # (the (K, 1, 1) view of the current class weights)
+            self.loss_fn.pos_weight.copy_(pc.view(-1, 1, 1))
         return self.loss_fn(ypred.float() if ypred.dtype == torch.bfloat16 else ypred, ytgt)
 
 
@@ -139,21 +191,61 @@ def get_batch_iou_device(preds: torch.Tensor, binimgs: torch.Tensor):
         return (pred & tgt).sum().float(), (pred | tgt).sum().float()
 
 
+def get_batch_iou_per_class(preds: torch.Tensor, binimgs: torch.Tensor):
+    """(intersection, union) per class of (N, K, H, W) logits and labels, as float device tensors of shape
+    (K,), without a host sync (the trainer's training-IoU event reads them at its own cadence)."""
+    with torch.no_grad():
+        pred = preds > 0
+        tgt = binimgs.bool()
+        return (pred & tgt).sum(dim=(0, 2, 3)).float(), (pred | tgt).sum(dim=(0, 2, 3)).float()
+
+
+def iou_summary(inter, union) -> dict:
+    """{"iou", "iou_per_class"} from per-class counts (sequences of numbers): inter / union per class, None
+    for a class whose union is empty, and their mean over the classes with a non-empty union; every union
+    empty raises ZeroDivisionError, as the reference's single division does."""
+    per = [float(i) / float(u) if u > 0 else None for i, u in zip(inter, union)]
+    seen = [v for v in per if v is not None]
+    if len(per) == 1:
+        return {"iou": float(inter[0]) / float(union[0]), "iou_per_class": per}
+    if not seen:
+        raise ZeroDivisionError("every class has an empty union")
+    return {"iou": sum(seen) / len(seen), "iou_per_class": per}
+
+
+def class_weights(pos_weight, K: int, device) -> torch.Tensor:
+    """K fp32 class weights on `device` from a float, a sequence of K floats or a tensor of K."""
+    if is_scalar_weight(pos_weight):
+        w = torch.full((K,), float(pos_weight), device=device, dtype=torch.float32)
+    elif torch.is_tensor(pos_weight):
+        w = pos_weight.detach().to(device=device, dtype=torch.float32).reshape(-1)
+    else:
+        w = torch.tensor([float(v) for v in pos_weight], device=device, dtype=torch.float32)
+    if w.numel() != K:
+        raise RuntimeError(f"{w.numel()} class weights for {K} classes")
+    return w.contiguous()
+
+
 _VAL_PARTIAL = {}
 
 
 def val_accumulate(preds: torch.Tensor, binimgs: torch.Tensor, totals: torch.Tensor, n_valid=None,
-                   pos_weight: float = 2.13) -> torch.Tensor:
+                   pos_weight=2.13) -> torch.Tensor:
     """One validation batch into get_val_info's accumulators, ``lss_bce_iou_accum`` (include/lss_convs.h):
     totals (3 float64 on the device) += (mean loss x samples, intersection, union) over the first
     ``n_valid`` samples (one int32 on the device, read there; None: all of them). preds: fp32 or bf16
     logits, binimgs: fp32 labels of the same shape. Two launches, no host synchronisation, capturable
-    (the scratch is kept per device and size: one stream at a time)."""
+    (the scratch is kept per device and size: one stream at a time).
+
+    K = labels.shape[1] > 1 classes: totals is 1 + 2 K float64 -- the loss term, then the K intersections,
+    then the K unions -- and pos_weight a float, K floats or a device tensor of K (pass the tensor when
+    capturing: building it is a host-to-device copy), ``lss_bce_iou_accum_pc``."""
     from . import _lib
     if not (preds.is_cuda and binimgs.device == preds.device and totals.device == preds.device):
         raise RuntimeError("val_accumulate: device tensors only (no CPU fallback)")
+    K = preds.shape[1] if preds.dim() >= 2 else 1
     if (binimgs.dtype != torch.float32 or binimgs.shape != preds.shape or totals.dtype != torch.float64
-            or totals.numel() != 3 or not totals.is_contiguous() or preds.dim() < 1 or preds.numel() == 0):
+            or totals.numel() != 1 + 2 * K or not totals.is_contiguous() or preds.dim() < 1 or preds.numel() == 0):
         raise RuntimeError(f"val_accumulate: preds {tuple(preds.shape)} {preds.dtype}, labels {tuple(binimgs.shape)} "
                            f"{binimgs.dtype}, totals {tuple(totals.shape)} {totals.dtype}")
     if n_valid is not None and not (n_valid.device == preds.device and n_valid.dtype == torch.int32
@@ -163,11 +255,19 @@ def val_accumulate(preds: torch.Tensor, binimgs: torch.Tensor, totals: torch.Ten
     x, t = preds.detach().contiguous(), binimgs.contiguous()
     batch = x.shape[0]
     per_sample = x.numel() // batch
-    nbytes = int(lib.lss_bce_iou_partial_bytes(x.numel()))
+    per_class = K > 1 or not is_scalar_weight(pos_weight)
+    nbytes = int(lib.lss_bce_iou_pc_partial_bytes(x.numel(), K) if per_class else
+                 lib.lss_bce_iou_partial_bytes(x.numel()))
     key = (x.device, nbytes)
     partial = _VAL_PARTIAL.get(key)
     if partial is None:
         partial = _VAL_PARTIAL[key] = torch.empty(nbytes // 8, device=x.device, dtype=torch.float64)
+    if per_class:
+        w = class_weights(pos_weight, K, x.device)
+        _lib.check(lib.lss_bce_iou_accum_pc(_lib.ptr(x), _lib.dtype_code(x.dtype), _lib.ptr(t), per_sample, batch,
+                                            _lib.ptr(n_valid), per_sample // K, K, _lib.ptr(w), _lib.ptr(totals),
+                                            _lib.ptr(partial), _lib.stream_handle(x.device)), "lss_bce_iou_accum_pc")
+        return totals
     _lib.check(lib.lss_bce_iou_accum(_lib.ptr(x), _lib.dtype_code(x.dtype), _lib.ptr(t), per_sample, batch,
                                      _lib.ptr(n_valid), float(pos_weight), _lib.ptr(totals), _lib.ptr(partial),
                                      _lib.stream_handle(x.device)), "lss_bce_iou_accum")
@@ -176,10 +276,10 @@ def val_accumulate(preds: torch.Tensor, binimgs: torch.Tensor, totals: torch.Ten
 
 def val_totals(model, loader, loss_fn, device):
     """The device accumulators of get_val_info: (sum of loss x batch size, intersection, union) as
-    float64 device tensors; nothing in the loop synchronises the host."""
+    float64 device tensors; nothing in the loop synchronises the host. The counts
+    are per class, sized by the labels: scalars for one label channel, (K,) tensors for K > 1."""
     total_loss = torch.zeros((), device=device, dtype=torch.float64)
-    total_intersect = torch.zeros((), device=device, dtype=torch.float64)
-    total_union = torch.zeros((), device=device, dtype=torch.float64)
+    total_intersect = total_union = None
     with torch.no_grad():
         for batch in loader:
             allimgs, rots, trans, intrins, post_rots, post_trans, binimgs = batch
@@ -187,19 +287,27 @@ def val_totals(model, loader, loss_fn, device):
                           post_rots.to(device), post_trans.to(device))
             binimgs = binimgs.to(device)
             total_loss += loss_fn(preds, binimgs).double() * preds.shape[0]
-            i, u = get_batch_iou_device(preds, binimgs)
-            total_intersect += i.double()
-            total_union += u.double()
+            if binimgs.dim() == 4 and binimgs.shape[1] > 1:
+                i, u = get_batch_iou_per_class(preds, binimgs)
+            else:
+                i, u = get_batch_iou_device(preds, binimgs)
+            total_intersect = i.double() if total_intersect is None else total_intersect + i.double()
+            total_union = u.double() if total_union is None else total_union + u.double()
+    if total_intersect is None:
+        total_intersect = torch.zeros((), device=device, dtype=torch.float64)
+        total_union = torch.zeros((), device=device, dtype=torch.float64)
     return total_loss, total_intersect, total_union
 
 
 def get_val_info(model, valloader, loss_fn, device, use_tqdm=True):
     """Validation loss / IoU over a loader (src/tools.py:243-270).
 
-    Same results and the same return dict as the reference, but the per-batch ``.item()`` syncs
-    are gone: loss (x batch size) and the intersection / union counts accumulate on the device in
-    float64 (val_totals) and are read once at the end. As in the reference, the loss is divided by
-    ``len(valloader.dataset)`` and an empty union raises ZeroDivisionError.
+    Same results as the reference, but the per-batch ``.item()`` syncs are gone: loss (x batch size) and the
+    intersection / union counts accumulate on the device in float64 (val_totals) and are read once at the
+    end. As in the reference, the loss is divided by ``len(valloader.dataset)`` and an empty union raises
+    ZeroDivisionError. One label channel: the reference's {"loss", "iou"}. K > 1 label channels:
+    {"loss", "iou", "iou_per_class"} -- inter_k / union_k per class, None for a class with an empty union,
+    and "iou" their mean over the classes seen (iou_summary).
     """
     model.eval()
     print("running eval...")
@@ -209,7 +317,8 @@ def get_val_info(model, valloader, loss_fn, device, use_tqdm=True):
         loader = tqdm(valloader, desc="Validation")
     total_loss, total_intersect, total_union = val_totals(model, loader, loss_fn, device)
     model.train()
-    return {
-        "loss": total_loss.item() / len(valloader.dataset),
-        "iou": total_intersect.item() / total_union.item(),
-    }
+    inter, union = total_intersect.reshape(-1).tolist(), total_union.reshape(-1).tolist()
+    info = {"loss": total_loss.item() / len(valloader.dataset), **iou_summary(inter, union)}
+    if len(inter) == 1:
+        del info["iou_per_class"]  # one label channel: exactly the reference's dict
+    return info

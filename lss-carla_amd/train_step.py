@@ -194,7 +194,8 @@ class TrainStep:
 class EvalStep:
     """The validation step of get_val_info (src/tools.py:243-270) over static inputs: forward only, the
     model in eval mode, no_grad, the training step's autocast dtype, then ``tools.val_accumulate`` into
-    ``totals`` (3 float64 on the device: loss x samples, intersection, union) -- eager, or one HIP graph.
+    ``totals`` (1 + 2 K float64 on the device for K = labels.shape[1] classes: loss x samples, the K
+    intersections, the K unions; K = 1: the reference's three) -- eager, or one HIP graph.
 
     forward: the callable the training step runs (e.g. ``FlatParams.bind(model)``: every call, and every
     replay, materialises the current masters). n_valid (one int32 on the device, e.g.
@@ -203,12 +204,20 @@ class EvalStep:
     module's mode flag: a captured graph replays the kernels it recorded."""
 
     def __init__(self, model: torch.nn.Module, forward: Callable[..., torch.Tensor], inputs: Sequence[torch.Tensor],
-                 labels: torch.Tensor, n_valid: Optional[torch.Tensor] = None, pos_weight: float = 2.13,
+                 labels: torch.Tensor, n_valid: Optional[torch.Tensor] = None, pos_weight=2.13,
                  amp_dtype: Optional[torch.dtype] = torch.bfloat16, n_samples: Optional[int] = None):
         self.model, self.forward, self.inputs, self.labels = model, forward, tuple(inputs), labels
         self.n_samples = n_samples  # len(valloader.dataset): what read() divides the loss total by
-        self.n_valid, self.pos_weight, self.amp_dtype = n_valid, float(pos_weight), amp_dtype
-        self.totals = torch.zeros(3, device=labels.device, dtype=torch.float64)
+        self.n_valid, self.amp_dtype = n_valid, amp_dtype
+        # K = labels.shape[1] classes: 1 + 2 K totals (loss, K intersections, K unions) and, for K > 1 or a
+        # sequence of weights, the class weights as a device buffer made here, outside any capture
+        self.classes = int(labels.shape[1]) if labels.dim() >= 2 else 1
+        from . import tools
+        if self.classes > 1 or not tools.is_scalar_weight(pos_weight):
+            self.pos_weight = tools.class_weights(pos_weight, self.classes, labels.device)
+        else:
+            self.pos_weight = float(pos_weight)
+        self.totals = torch.zeros(1 + 2 * self.classes, device=labels.device, dtype=torch.float64)
         self.graph = None
         self.static_preds = None
 
@@ -260,8 +269,13 @@ class EvalStep:
         self.totals.zero_()
 
     def read(self, n_samples: Optional[int] = None) -> dict:
-        """get_val_info's dict: the loss total over ``n_samples`` (``len(valloader.dataset)``; default: the
-        constructor's), and intersection / union (an empty union raises ZeroDivisionError, as the
-        reference's does). The one host read of a validation pass."""
-        loss, inter, union = self.totals.tolist()
-        return {"loss": loss / (self.n_samples if n_samples is None else n_samples), "iou": inter / union}
+        """get_val_info's dict {"loss", "iou", "iou_per_class"}: the loss total over ``n_samples``
+        (``len(valloader.dataset)``; default: the constructor's), intersection / union per class (None for a
+        class with an empty union) and their mean over the classes seen -- for one class the reference's
+        intersection / union; every union empty raises ZeroDivisionError, as the reference's does. The one
+        host read of a validation pass."""
+        from . import tools
+        t = self.totals.tolist()
+        K = self.classes
+        return {"loss": t[0] / (self.n_samples if n_samples is None else n_samples),
+                **tools.iou_summary(t[1:1 + K], t[1 + K:1 + 2 * K])}

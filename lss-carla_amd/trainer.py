@@ -95,12 +95,53 @@ class _Cycle:
             yield self.batches[i % len(self.batches)]
 
 
+def parse_label_groups(text):
+    """``--label_groups "0;1,2,3;6,7"`` -> [[0], [1, 2, 3], [6, 7]]: semicolons between the groups, commas
+    inside one. None or an empty string: None (the reference's single vehicle mask)."""
+    if text is None or not str(text).strip():
+        return None
+    groups = []
+    for part in str(text).split(";"):
+        items = [v.strip() for v in part.split(",") if v.strip()]
+        if not items:
+            raise ValueError(f"--label_groups {text!r}: an empty group")
+        groups.append([int(v) for v in items])
+    return groups
+
+
+def parse_pos_weight(text):
+    """``--pos_weight 2.13`` -> 2.13; ``--pos_weight 1.0,2.13,5.0`` -> [1.0, 2.13, 5.0] (one per class)."""
+    items = [v.strip() for v in str(text).split(",") if v.strip()]
+    if not items:
+        raise ValueError(f"--pos_weight {text!r}: no value")
+    vals = [float(v) for v in items]
+    return vals[0] if len(vals) == 1 else vals
+
+
+def _class_setup(label_groups, pos_weight):
+    """(groups or None, K, the loss's pos_weight): a list of weights must name one per class; a single-class
+    run keeps a float (the one-weight kernels), a list of one collapsing to it."""
+    from . import simbev, tools
+    groups = None if label_groups is None else [[int(c) for c in g] for g in label_groups]
+    if groups is not None:
+        simbev.group_bits(groups)
+    K = 1 if groups is None else len(groups)
+    if not tools.is_scalar_weight(pos_weight):
+        pos_weight = [float(v) for v in pos_weight]
+        if len(pos_weight) != K:
+            raise ValueError(f"pos_weight names {len(pos_weight)} classes, label_groups {K}")
+        if K == 1:
+            pos_weight = pos_weight[0]
+    return groups, K, pos_weight
+
+
 def build_step(grid_conf, data_aug_conf, bsz, device, *, dtype="bf16", lr=1e-3, weight_decay=1e-7,
-               max_grad_norm=5.0, pos_weight=2.13, skip_nonfinite=True, n_val=None) -> dict:
+               max_grad_norm=5.0, pos_weight=2.13, skip_nonfinite=True, n_val=None, label_groups=None) -> dict:
     """The model and its steps as bench.py's train branch builds them -- unused parameters frozen, one flat
     fp32 master per backward group, fused capturable Adam, TrainStep without a pre_step (the stager's
     commit stages the inverses) -- plus the stager and the EvalStep over the same static tensors. Nothing is
-    captured yet."""
+    captured yet. label_groups: K lists of BEV channels -> a model with outC = K and (B, K, X, Y) labels
+    (None: the reference's vehicle mask, outC = 1); pos_weight: a float, or one weight per class."""
     import lss_carla_amd as L
     from . import parallel, simbev, tools
     from .flat_params import FlatParamGroups, lss_backward_groups
@@ -108,7 +149,8 @@ def build_step(grid_conf, data_aug_conf, bsz, device, *, dtype="bf16", lr=1e-3, 
     from .train_step import EvalStep, TrainStep
 
     amp_dtype = torch.bfloat16 if dtype == "bf16" else None
-    model = L.compile_model(grid_conf, data_aug_conf, outC=1).to(device)
+    label_groups, outC, pos_weight = _class_setup(label_groups, pos_weight)
+    model = L.compile_model(grid_conf, data_aug_conf, outC=outC).to(device)
     model.bevencode.to(memory_format=torch.channels_last)
     model.camencode.up1.to(memory_format=torch.channels_last)
     model.train()
@@ -117,7 +159,7 @@ def build_step(grid_conf, data_aug_conf, bsz, device, *, dtype="bf16", lr=1e-3, 
     masters = flat.masters
     opt = torch.optim.Adam(masters, lr=lr, weight_decay=weight_decay, fused=True, capturable=True)
     stager = BatchStager(data_aug_conf["final_dim"], bsz, len(simbev.CAMERA_ORDER),
-                         (data_aug_conf["H"], data_aug_conf["W"]), grid_conf, device)
+                         (data_aug_conf["H"], data_aug_conf["W"]), grid_conf, device, label_groups=label_groups)
     model.static_inverses = (stager.hinv.pinv, stager.hinv.kinv)  # staged by the stager's commit
     loss_fn = tools.SimpleLoss(pos_weight).to(device)
     forward = flat.bind(model)
@@ -127,7 +169,7 @@ def build_step(grid_conf, data_aug_conf, bsz, device, *, dtype="bf16", lr=1e-3, 
     evaluate = EvalStep(model, forward, stager.inputs, stager.binimgs, n_valid=stager.n_valid,
                         pos_weight=pos_weight, amp_dtype=amp_dtype, n_samples=n_val)
     return {"model": model, "flat": flat, "masters": masters, "opt": opt, "stager": stager, "step": step,
-            "evaluate": evaluate, "loss_fn": loss_fn, "forward": forward}
+            "evaluate": evaluate, "loss_fn": loss_fn, "forward": forward, "label_groups": label_groups}
 
 
 def train(
@@ -171,6 +213,7 @@ def train(
     iou_step=100,
     cycle_batches=0,
     on_start: Optional[Callable[[dict], None]] = None,
+    label_groups=None,
 ):
     """Train LiftSplatShoot on a SimBEV tree; the reference's arguments (train_simbev.py:23-98) plus:
 
@@ -181,6 +224,9 @@ def train(
     loss_step / iou_step: the cadence of the loss and of the IoU / skipped-step reads (the reference's
     10 and 100). cycle_batches: cycle this many pre-decoded batches instead of reading the loader
     (measurement). on_start: called once, before the first step, with the loop's objects.
+    label_groups: K lists of BEV channels, one output class each (outC = K; None: the reference's vehicle
+    mask [[1, 2, 3]], outC = 1); pos_weight is then a float or a list of K. With K > 1 the ``val`` and
+    ``train_iou`` events carry ``iou_per_class`` and ``iou`` is the mean over the classes seen.
     Returns a summary dict (counter, epoch, best_val_iou, skipped, frames_per_s of the training steps)."""
     from . import checkpoint, simbev, tools
 
@@ -190,6 +236,9 @@ def train(
         raise NotImplementedError("ncams must be 6: validation uses every camera and the step's shape is static")
     if dtype not in ("bf16", "fp32"):
         raise ValueError(f"dtype {dtype!r}: bf16 or fp32")
+    label_groups, n_out, pos_weight = _class_setup(label_groups, pos_weight)
+    if resume is not None and os.path.exists(resume):
+        _check_head_classes(resume, n_out)  # before anything is built, loaded or captured
     os.makedirs(logdir, exist_ok=True)
     grid_conf = {"xbound": xbound, "ybound": ybound, "zbound": zbound, "dbound": dbound}
     data_aug_conf = {"resize_lim": resize_lim, "final_dim": final_dim, "rot_lim": rot_lim, "H": H, "W": W,
@@ -199,6 +248,8 @@ def train(
               "final_dim": list(final_dim), "max_grad_norm": max_grad_norm, "pos_weight": pos_weight,
               "grid_conf": grid_conf, "val_step": val_step, "save_step": save_step, "graph": bool(graph),
               "dtype": dtype, "seed": seed}
+    if label_groups is not None:
+        config["label_groups"] = label_groups
     log = _Log(logdir, use_wandb, {"project": wandb_project, "name": wandb_name, "entity": wandb_entity}, config)
 
     device = torch.device(f"cuda:{gpuid}")
@@ -219,7 +270,7 @@ def train(
 
     ctx = build_step(grid_conf, data_aug_conf, bsz, device, dtype=dtype, lr=lr, weight_decay=weight_decay,
                      max_grad_norm=max_grad_norm, pos_weight=pos_weight, skip_nonfinite=skip_nonfinite,
-                     n_val=n_val)
+                     n_val=n_val, label_groups=label_groups)
     model, flat, masters, opt = ctx["model"], ctx["flat"], ctx["masters"], ctx["opt"]
     stager, step, evaluate = ctx["stager"], ctx["step"], ctx["evaluate"]
 
@@ -308,16 +359,25 @@ def train(
                 last_loss = float(loss.item())
                 log.event("train", counter, epoch=epoch, loss=last_loss)
             if counter % iou_step == 0:
-                _, _, iou = tools.get_batch_iou(step.static_preds, stager.binimgs)
+                extra = {}
+                if n_out > 1:
+                    ci, cu = tools.get_batch_iou_per_class(step.static_preds, stager.binimgs)
+                    ci, cu = ci.tolist(), cu.tolist()
+                    extra["iou_per_class"] = [i / u if u > 0 else None for i, u in zip(ci, cu)]
+                    seen = [v for v in extra["iou_per_class"] if v is not None]
+                    iou = sum(seen) / len(seen) if seen else 1.0  # (get_batch_iou's value for an empty union)
+                else:
+                    _, _, iou = tools.get_batch_iou(step.static_preds, stager.binimgs)
                 skipped = int(step.skipped.item()) if step.skipped is not None else 0
-                log.event("train_iou", counter, epoch=epoch, iou=iou, skipped=skipped)
+                log.event("train_iou", counter, epoch=epoch, iou=iou, skipped=skipped, **extra)
             if will_val or counter % save_step == 0:
                 torch.cuda.synchronize(device)
                 t_train += time.perf_counter() - t_mark
             if will_val:
                 info = validate()
                 print(f"  Validation at {counter} - Loss: {info['loss']:.4f}, IoU: {info['iou']:.4f}")
-                log.event("val", counter, epoch=epoch, loss=info["loss"], iou=info["iou"])
+                extra = {"iou_per_class": info["iou_per_class"]} if n_out > 1 else {}
+                log.event("val", counter, epoch=epoch, loss=info["loss"], iou=info["iou"], **extra)
                 if info["iou"] > best_val_iou:
                     best_val_iou = info["iou"]
                     save(os.path.join(logdir, "model_best.pt"), epoch, best_val_iou)
@@ -350,6 +410,17 @@ def train(
             "skipped": skipped, "frames_per_s": fps, "loss": last_loss}
 
 
+def _check_head_classes(path, n_out: int) -> None:
+    """A checkpoint whose head (bevencode.up2.4) has another number of output classes than this run's
+    label_groups ask for cannot be resumed: say so with both numbers."""
+    ckpt = torch.load(path, map_location="cpu")
+    sd = ckpt["model_state_dict"] if isinstance(ckpt, dict) and "model_state_dict" in ckpt else ckpt
+    w = sd.get("bevencode.up2.4.weight") if isinstance(sd, dict) else None
+    if w is not None and int(w.shape[0]) != n_out:
+        raise RuntimeError(f"resume: the checkpoint {path} has a head of {int(w.shape[0])} output classes "
+                           f"(bevencode.up2.4.weight {tuple(w.shape)}), this run's label_groups ask for {n_out}")
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description="Train LSS on a SimBEV dataset (captured step on the MI355X)")
     p.add_argument("--dataroot", type=str, required=True, help="SimBEV dataset root directory")
@@ -379,13 +450,17 @@ def main(argv=None):
     p.add_argument("--seed", type=int, default=None)
     p.add_argument("--max_steps", type=int, default=None)
     p.add_argument("--skip_nonfinite", type=int, default=1)
+    p.add_argument("--label_groups", type=str, default=None,
+                   help='BEV channel groups, one output class each: "0;1,2,3;6,7" (default: the vehicle mask 1,2,3)')
+    p.add_argument("--pos_weight", type=str, default="2.13", help="one positive-class weight, or one per class: 1.0,2.13,5.0")
     a = p.parse_args(argv)
     return train(dataroot=a.dataroot, nepochs=a.nepochs, gpuid=a.gpuid, H=a.H, W=a.W, final_dim=(a.final_h, a.final_w),
                  ncams=a.ncams, bsz=a.bsz, nworkers=a.nworkers, lr=a.lr, weight_decay=a.weight_decay, logdir=a.logdir,
                  val_step=a.val_step, save_step=a.save_step, resume=a.resume, use_wandb=a.use_wandb,
                  wandb_project=a.wandb_project, wandb_name=a.wandb_name, wandb_entity=a.wandb_entity,
                  graph=bool(a.graph), dtype=a.dtype, miopen_find=bool(a.miopen_find), seed=a.seed,
-                 max_steps=a.max_steps, skip_nonfinite=bool(a.skip_nonfinite))
+                 max_steps=a.max_steps, skip_nonfinite=bool(a.skip_nonfinite),
+                 label_groups=parse_label_groups(a.label_groups), pos_weight=parse_pos_weight(a.pos_weight))
 
 
 if __name__ == "__main__":

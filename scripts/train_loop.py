@@ -5,6 +5,8 @@ train_loop step): one JSON line {"frames_per_s", "steps", "nworkers", "cycle_bat
   python scripts/train_loop.py --dataroot DIR --steps 200 --cycle-batches 4        pre-decoded host batches cycled:
                                                                                     the step plus the staging only
   python scripts/train_loop.py --make DIR --samples 2000                           write the tree and exit
+  python scripts/train_loop.py --dataroot DIR --label-groups "0;1,2;3"             a multi-class run (on a tree made
+                                                                                    with --box-classes 0,1,2,3)
 """
 from __future__ import annotations
 
@@ -29,13 +31,17 @@ def main():
     ap.add_argument("--cycle-batches", type=int, default=0)
     ap.add_argument("--graph", type=int, default=1)
     ap.add_argument("--miopen-find", type=int, default=0)
+    ap.add_argument("--label-groups", default="", help='trainer --label_groups, e.g. "0;1,2;3" (default: the vehicle mask)')
+    ap.add_argument("--pos-weight", default="2.13", help="trainer --pos_weight: one weight, or one per class")
+    ap.add_argument("--box-classes", default="1,2,3", help="--make: the BEV channels the boxes are drawn in")
     a = ap.parse_args()
     from lss_carla_amd import miopen_db
     miopen_db.use_committed()  # before torch starts
     from lss_carla_amd import synthetic as syn
     if a.make:
         per_scene = 20
-        n = syn.make_simbev_tree(a.make, (a.samples + per_scene - 1) // per_scene, per_scene)
+        n = syn.make_simbev_tree(a.make, (a.samples + per_scene - 1) // per_scene, per_scene,
+                                 box_classes=tuple(int(c) for c in a.box_classes.split(",")))
         print(json.dumps({"made": a.make, "samples": n}))
         return
     from lss_carla_amd import trainer
@@ -43,10 +49,11 @@ def main():
         out = trainer.train(a.dataroot, nepochs=1000, bsz=a.bsz, nworkers=a.nworkers, logdir=logdir,
                             val_step=10 ** 9, save_step=10 ** 9, use_wandb=False, graph=bool(a.graph),
                             miopen_find=bool(a.miopen_find), seed=0, max_steps=a.steps,
-                            cycle_batches=a.cycle_batches)
+                            cycle_batches=a.cycle_batches, label_groups=trainer.parse_label_groups(a.label_groups),
+                            pos_weight=trainer.parse_pos_weight(a.pos_weight))
     print(json.dumps({"frames_per_s": out["frames_per_s"], "steps": out["counter"], "bsz": a.bsz,
                       "nworkers": a.nworkers, "cycle_batches": a.cycle_batches, "graph": a.graph,
-                      "skipped": out["skipped"], "loss": out["loss"]}))
+                      "skipped": out["skipped"], "loss": out["loss"], "label_groups": a.label_groups or None}))
 
 
 if __name__ == "__main__":

@@ -312,14 +312,22 @@ int lss_upsample_bwd2(const void* dy, int32_t N, int32_t Hi, int32_t Wi, int32_t
  * masters. Weights and values are rounded to bf16 where bf16 autocast rounds them (conv operands,
  * pooled map, both conv outputs, swish, sigmoid). Saved for the backward: m (N, C) pooled means, r / h (N, sq) reduce-conv output and
  * its swish, sig (N, C); all fp32 buffers. Alignment: x, y (and dy, dx of lss_se_bwd) 8-B aligned
- * (four bf16 per access). */
+ * (four bf16 per access).
+ * (ABI 26) With the MLP tails (lss_se_tails) two launches: the plane means, whose last block of each image
+ * to finish also runs both 1x1 convs for that image (the arithmetic and its order are those of the separate MLP launches, so the
+ * values are the same bit for bit), then the scale pass. The hand-off is a ticket per image on a
+ * counter the library owns (zero between calls), with no waiting; see lss_se_tails. */
 int lss_se_fwd(const void* x, int32_t N, int32_t C, int32_t HW, const float* w1, const float* b1, const float* w2,
                const float* b2, int32_t sq, float* m, float* r, float* h, float* sig, void* y, void* stream);
 
 /* Backward: dx (bf16) = dy * sig + dm / HW (the excitation and the pooling paths), and the
  * per-image gradients the caller turns into parameter gradients with small GEMMs: de (N, C) =
  * d(expand-conv output), dr (N, sq) = d(reduce-conv output), dm (N, C) = d(pooled means).
- * Scratch: t (N, C) fp32 (sum over HW of dy * x), dh_part (N, ceil(C / 64), sq) fp32. */
+ * Scratch: t (N, C) fp32 (sum over HW of dy * x), dh_part (N, ceil(C / 64), sq) fp32.
+ * (ABI 26) With the MLP tails two launches, as the forward: the plane sums t with the MLP backward in each image's last
+ * block, then dx. The per-chunk partials of dh then stay on chip: dh_part must still be a valid buffer
+ * of that size, its contents after the call are unspecified (the tails leave it untouched, the fallback
+ * sequence of lss_se_tails stores the partials in it). */
 int lss_se_bwd(const void* dy, const void* x, int32_t N, int32_t C, int32_t HW, const float* w1, const float* w2,
                int32_t sq, const float* r, const float* sig, float* t, float* dh_part, float* de, float* dr, float* dm,
                void* dx, void* stream);
@@ -329,6 +337,20 @@ int lss_se_bwd(const void* dy, const void* x, int32_t N, int32_t C, int32_t HW, 
  * db2 (C) = sum_n de. */
 int lss_se_wgrad(const float* de, const float* h, const float* dr, const float* m, int32_t N, int32_t C, int32_t sq,
                  float* dw1, float* db1, float* dw2, float* db2, void* stream);
+
+/* (ABI 26) Switch of the per-image MLP tails in lss_se_fwd / lss_se_bwd. Settings:
+ *   0  off: the earlier sequence of four launches each (mean / dot, two MLP kernels, scale / dx);
+ *   1  on (the default): two launches each for the shapes where that measured faster -- small weight
+ *      matrices, C * sq <= 1024 forward and <= 4096 backward -- and the earlier sequence for the rest;
+ *   2  on for every shape (tests, tuning).
+ * N > LSS_SE_TAIL_MAX_IMAGES (one counter word per image) always takes the earlier sequence. The results
+ * are equal bit for bit whichever sequence runs. Sets the process-wide setting (on <= 0: 0, on >= 2: 2)
+ * and returns the previous one; a captured graph keeps the sequence it was captured with.
+ * Streams: the counters are per device, in a few banks that successive calls take in turn. That makes
+ * two calls in flight at once on two streams of one device unlikely to share counters, not unable to:
+ * the supported use is one stream per device, as for the batch-norm sync workspace. */
+#define LSS_SE_TAIL_MAX_IMAGES 4096
+int lss_se_tails(int on);
 
 #ifdef __cplusplus
 }

@@ -13,10 +13,13 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
-SOURCES = [os.path.join(HERE, "csrc", f) for f in ("lss_hip.hip", "lss_convs.hip", "lss_bnorm.hip",
+SOURCES = [os.path.join(HERE, "csrc", f) for f in ("lss_hip.hip", "lss_dwconv.hip", "lss_head.hip", "lss_pointwise.hip",
+                                                            "lss_loss.hip", "lss_elementwise.hip", "lss_bnorm.hip",
                                                             "lss_resample.hip", "lss_se.hip", "lss_simbev.hip",
                                                             "lss_ceiling.hip", "lss_optim.hip")]
-HEADERS = [os.path.join(REPO, "include", h) for h in ("lss_hip.h", "lss_convs.h", "lss_simbev.h")]
+# the C ABI (include/) and the helpers the .hip files share (csrc/lss_device.h, found next to the file that includes it)
+HEADERS = [os.path.join(REPO, "include", h) for h in ("lss_hip.h", "lss_convs.h", "lss_simbev.h")] + \
+    [os.path.join(HERE, "csrc", "lss_device.h")]
 OUT = os.path.join(HERE, "liblss_hip.so")
 # LSS_DEBUG build: every data-derived index checked on the device (include/lss_hip.h, lss_debug_status);
 # loaded instead of the product library when LSS_DEBUG=1 (_lib.py)

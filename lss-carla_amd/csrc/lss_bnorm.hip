@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include "lss_convs.h"
+#include "lss_device.h"
 
 // The library is built with -ffp-contract=off for the geometry's reference op order (lss_hip.hip);
 // the conv-stack kernels here have no bit-exact contract, so they keep FMA contraction.
@@ -35,9 +36,7 @@
 
 namespace {
 
-using bf16 = __hip_bfloat16;
 constexpr int kBlock = 256;
-constexpr int kWave = 64;
 #ifndef LSS_BN_GMAX
 #define LSS_BN_GMAX 4096
 #endif
@@ -50,65 +49,9 @@ constexpr int kWave = 64;
 constexpr int kMaxGroupsNhwc = 4096;  // partial groups the ABI accepts (NHWC)
 constexpr int kGroupsNhwc = LSS_BN_GMAX;  // groups lss_bn_groups picks at most (NHWC)
 
-__device__ __forceinline__ float ld(const float* p) { return *p; }
-__device__ __forceinline__ float ld(const bf16* p) { return __bfloat162float(*p); }
-
-// V consecutive elements <-> fp32 (V in {1, 4, 8})
-template <int V> __device__ __forceinline__ void ldv(const float* p, float* o) {
-    if constexpr (V == 1) {
-        o[0] = *p;
-    } else {
-#pragma unroll
-        for (int i = 0; i < V; i += 4) {
-            const float4 a = *reinterpret_cast<const float4*>(p + i);
-            o[i] = a.x; o[i + 1] = a.y; o[i + 2] = a.z; o[i + 3] = a.w;
-        }
-    }
-}
-template <int V> __device__ __forceinline__ void ldv(const bf16* p, float* o) {
-    if constexpr (V == 1) {
-        o[0] = __bfloat162float(*p);
-    } else {
-        unsigned w[V / 2];
-        if constexpr (V == 8) {
-            const uint4 u = *reinterpret_cast<const uint4*>(p);
-            w[0] = u.x; w[1] = u.y; w[2] = u.z; w[3] = u.w;
-        } else {
-            const uint2 u = *reinterpret_cast<const uint2*>(p);
-            w[0] = u.x; w[1] = u.y;
-        }
-#pragma unroll
-        for (int i = 0; i < V / 2; ++i) {
-            o[2 * i] = __uint_as_float(w[i] << 16);
-            o[2 * i + 1] = __uint_as_float(w[i] & 0xFFFF0000u);
-        }
-    }
-}
-template <int V> __device__ __forceinline__ void stv(float* p, const float* v) {
-    if constexpr (V == 1) {
-        *p = v[0];
-    } else {
-#pragma unroll
-        for (int i = 0; i < V; i += 4) *reinterpret_cast<float4*>(p + i) = make_float4(v[i], v[i + 1], v[i + 2], v[i + 3]);
-    }
-}
-template <int V> __device__ __forceinline__ void stv(bf16* p, const float* v) {
-    if constexpr (V == 1) {
-        *p = __float2bfloat16(v[0]);
-    } else {
-        bf16 b[V];
-#pragma unroll
-        for (int i = 0; i < V; ++i) b[i] = __float2bfloat16(v[i]);
-        if constexpr (V == 8) *reinterpret_cast<uint4*>(p) = *reinterpret_cast<const uint4*>(b);
-        else *reinterpret_cast<uint2*>(p) = *reinterpret_cast<const uint2*>(b);
-    }
-}
-
-__device__ __forceinline__ float sigmoidf(float z) { return 1.f / (1.f + __expf(-z)); }
-
 __device__ __forceinline__ float act_fwd(float z, int act) {
     if (act == LSS_ACT_RELU) return fmaxf(z, 0.f);
-    if (act == LSS_ACT_SWISH) return z * sigmoidf(z);
+    if (act == LSS_ACT_SWISH) return z * sigmoid(z);
     return z;
 }
 
@@ -116,7 +59,7 @@ __device__ __forceinline__ float act_fwd(float z, int act) {
 __device__ __forceinline__ float grad_pre(float dy, float y, float z, int act) {
     if (act == LSS_ACT_RELU) return y > 0.f ? dy : 0.f;
     if (act == LSS_ACT_SWISH) {
-        const float s = sigmoidf(z);
+        const float s = sigmoid(z);
         return dy * s * (1.f + z * (1.f - s));
     }
     return dy;
@@ -610,15 +553,6 @@ constexpr int kBnSyncMaxC = 4096;   // channels a sync workspace covers (+ the s
 constexpr int kBnSyncStride = 32;   // words per channel: its two counters alone in a 128-B line (a line
                                     // shared by the counters of many channels serialised every poll)
 
-__device__ __forceinline__ void st_pair_agent(float* p, float a, float b) {
-    const unsigned long long v = ((unsigned long long)__float_as_uint(b) << 32) | __float_as_uint(a);
-    __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float2 ld_pair_agent(const float* p) {
-    const unsigned long long v =
-        __hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return make_float2(__uint_as_float((unsigned)v), __uint_as_float((unsigned)(v >> 32)));
-}
 
 // thread 0: publish (a, b) as group q's pair, arrive, wait for the cluster; true = all G arrived.
 // limit_word (the workspace's last word): 0 = kBnSpinLimit polls, s > 0 = s - 1 (tests of the timeout path)
@@ -1256,11 +1190,6 @@ __global__ __launch_bounds__(kBlock) void k_bn_bwd_apply_rows_nhwc(const T* __re
 }
 
 // ============================================================================= host side
-inline int launch_status() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
-}
-
 inline bool bn_ok(const BnGeo& g, int layout) {
     if (g.N <= 0 || g.C <= 0 || g.HW <= 0 || (long)g.N * g.C * g.HW >= INT_MAX) return false;
     if (layout == LSS_CONV_NHWC) return g.C % 8 == 0 && g.C / 8 <= kBlock && kBlock % (g.C / 8) == 0;

@@ -27,24 +27,16 @@
 #include <type_traits>
 
 #include "lss_hip.h"
+#include "lss_device.h"
 
 namespace {
 
 constexpr int kC = 64;       // camC (src/models.py:148)
-constexpr int kWave = 64;
 constexpr int kBlock = 256;
 constexpr int kScanItems = 4096;  // cells per scan block (1024 threads x 4)
 
-using bf16 = __hip_bfloat16;
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
-
-__device__ __forceinline__ float to_f32(float v) { return v; }
-__device__ __forceinline__ float to_f32(bf16 v) { return __bfloat162float(v); }
-
-template <typename T> __device__ __forceinline__ T from_f32(float v);
-template <> __device__ __forceinline__ float from_f32<float>(float v) { return v; }
-template <> __device__ __forceinline__ bf16 from_f32<bf16>(float v) { return __float2bfloat16(v); }
 
 // 4 consecutive elements, 16 B (fp32) or 8 B (bf16) store.
 __device__ __forceinline__ void store4(float* dst, float a, float b, float c, float d) {
@@ -68,25 +60,6 @@ __device__ __forceinline__ float readlane_f(float v, int lane) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
 }
 
-// "v if c else 0" without a branch: the mask goes through an empty asm, so the compiler cannot turn
-// the AND back into a select and then into a branch around the load that produced v (it sinks such
-// loads into conditional blocks, and the blocks serialise loads that should all be in flight).
-__device__ __forceinline__ unsigned keep_mask(bool c) {
-    unsigned m = c ? 0xFFFFFFFFu : 0u;
-    asm("" : "+v"(m));
-    return m;
-}
-__device__ __forceinline__ uint4 keep_if(bool c, uint4 v) {
-    const unsigned m = keep_mask(c);
-    return make_uint4(v.x & m, v.y & m, v.z & m, v.w & m);
-}
-__device__ __forceinline__ float keep_if(bool c, float v) { return __uint_as_float(__float_as_uint(v) & keep_mask(c)); }
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-    return v;
-}
 __device__ __forceinline__ int wave_sum_i(int v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
@@ -602,12 +575,6 @@ __device__ unsigned long long scan_fill_missing(unsigned long long x, int jb, co
     }
     return x;
 }
-__device__ __forceinline__ unsigned long long ld_agent(const unsigned long long* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st_agent(unsigned long long* p, unsigned long long v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // cmask: the count bits of a cell word (-1: plain counts; kOrdCountMask: ordered-plan words)
 __global__ __launch_bounds__(1024) void k_scan_lookback(const int32_t* __restrict__ cnt, int ncells,
@@ -977,9 +944,9 @@ __global__ __launch_bounds__(kBlock) void k_lift_prep(const InT* __restrict__ dn
     const InT* src = dn + (size_t)bn * (D + kC) * HW + hw;
     float cv[16], l[NI];
 #pragma unroll
-    for (int i = 0; i < 16; ++i) cv[i] = to_f32(src[(size_t)(D + part * 16 + i) * HW]);
+    for (int i = 0; i < 16; ++i) cv[i] = ld(&src[(size_t)(D + part * 16 + i) * HW]);
 #pragma unroll
-    for (int i = 0; i < NI; ++i) l[i] = to_f32(src[(size_t)min(part + 4 * i, D - 1) * HW]);
+    for (int i = 0; i < NI; ++i) l[i] = ld(&src[(size_t)min(part + 4 * i, D - 1) * HW]);
     float m = -INFINITY;
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
@@ -1565,7 +1532,7 @@ __device__ float reduce_big_cell(int start, int nprime, const long long* __restr
         const int r = mine ? dchk(FUSED ? row[e] : (int)(k & 0xFFFFFFFF), nrows, kDbgSplatRow) : 0;
         const float w = (FUSED && mine) ? depth[dchk((int)(k & 0xFFFFFFFF), nprime, kDbgSplatPoint)] : 1.f;
         for (int i = 0; i < n; ++i) {
-            const float v = to_f32(rows_base[(size_t)__builtin_amdgcn_readlane(r, i) * kC + lane]);
+            const float v = ld(&rows_base[(size_t)__builtin_amdgcn_readlane(r, i) * kC + lane]);
             acc = FUSED ? fmaf(readlane_f(w, i), v, acc) : __fadd_rn(acc, v);
         }
         if (n < kWave) break;
@@ -2150,7 +2117,7 @@ __global__ __launch_bounds__(kBlock) void k_bev_rows(const GT* __restrict__ dbev
     } else {
         for (int i = threadIdx.x; i < kC * ny; i += kBlock) {
             const int c = i / ny, yy = i - c * ny;
-            lds[c * S + yy] = to_f32(gbase[c * XY + yy]);
+            lds[c * S + yy] = ld(&gbase[c * XY + yy]);
         }
     }
     __syncthreads();
@@ -2199,7 +2166,7 @@ __global__ __launch_bounds__(kBlock) void k_splat_bwd_reg(const GT* __restrict__
     const int sub = lane / LPR, col = (lane % LPR) * EPL;
     float cx[EPL];
 #pragma unroll
-    for (int e = 0; e < EPL; ++e) cx[e] = to_f32(ctx_t[(size_t)q * kC + col + e]);
+    for (int e = 0; e < EPL; ++e) cx[e] = ld(&ctx_t[(size_t)q * kC + col + e]);
     float dc[EPL];
 #pragma unroll
     for (int e = 0; e < EPL; ++e) dc[e] = 0.f;
@@ -2484,7 +2451,7 @@ __global__ __launch_bounds__(kBlock) void k_splat_bwd_lifted(const GT* __restric
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     if (cell >= 0) {
         const GT* r = g + row_offset<NHWC>(cell, sg) + j;
-        v = make_float4(to_f32(r[0]), to_f32(r[1]), to_f32(r[2]), to_f32(r[3]));
+        v = make_float4(ld(&r[0]), ld(&r[1]), ld(&r[2]), ld(&r[3]));
     }
     *reinterpret_cast<float4*>(dx + (size_t)p * kC + j) = v;
 }
@@ -2565,8 +2532,6 @@ __global__ __launch_bounds__(kBlock) void k_seg_gather(const float* __restrict__
 }
 
 // ----------------------------------------------------------------------------- host helpers
-inline int grid_blocks(long n, int per) { return (int)((n + per - 1) / per); }
-
 // Compute units of the current device, cached per device id (the library's only global state).
 inline int device_cus() {
     static std::atomic<int> cache[64];
@@ -2611,11 +2576,6 @@ inline SplatGeo splat_geo(const lss_grid_t* g, const lss_dims_t* d, long nrows =
     s.nprime = (int)std::min<long>(pix * d->D, INT_MAX);
     s.nrows = (int)std::min<long>(nrows > 0 ? nrows : pix, INT_MAX);
     return s;
-}
-
-inline int launch_status() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
 }
 
 // LSS_DEBUG builds: the CSR invariants after every build (k_debug_csr); nothing in release builds.

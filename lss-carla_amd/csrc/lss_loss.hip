@@ -1,0 +1,508 @@
+// lss_loss.hip -- SimpleLoss (src/tools.py:222-230): BCEWithLogitsLoss(pos_weight), mean over the n elements,
+// with its input gradient computed in the same pass. Per element (torch's formula for pos_weight):
+//   lw = 1 + (pw - 1) t,  l = (1 - t) x + lw (log1p(exp(-|x|)) + max(-x, 0)),
+//   dl/dx = lw sigmoid(x) - pw t = (1 - t) sigmoid(x) - pw t sigmoid(-x)
+// Thread = 8 consecutive elements; block sums in a fixed order (wave butterflies, then the 4 waves
+// in order) into partial[block]; k_bce_total folds the partials in block order. fp32 arithmetic for
+// fp32 and bf16 logits (a bf16 input is the same as its exact fp32 cast); the gradient (times 1 / n)
+// is written in the logits' type.
+
+#include <limits.h>
+
+#include "lss_convs.h"
+#include "lss_device.h"
+
+// The library is built with -ffp-contract=off for the geometry's reference op order (lss_hip.hip);
+// the conv-stack kernels here have no bit-exact contract, so they keep FMA contraction.
+#pragma clang fp contract(fast)
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kBceVpt = 8;
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_bce_fwd(const T* __restrict__ x, const float* __restrict__ t, long long n,
+                                                    float pw, float inv_n, float* __restrict__ partial,
+                                                    T* __restrict__ grad) {
+    __shared__ float s_w[kBlock / kWave];
+    const long long i0 = ((long long)blockIdx.x * kBlock + threadIdx.x) * kBceVpt;
+    float xv[kBceVpt], tv[kBceVpt], gv[kBceVpt];
+    const bool full = i0 + kBceVpt <= n;
+    if (full) {
+        ldv<8>(x + i0, xv);
+        const float4 a = *reinterpret_cast<const float4*>(t + i0), b = *reinterpret_cast<const float4*>(t + i0 + 4);
+        tv[0] = a.x; tv[1] = a.y; tv[2] = a.z; tv[3] = a.w; tv[4] = b.x; tv[5] = b.y; tv[6] = b.z; tv[7] = b.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < kBceVpt; ++j) {
+            xv[j] = i0 + j < n ? ld(x + i0 + j) : 0.f;
+            tv[j] = i0 + j < n ? t[i0 + j] : 0.f;
+        }
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < kBceVpt; ++j) {
+        const float xx = xv[j], tt = tv[j];
+        const float lw = fmaf(pw - 1.f, tt, 1.f);
+        const float e = expf(-fabsf(xx));
+        const float l = (1.f - tt) * xx + lw * (log1pf(e) + fmaxf(-xx, 0.f));
+        // lw sigmoid(x) - pw t = (1 - t) sigmoid(x) - pw t sigmoid(-x): no cancellation for saturated x
+        const float sp = 1.f / (1.f + e), sn = e / (1.f + e);  // sigmoid(|x|), sigmoid(-|x|)
+        const float sx = xx >= 0.f ? sp : sn, smx = xx >= 0.f ? sn : sp;
+        gv[j] = ((1.f - tt) * sx - pw * tt * smx) * inv_n;
+        if (i0 + j < n) s += l;
+    }
+    if (full) stv<8>(grad + i0, gv);
+    else {
+#pragma unroll
+        for (int j = 0; j < kBceVpt; ++j)
+            if (i0 + j < n) st(grad + i0 + j, gv[j]);
+    }
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, kWave);
+    if ((threadIdx.x & (kWave - 1)) == 0) s_w[threadIdx.x / kWave] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float b = 0.f;
+#pragma unroll
+        for (int w = 0; w < kBlock / kWave; ++w) b += s_w[w];
+        partial[blockIdx.x] = b;
+    }
+}
+
+// dx = grad * gout[0] (the incoming gradient of the loss, read on the device), rounded once to T
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_bce_bwd(const T* __restrict__ grad, long long n, const float* __restrict__ gout,
+                                                    T* __restrict__ dx) {
+    const long long i0 = ((long long)blockIdx.x * kBlock + threadIdx.x) * kBceVpt;
+    const float gs = gout[0];
+    float v[kBceVpt];
+    if (i0 + kBceVpt <= n) {
+        ldv<8>(grad + i0, v);
+#pragma unroll
+        for (int j = 0; j < kBceVpt; ++j) v[j] *= gs;
+        stv<8>(dx + i0, v);
+    } else {
+        for (long long i = i0; i < n; ++i) st(dx + i, ld(grad + i) * gs);
+    }
+}
+
+// loss = (sum of the block partials, lanes strided over blocks then a fixed butterfly) / n
+__global__ __launch_bounds__(kWave) void k_bce_total(const float* __restrict__ partial, int nb, float inv_n,
+                                                     float* __restrict__ loss) {
+    float s = 0.f;
+    for (int b = threadIdx.x; b < nb; b += kWave) s += partial[b];
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, kWave);
+    if (threadIdx.x == 0) loss[0] = s * inv_n;
+}
+
+// ---- Validation metrics (get_val_info, src/tools.py:243-270) over the first n_valid samples of a batch,
+// one pass: per element the loss term of k_bce_fwd (the same fp32 expression) and the two IoU predicates.
+// The valid samples are the leading `limit = n_valid * per_sample` elements, so the mask is per element:
+// i < limit. Thread = 8 consecutive elements; the loss terms are summed in fp64 and the counts in integers,
+// in a fixed order (lane, wave butterfly, the 4 waves in order) into one record per block; k_bce_iou_fold
+// (one block) folds the records in block order and adds to totals[3].
+struct BceIouPartial {
+    double loss;
+    long long inter, uni;
+};
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_bce_iou(const T* __restrict__ x, const float* __restrict__ t,
+                                                    long long per_sample, int batch, const int* __restrict__ n_valid,
+                                                    float pw, int vec, BceIouPartial* __restrict__ partial) {
+    __shared__ double s_l[kBlock / kWave];
+    __shared__ int s_i[kBlock / kWave], s_u[kBlock / kWave];
+    int nv = n_valid ? n_valid[0] : batch;
+    nv = nv < 0 ? 0 : (nv > batch ? batch : nv);
+    const long long limit = (long long)nv * per_sample;
+    const long long i0 = ((long long)blockIdx.x * kBlock + threadIdx.x) * kBceVpt;
+    double s = 0.0;
+    int ni = 0, nu = 0;
+    if (i0 < limit) {
+        float xv[kBceVpt], tv[kBceVpt];
+        if (vec && i0 + kBceVpt <= limit) {
+            ldv<8>(x + i0, xv);
+            const float4 a = *reinterpret_cast<const float4*>(t + i0), b = *reinterpret_cast<const float4*>(t + i0 + 4);
+            tv[0] = a.x; tv[1] = a.y; tv[2] = a.z; tv[3] = a.w; tv[4] = b.x; tv[5] = b.y; tv[6] = b.z; tv[7] = b.w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < kBceVpt; ++j) {
+                xv[j] = i0 + j < limit ? ld(x + i0 + j) : 0.f;
+                tv[j] = i0 + j < limit ? t[i0 + j] : 0.f;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < kBceVpt; ++j) {
+            const float xx = xv[j], tt = tv[j];
+            const float lw = fmaf(pw - 1.f, tt, 1.f);
+            const float e = expf(-fabsf(xx));
+            const float l = (1.f - tt) * xx + lw * (log1pf(e) + fmaxf(-xx, 0.f));
+            if (i0 + j < limit) {
+                s += (double)l;
+                const bool p = xx > 0.f, q = tt != 0.f;
+                ni += (p && q) ? 1 : 0;
+                nu += (p || q) ? 1 : 0;
+            }
+        }
+    }
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+        s += __shfl_xor(s, o, kWave);
+        ni += __shfl_xor(ni, o, kWave);
+        nu += __shfl_xor(nu, o, kWave);
+    }
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+        s_l[threadIdx.x / kWave] = s;
+        s_i[threadIdx.x / kWave] = ni;
+        s_u[threadIdx.x / kWave] = nu;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        BceIouPartial r{0.0, 0, 0};
+#pragma unroll
+        for (int w = 0; w < kBlock / kWave; ++w) {
+            r.loss += s_l[w];
+            r.inter += s_i[w];
+            r.uni += s_u[w];
+        }
+        partial[blockIdx.x] = r;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_bce_iou_fold(const BceIouPartial* __restrict__ partial, int nb,
+                                                         double per_sample, double* __restrict__ totals) {
+    __shared__ double s_l[kBlock / kWave];
+    __shared__ long long s_i[kBlock / kWave], s_u[kBlock / kWave];
+    double s = 0.0;
+    long long ni = 0, nu = 0;
+    for (int b = threadIdx.x; b < nb; b += kBlock) {
+        const BceIouPartial r = partial[b];
+        s += r.loss;
+        ni += r.inter;
+        nu += r.uni;
+    }
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+        s += __shfl_xor(s, o, kWave);
+        ni += __shfl_xor(ni, o, kWave);
+        nu += __shfl_xor(nu, o, kWave);
+    }
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+        s_l[threadIdx.x / kWave] = s;
+        s_i[threadIdx.x / kWave] = ni;
+        s_u[threadIdx.x / kWave] = nu;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double l = 0.0;
+        long long a = 0, u = 0;
+#pragma unroll
+        for (int w = 0; w < kBlock / kWave; ++w) {
+            l += s_l[w];
+            a += s_i[w];
+            u += s_u[w];
+        }
+        totals[0] += l / per_sample;
+        totals[1] += (double)a;
+        totals[2] += (double)u;
+    }
+}
+
+// ---- The per-class forms (multi-class BEV: logits (N, K, H, W) contiguous, plane = H W): element i belongs
+// to class (i / plane) % K and takes pos_weight[class] from device memory (a captured graph replays with
+// the current weights). A thread's 8 elements may cross a plane boundary (plane % 8 != 0), so the class is
+// walked per element: one division per thread, then increments. Partition, per-element expression and
+// folds are k_bce_fwd's / k_bce_iou's, so equal weights (K = 1 for the metrics) give the same bits.
+struct ClassWalk {
+    long long rem, plane;  // position inside the plane
+    int k, K;
+    __device__ ClassWalk(long long i0, long long plane_, int K_) : plane(plane_), K(K_) {
+        const long long p = i0 / plane_;
+        rem = i0 - p * plane_;
+        k = (int)(p % K_);
+    }
+    __device__ __forceinline__ void next() {
+        if (++rem == plane) {
+            rem = 0;
+            k = k + 1 == K ? 0 : k + 1;
+        }
+    }
+};
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_bce_fwd_pc(const T* __restrict__ x, const float* __restrict__ t,
+                                                       long long n, long long plane, int K,
+                                                       const float* __restrict__ pwc, float inv_n,
+                                                       float* __restrict__ partial, T* __restrict__ grad) {
+    __shared__ float s_w[kBlock / kWave];
+    const long long i0 = ((long long)blockIdx.x * kBlock + threadIdx.x) * kBceVpt;
+    float xv[kBceVpt], tv[kBceVpt], gv[kBceVpt];
+    const bool full = i0 + kBceVpt <= n;
+    if (full) {
+        ldv<8>(x + i0, xv);
+        const float4 a = *reinterpret_cast<const float4*>(t + i0), b = *reinterpret_cast<const float4*>(t + i0 + 4);
+        tv[0] = a.x; tv[1] = a.y; tv[2] = a.z; tv[3] = a.w; tv[4] = b.x; tv[5] = b.y; tv[6] = b.z; tv[7] = b.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < kBceVpt; ++j) {
+            xv[j] = i0 + j < n ? ld(x + i0 + j) : 0.f;
+            tv[j] = i0 + j < n ? t[i0 + j] : 0.f;
+        }
+    }
+    ClassWalk cw(i0, plane, K);
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < kBceVpt; ++j) {
+        const float xx = xv[j], tt = tv[j];
+        const float pw = pwc[cw.k];
+        cw.next();
+        const float lw = fmaf(pw - 1.f, tt, 1.f);
+        const float e = expf(-fabsf(xx));
+        const float l = (1.f - tt) * xx + lw * (log1pf(e) + fmaxf(-xx, 0.f));
+        const float sp = 1.f / (1.f + e), sn = e / (1.f + e);  // sigmoid(|x|), sigmoid(-|x|)
+        const float sx = xx >= 0.f ? sp : sn, smx = xx >= 0.f ? sn : sp;
+        gv[j] = ((1.f - tt) * sx - pw * tt * smx) * inv_n;
+        if (i0 + j < n) s += l;
+    }
+    if (full) stv<8>(grad + i0, gv);
+    else {
+#pragma unroll
+        for (int j = 0; j < kBceVpt; ++j)
+            if (i0 + j < n) st(grad + i0 + j, gv[j]);
+    }
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, kWave);
+    if ((threadIdx.x & (kWave - 1)) == 0) s_w[threadIdx.x / kWave] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float b = 0.f;
+#pragma unroll
+        for (int w = 0; w < kBlock / kWave; ++w) b += s_w[w];
+        partial[blockIdx.x] = b;
+    }
+}
+
+// Block record of the per-class metrics: partial = nb doubles (the loss terms, k_bce_iou's fp64 sum), then
+// nb x 2K int32 (intersection counts of the K classes, then union counts). A thread counts a run of one class
+// in registers and adds it to the block's LDS counters when the class changes (integer adds: any order).
+constexpr int kIouMaxClasses = 32;
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_bce_iou_pc(const T* __restrict__ x, const float* __restrict__ t,
+                                                       long long per_sample, int batch, const int* __restrict__ n_valid,
+                                                       long long plane, int K, const float* __restrict__ pwc, int vec,
+                                                       double* __restrict__ ploss, int* __restrict__ pcount) {
+    __shared__ double s_l[kBlock / kWave];
+    __shared__ int s_c[2 * kIouMaxClasses];
+    if (threadIdx.x < 2 * K) s_c[threadIdx.x] = 0;
+    __syncthreads();
+    int nv = n_valid ? n_valid[0] : batch;
+    nv = nv < 0 ? 0 : (nv > batch ? batch : nv);
+    const long long limit = (long long)nv * per_sample;
+    const long long i0 = ((long long)blockIdx.x * kBlock + threadIdx.x) * kBceVpt;
+    double s = 0.0;
+    if (i0 < limit) {
+        float xv[kBceVpt], tv[kBceVpt];
+        if (vec && i0 + kBceVpt <= limit) {
+            ldv<8>(x + i0, xv);
+            const float4 a = *reinterpret_cast<const float4*>(t + i0), b = *reinterpret_cast<const float4*>(t + i0 + 4);
+            tv[0] = a.x; tv[1] = a.y; tv[2] = a.z; tv[3] = a.w; tv[4] = b.x; tv[5] = b.y; tv[6] = b.z; tv[7] = b.w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < kBceVpt; ++j) {
+                xv[j] = i0 + j < limit ? ld(x + i0 + j) : 0.f;
+                tv[j] = i0 + j < limit ? t[i0 + j] : 0.f;
+            }
+        }
+        ClassWalk cw(i0, plane, K);
+        int ni = 0, nu = 0;
+#pragma unroll
+        for (int j = 0; j < kBceVpt; ++j) {
+            const float xx = xv[j], tt = tv[j];
+            const int k = cw.k;
+            const float pw = pwc[k];
+            cw.next();
+            const float lw = fmaf(pw - 1.f, tt, 1.f);
+            const float e = expf(-fabsf(xx));
+            const float l = (1.f - tt) * xx + lw * (log1pf(e) + fmaxf(-xx, 0.f));
+            if (i0 + j < limit) {
+                s += (double)l;
+                const bool p = xx > 0.f, q = tt != 0.f;
+                ni += (p && q) ? 1 : 0;
+                nu += (p || q) ? 1 : 0;
+            }
+            if (j == kBceVpt - 1 || cw.k != k) {  // the run of class k ends here
+                if (ni) atomicAdd(&s_c[k], ni);
+                if (nu) atomicAdd(&s_c[K + k], nu);
+                ni = nu = 0;
+            }
+        }
+    }
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, kWave);
+    if ((threadIdx.x & (kWave - 1)) == 0) s_l[threadIdx.x / kWave] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double l = 0.0;
+#pragma unroll
+        for (int w = 0; w < kBlock / kWave; ++w) l += s_l[w];
+        ploss[blockIdx.x] = l;
+    }
+    if (threadIdx.x < 2 * K) pcount[(size_t)blockIdx.x * 2 * K + threadIdx.x] = s_c[threadIdx.x];
+}
+
+// totals[0] += the loss records folded as k_bce_iou_fold folds them; totals[1 + k] += intersection of class k,
+// totals[1 + K + k] += its union (wave w sums the counters w, w + 4, ... over the blocks: integers).
+__global__ __launch_bounds__(kBlock) void k_bce_iou_fold_pc(const double* __restrict__ ploss,
+                                                            const int* __restrict__ pcount, int nb, int K,
+                                                            double per_sample, double* __restrict__ totals) {
+    __shared__ double s_l[kBlock / kWave];
+    double s = 0.0;
+    for (int b = threadIdx.x; b < nb; b += kBlock) s += ploss[b];
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, kWave);
+    if ((threadIdx.x & (kWave - 1)) == 0) s_l[threadIdx.x / kWave] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double l = 0.0;
+#pragma unroll
+        for (int w = 0; w < kBlock / kWave; ++w) l += s_l[w];
+        totals[0] += l / per_sample;
+    }
+    const int lane = threadIdx.x & (kWave - 1);
+    for (int c = threadIdx.x / kWave; c < 2 * K; c += kBlock / kWave) {
+        long long a = 0;
+        for (int b = lane; b < nb; b += kWave) a += pcount[(size_t)b * 2 * K + c];
+#pragma unroll
+        for (int o = kWave / 2; o > 0; o >>= 1) a += __shfl_xor(a, o, kWave);
+        if (lane == 0) totals[1 + c] += (double)a;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int lss_bce_logits(const void* x, int32_t dtype, const float* target, int64_t n, float pos_weight, float* partial,
+                   float* loss, void* grad, void* stream) {
+    const int esz = dtype == LSS_CONV_BF16 ? 2 : dtype == LSS_CONV_F32 ? 4 : 0;
+    if (!x || !target || !partial || !loss || !grad || !esz || n <= 0 ||
+        ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(grad)) & 15) ||
+        (reinterpret_cast<uintptr_t>(target) & 15))
+        return LSS_CONV_EINVAL;
+    const long long nb = (n + (long long)kBlock * kBceVpt - 1) / ((long long)kBlock * kBceVpt);
+    if (nb > INT_MAX) return LSS_CONV_EINVAL;
+    const float inv_n = 1.0f / (float)n;
+    hipStream_t s = (hipStream_t)stream;
+    if (esz == 2)
+        hipLaunchKernelGGL(k_bce_fwd<bf16>, dim3((unsigned)nb), dim3(kBlock), 0, s, (const bf16*)x, target, (long long)n,
+                           pos_weight, inv_n, partial, (bf16*)grad);
+    else
+        hipLaunchKernelGGL(k_bce_fwd<float>, dim3((unsigned)nb), dim3(kBlock), 0, s, (const float*)x, target,
+                           (long long)n, pos_weight, inv_n, partial, (float*)grad);
+    hipLaunchKernelGGL(k_bce_total, dim3(1), dim3(kWave), 0, s, partial, (int)nb, inv_n, loss);
+    return launch_status();
+}
+
+int lss_bce_logits_bwd(const void* grad, int32_t dtype, int64_t n, const float* grad_loss, void* dx, void* stream) {
+    const int esz = dtype == LSS_CONV_BF16 ? 2 : dtype == LSS_CONV_F32 ? 4 : 0;
+    if (!grad || !grad_loss || !dx || !esz || n <= 0 ||
+        ((reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(dx)) & 15))
+        return LSS_CONV_EINVAL;
+    const long long nb = (n + (long long)kBlock * kBceVpt - 1) / ((long long)kBlock * kBceVpt);
+    if (nb > INT_MAX) return LSS_CONV_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    if (esz == 2)
+        hipLaunchKernelGGL(k_bce_bwd<bf16>, dim3((unsigned)nb), dim3(kBlock), 0, s, (const bf16*)grad, (long long)n,
+                           grad_loss, (bf16*)dx);
+    else
+        hipLaunchKernelGGL(k_bce_bwd<float>, dim3((unsigned)nb), dim3(kBlock), 0, s, (const float*)grad, (long long)n,
+                           grad_loss, (float*)dx);
+    return launch_status();
+}
+
+int64_t lss_bce_iou_partial_bytes(int64_t n) {
+    return n <= 0 ? 0 : lss_bce_partials(n) * (int64_t)sizeof(BceIouPartial);
+}
+
+int lss_bce_iou_accum(const void* x, int32_t dtype, const float* target, int64_t per_sample, int32_t batch,
+                      const int32_t* n_valid, float pos_weight, double* totals, void* partial, void* stream) {
+    const int esz = dtype == LSS_CONV_BF16 ? 2 : dtype == LSS_CONV_F32 ? 4 : 0;
+    if (!x || !target || !totals || !partial || !esz || per_sample <= 0 || batch <= 0 ||
+        per_sample > LLONG_MAX / batch || (reinterpret_cast<uintptr_t>(partial) & 7) ||
+        (reinterpret_cast<uintptr_t>(totals) & 7))
+        return LSS_CONV_EINVAL;
+    const long long n = (long long)per_sample * batch;
+    const long long nb = (n + (long long)kBlock * kBceVpt - 1) / ((long long)kBlock * kBceVpt);
+    if (nb > INT_MAX) return LSS_CONV_EINVAL;
+    // 16-byte loads only from 16-byte aligned bases (a thread's first element is a multiple of 8)
+    const int vec = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(target)) & 15) == 0;
+    hipStream_t s = (hipStream_t)stream;
+    BceIouPartial* pp = (BceIouPartial*)partial;
+    if (esz == 2)
+        hipLaunchKernelGGL(k_bce_iou<bf16>, dim3((unsigned)nb), dim3(kBlock), 0, s, (const bf16*)x, target,
+                           (long long)per_sample, (int)batch, (const int*)n_valid, pos_weight, vec, pp);
+    else
+        hipLaunchKernelGGL(k_bce_iou<float>, dim3((unsigned)nb), dim3(kBlock), 0, s, (const float*)x, target,
+                           (long long)per_sample, (int)batch, (const int*)n_valid, pos_weight, vec, pp);
+    hipLaunchKernelGGL(k_bce_iou_fold, dim3(1), dim3(kBlock), 0, s, (const BceIouPartial*)pp, (int)nb,
+                       (double)per_sample, totals);
+    return launch_status();
+}
+
+int64_t lss_bce_partials(int64_t n) { return (n + (int64_t)kBlock * kBceVpt - 1) / ((int64_t)kBlock * kBceVpt); }
+
+int lss_bce_logits_pc(const void* x, int32_t dtype, const float* target, int64_t n, int64_t plane, int32_t K,
+                      const float* pos_weight, float* partial, float* loss, void* grad, void* stream) {
+    const int esz = dtype == LSS_CONV_BF16 ? 2 : dtype == LSS_CONV_F32 ? 4 : 0;
+    if (!x || !target || !pos_weight || !partial || !loss || !grad || !esz || n <= 0 || plane <= 0 || K <= 0 ||
+        ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(grad)) & 15) ||
+        (reinterpret_cast<uintptr_t>(target) & 15))
+        return LSS_CONV_EINVAL;
+    const long long nb = (n + (long long)kBlock * kBceVpt - 1) / ((long long)kBlock * kBceVpt);
+    if (nb > INT_MAX) return LSS_CONV_EINVAL;
+    const float inv_n = 1.0f / (float)n;
+    hipStream_t s = (hipStream_t)stream;
+    if (esz == 2)
+        hipLaunchKernelGGL(k_bce_fwd_pc<bf16>, dim3((unsigned)nb), dim3(kBlock), 0, s, (const bf16*)x, target,
+                           (long long)n, (long long)plane, (int)K, pos_weight, inv_n, partial, (bf16*)grad);
+    else
+        hipLaunchKernelGGL(k_bce_fwd_pc<float>, dim3((unsigned)nb), dim3(kBlock), 0, s, (const float*)x, target,
+                           (long long)n, (long long)plane, (int)K, pos_weight, inv_n, partial, (float*)grad);
+    hipLaunchKernelGGL(k_bce_total, dim3(1), dim3(kWave), 0, s, partial, (int)nb, inv_n, loss);
+    return launch_status();
+}
+
+int64_t lss_bce_iou_pc_partial_bytes(int64_t n, int32_t K) {
+    return n <= 0 || K <= 0 ? 0 : lss_bce_partials(n) * (int64_t)(sizeof(double) + 2 * (size_t)K * sizeof(int));
+}
+
+int lss_bce_iou_accum_pc(const void* x, int32_t dtype, const float* target, int64_t per_sample, int32_t batch,
+                         const int32_t* n_valid, int64_t plane, int32_t K, const float* pos_weight, double* totals,
+                         void* partial, void* stream) {
+    const int esz = dtype == LSS_CONV_BF16 ? 2 : dtype == LSS_CONV_F32 ? 4 : 0;
+    if (!x || !target || !pos_weight || !totals || !partial || !esz || per_sample <= 0 || batch <= 0 || plane <= 0 ||
+        K <= 0 || K > kIouMaxClasses || per_sample != plane * K || per_sample > LLONG_MAX / batch ||
+        (reinterpret_cast<uintptr_t>(partial) & 7) || (reinterpret_cast<uintptr_t>(totals) & 7))
+        return LSS_CONV_EINVAL;
+    const long long n = (long long)per_sample * batch;
+    const long long nb = (n + (long long)kBlock * kBceVpt - 1) / ((long long)kBlock * kBceVpt);
+    if (nb > INT_MAX) return LSS_CONV_EINVAL;
+    const int vec = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(target)) & 15) == 0;
+    hipStream_t s = (hipStream_t)stream;
+    double* pl = (double*)partial;
+    int* pc = (int*)(pl + nb);
+    if (esz == 2)
+        hipLaunchKernelGGL(k_bce_iou_pc<bf16>, dim3((unsigned)nb), dim3(kBlock), 0, s, (const bf16*)x, target,
+                           (long long)per_sample, (int)batch, (const int*)n_valid, (long long)plane, (int)K, pos_weight,
+                           vec, pl, pc);
+    else
+        hipLaunchKernelGGL(k_bce_iou_pc<float>, dim3((unsigned)nb), dim3(kBlock), 0, s, (const float*)x, target,
+                           (long long)per_sample, (int)batch, (const int*)n_valid, (long long)plane, (int)K, pos_weight,
+                           vec, pl, pc);
+    hipLaunchKernelGGL(k_bce_iou_fold_pc, dim3(1), dim3(kBlock), 0, s, (const double*)pl, (const int*)pc, (int)nb, (int)K,
+                       (double)per_sample, totals);
+    return launch_status();
+}
+
+}  // extern "C"

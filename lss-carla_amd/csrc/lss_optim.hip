@@ -18,13 +18,13 @@
 #include <stdint.h>
 
 #include "lss_convs.h"
+#include "lss_device.h"
 
 #pragma clang fp contract(fast)
 
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kWave = 64;
 constexpr int kMaxBlocks = 1024;       // norm-pass blocks (partials)
 constexpr int kMaxAdamBlocks = 16384;  // Adam-pass blocks
 
@@ -244,8 +244,7 @@ int clip_adam(int32_t count, float* const* params, const float* const* grads, fl
         hipLaunchKernelGGL(k_clip_adam<false>, dim3((unsigned)nb2), dim3(kBlock), 0, st, s, (const float*)partial,
                            (int)nb, max_norm, lr, beta1, beta2, eps, weight_decay);
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launch_status();
 }
 
 }  // namespace

@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "lss_convs.h"
+#include "lss_device.h"
 
 // The library is built with -ffp-contract=off for the geometry's reference op order (lss_hip.hip);
 // the conv-stack kernels here have no bit-exact contract, so they keep FMA contraction.
@@ -35,26 +36,10 @@ struct UpGeo {
     float rh, rw;  // (in - 1) / (out - 1) in fp32, as PyTorch's area_pixel_compute_scale (align_corners)
 };
 
-__device__ __forceinline__ void unpack8(u32x4 v, float f[8]) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        f[2 * k] = __uint_as_float(v[k] << 16);
-        f[2 * k + 1] = __uint_as_float(v[k] & 0xffff0000u);
-    }
-}
-
-// fp32 -> bf16 bits, round to nearest even (c10::BFloat16's rounding; NaN kept quiet)
-__device__ __forceinline__ unsigned bf16_bits(float x) {
-    unsigned u = __float_as_uint(x);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return u >> 16;
-}
-
 __device__ __forceinline__ u32x4 pack8(const float f[8]) {
     u32x4 v;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = bf16_bits(f[2 * k]) | (bf16_bits(f[2 * k + 1]) << 16);
+    for (int k = 0; k < 4; ++k) v[k] = bf16_bits_branch(f[2 * k]) | (bf16_bits_branch(f[2 * k + 1]) << 16);
     return v;
 }
 
@@ -260,19 +245,12 @@ __global__ __launch_bounds__(kBlock) void k_up_bwd_taps(const u32x4* __restrict_
     dx[t] = pack8(acc);
 }
 
-inline int launch_status() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
-}
-
 inline bool up_ok(int N, int Hi, int Wi, int C1, int C2, int Ho, int Wo) {
     // upsampling only (Ho >= Hi, Wo >= Wi), > 1 line on both sides (align_corners scale defined)
     return N > 0 && Hi > 1 && Wi > 1 && Ho >= Hi && Wo >= Wi && C1 > 0 && C1 % 8 == 0 && C2 >= 0 &&
            C2 % 8 == 0 && (long)N * Ho * Wo * (C1 + C2) / 8 < INT_MAX - kBlock &&
            (long)N * Hi * Wi * (C1 + C2) < INT_MAX;
 }
-
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 UpGeo make_geo(int N, int Hi, int Wi, int C1, int C2, int Ho, int Wo) {
     UpGeo g;

@@ -17,7 +17,7 @@
 // The per-image tails. The MLPs work on a few KB per image and were four launches of their own
 // (k_se_mlp1 / k_se_mlp2 / k_se_mlpb1 / k_se_mlpb2) at the ~5 us floor of a launch in the replayed
 // graph. They now ride in the reductions that feed them, with the hand-off of the depthwise
-// weight-gradient fold (dw_finish, lss_convs.hip) and of the batch-norm clusters (lss_bnorm.hip):
+// weight-gradient fold (dw_finish, lss_dwconv.hip) and of the batch-norm clusters (lss_bnorm.hip):
 //   * a block holds planes of ONE image (grid N x bpi, se_tail_grid); it publishes its m (or t) values with
 //     agent-scope write-through stores, every storing wave retires them (vmcnt(0)), the block meets at
 //     a barrier, and one lane draws a ticket on the image's counter (relaxed agent-scope fetch_add);
@@ -42,6 +42,7 @@
 #include <atomic>
 
 #include "lss_convs.h"
+#include "lss_device.h"
 
 // The library is built with -ffp-contract=off for the geometry's reference op order (lss_hip.hip);
 // the conv-stack kernels here have no bit-exact contract, so they keep FMA contraction.
@@ -54,40 +55,21 @@
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kWave = 64;
 constexpr int kMaxC = 2048;  // channels of the widest MBConv block: 1152
 
 __device__ __forceinline__ float bf(unsigned short b) { return __uint_as_float((unsigned)b << 16); }
-// fp32 -> bf16 bits, round to nearest even (NaN kept quiet). A select, not a branch: a branch per element
-// would put every load of an unrolled loop in a block of its own, each waited for before the next is issued.
-__device__ __forceinline__ unsigned short bfbits(float x) {
-    const unsigned u = __float_as_uint(x);
-    const unsigned nan = (u >> 16) | 0x40u, rne = (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-    return (unsigned short)((u & 0x7fffffffu) > 0x7f800000u ? nan : rne);
-}
-__device__ __forceinline__ float rbf(float x) { return bf(bfbits(x)); }  // round through bf16
-__device__ __forceinline__ float sigm(float z) { return 1.f / (1.f + __expf(-z)); }
+__device__ __forceinline__ float rbf(float x) { return bf(bf16_bits_select(x)); }  // round through bf16
 
 // Uses a loaded value where it stands. Without it the compiler sinks each load of an unrolled batch into the
 // branch that consumes it, and the batch becomes one memory round trip per element.
 __device__ __forceinline__ void pin(float& v) { asm volatile("" : "+v"(v)); }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-    return v;
-}
-
 // 4 consecutive bf16 (8 bytes) <-> fp32
-__device__ __forceinline__ void unpack4(uint2 u, float* o) {
-    o[0] = __uint_as_float(u.x << 16); o[1] = __uint_as_float(u.x & 0xffff0000u);
-    o[2] = __uint_as_float(u.y << 16); o[3] = __uint_as_float(u.y & 0xffff0000u);
-}
 __device__ __forceinline__ void ld4(const unsigned short* p, float* o) { unpack4(*reinterpret_cast<const uint2*>(p), o); }
 __device__ __forceinline__ void st4(unsigned short* p, const float* v) {
     uint2 u;
-    u.x = (unsigned)bfbits(v[0]) | ((unsigned)bfbits(v[1]) << 16);
-    u.y = (unsigned)bfbits(v[2]) | ((unsigned)bfbits(v[3]) << 16);
+    u.x = (unsigned)bf16_bits_select(v[0]) | ((unsigned)bf16_bits_select(v[1]) << 16);
+    u.y = (unsigned)bf16_bits_select(v[2]) | ((unsigned)bf16_bits_select(v[3]) << 16);
     *reinterpret_cast<uint2*>(p) = u;
 }
 
@@ -217,7 +199,7 @@ __device__ __forceinline__ void se_fc1_dots(const float* __restrict__ w1, const 
 __device__ __forceinline__ void se_fc1_finish(float a, float b1j, float& r, float& h) {
 #pragma clang fp contract(off)
     r = rbf(a + rbf(b1j));
-    h = rbf(r * sigm(r));
+    h = rbf(r * sigmoid(r));
 }
 
 // Expand conv, one thread per channel: wr = the channel's row of W2 (LDS, rounded to bf16), the sq
@@ -228,7 +210,7 @@ __device__ __forceinline__ float se_fc2(const float* wr, const float* s_h, int s
 #pragma unroll 4
     for (int j = 0; j < sq; ++j) e = fmaf(wr[j], s_h[j], e);
     e = rbf(e + rbf(b2c));
-    return rbf(sigm(e));
+    return rbf(sigmoid(e));
 }
 
 // de = t sig (1 - sig)
@@ -264,7 +246,7 @@ __device__ __forceinline__ float se_dh16(const float* __restrict__ w2, const flo
 // dr = dh swish'(r)
 __device__ __forceinline__ float se_dr(float dh, float rv) {
 #pragma clang fp contract(off)
-    const float s = sigm(rv);
+    const float s = sigmoid(rv);
     return dh * s * fmaf(rv, 1.f - s, 1.f);
 }
 
@@ -427,15 +409,6 @@ constexpr int kSeBankImages = LSS_SE_TAIL_MAX_IMAGES;
 
 // arrival counters, one word per image and bank; zero at load and between calls
 __device__ unsigned g_se_ctr[kSeBanks][kSeBankImages];
-
-// values handed from block to block inside a launch: write-through stores, L1-bypassing loads
-__device__ __forceinline__ void st_agent(float* p, float v) {
-    __hip_atomic_store(reinterpret_cast<unsigned*>(p), __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float ld_agent(const float* p) {
-    return __uint_as_float(
-        __hip_atomic_load(reinterpret_cast<const unsigned*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
 
 // Called by every thread of a block after its published stores. True, in every thread, in the block whose
 // ticket is the last of the `expected` of this counter; that block has re-zeroed the counter.
@@ -690,11 +663,6 @@ __global__ __launch_bounds__(kBlock) void k_se_wgrad(const float* __restrict__ d
     }
 }
 
-inline int launch_status() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
-}
-
 inline bool se_ok(int N, int C, int HW, int sq) {
     return N > 0 && C > 0 && C <= kMaxC && sq > 0 && sq <= kWave && HW > 0 && HW % 4 == 0 &&
            (long)N * C * HW < INT_MAX;
@@ -704,8 +672,6 @@ inline bool se_ok(int N, int C, int HW, int sq) {
 inline bool se_aligned(const void* a, const void* b, const void* c = nullptr) {
     return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 7) == 0;
 }
-
-inline int blocks(long n, int per) { return (int)((n + per - 1) / per); }
 
 std::atomic<int> g_se_tails{LSS_SE_TAILS_DEFAULT};
 std::atomic<unsigned> g_se_bank{0};
@@ -729,9 +695,9 @@ inline bool se_tails(int N, int C, int sq, int /*HW*/, bool backward) {
 // resident at once -- two per CU -- however many planes that gives a wave.
 constexpr int kTailSlots = 512;
 inline void se_tail_grid(int N, int C, int* bpi, int* cpb) {
-    const int want = std::min(blocks(C, kTailWaves), std::max(1, kTailSlots / N));
-    *cpb = blocks(blocks(C, want), kTailWaves) * kTailWaves;  // whole rounds of the 16 waves
-    *bpi = blocks(C, *cpb);
+    const int want = std::min(grid_blocks(C, kTailWaves), std::max(1, kTailSlots / N));
+    *cpb = grid_blocks(grid_blocks(C, want), kTailWaves) * kTailWaves;  // whole rounds of the 16 waves
+    *bpi = grid_blocks(C, *cpb);
 }
 inline int se_next_bank() { return (int)(g_se_bank.fetch_add(1u, std::memory_order_relaxed) % kSeBanks); }
 
@@ -753,13 +719,13 @@ int lss_se_fwd(const void* x, int32_t N, int32_t C, int32_t HW, const float* w1,
         hipLaunchKernelGGL(k_se_mean_tail, dim3(N * bpi), dim3(kTail), 0, s, (const unsigned short*)x, C, HW, bpi, cpb,
                            se_next_bank(), w1, b1, w2, b2, sq, m, r, h, sig);
     } else {
-        hipLaunchKernelGGL(k_se_mean, dim3(blocks(planes, kBlock / kWave)), dim3(kBlock), 0, s,
+        hipLaunchKernelGGL(k_se_mean, dim3(grid_blocks(planes, kBlock / kWave)), dim3(kBlock), 0, s,
                            (const unsigned short*)x, planes, HW, m);
         const int nchunk = (C + kMlpC - 1) / kMlpC;
         hipLaunchKernelGGL(k_se_mlp1, dim3(N * ((sq + 3) / 4)), dim3(kBlock), 0, s, m, w1, b1, C, sq, r, h);
         hipLaunchKernelGGL(k_se_mlp2, dim3(N * nchunk), dim3(kBlock), 0, s, h, w2, b2, C, sq, sig);
     }
-    hipLaunchKernelGGL(k_se_scale, dim3(blocks(n4, kBlock)), dim3(kBlock), 0, s, (const unsigned short*)x, sig, HW, n4,
+    hipLaunchKernelGGL(k_se_scale, dim3(grid_blocks(n4, kBlock)), dim3(kBlock), 0, s, (const unsigned short*)x, sig, HW, n4,
                        (unsigned short*)y);
     return launch_status();
 }
@@ -779,13 +745,13 @@ int lss_se_bwd(const void* dy, const void* x, int32_t N, int32_t C, int32_t HW, 
                            (const unsigned short*)x, C, HW, bpi, cpb, se_next_bank(), sig, r, w1, w2, sq, t, de, dr,
                            dm);
     } else {
-        hipLaunchKernelGGL(k_se_dot, dim3(blocks(planes, kBlock / kWave)), dim3(kBlock), 0, s,
+        hipLaunchKernelGGL(k_se_dot, dim3(grid_blocks(planes, kBlock / kWave)), dim3(kBlock), 0, s,
                            (const unsigned short*)dy, (const unsigned short*)x, planes, HW, t);
         const int nchunk = (C + kMlpbC - 1) / kMlpbC;
         hipLaunchKernelGGL(k_se_mlpb1, dim3(N * nchunk), dim3(kBlock), 0, s, t, sig, w2, C, sq, de, dh_part);
         hipLaunchKernelGGL(k_se_mlpb2, dim3(N * nchunk), dim3(kBlock), 0, s, dh_part, r, w1, C, sq, dr, dm);
     }
-    hipLaunchKernelGGL(k_se_dx, dim3(blocks(n4, kBlock)), dim3(kBlock), 0, s, (const unsigned short*)dy, sig, dm, HW,
+    hipLaunchKernelGGL(k_se_dx, dim3(grid_blocks(n4, kBlock)), dim3(kBlock), 0, s, (const unsigned short*)dy, sig, dm, HW,
                        n4, (unsigned short*)dx);
     return launch_status();
 }
@@ -796,7 +762,7 @@ int lss_se_wgrad(const float* de, const float* h, const float* dr, const float* 
         sq > kWave)
         return LSS_CONV_EINVAL;
     const int total = 2 * C * sq + sq + C;
-    hipLaunchKernelGGL(k_se_wgrad, dim3(blocks(total, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, de, h, dr, m, N,
+    hipLaunchKernelGGL(k_se_wgrad, dim3(grid_blocks(total, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, de, h, dr, m, N,
                        C, sq, dw1, db1, dw2, db2);
     return launch_status();
 }

@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "lss_simbev.h"
+#include "lss_device.h"
 
 namespace {
 
@@ -228,8 +229,7 @@ int lss_simbev_images(const uint8_t* src, int32_t n, int32_t src_h, int32_t src_
     const dim3 grid((unsigned)((out_h * out_w + kThreads - 1) / kThreads), (unsigned)n);
     hipLaunchKernelGGL(k_simbev_images, grid, dim3(kThreads), 0, (hipStream_t)stream, src, src_h, src_w, aug, tables,
                        out_h, out_w, out);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launch_status();
 }
 
 int lss_simbev_vehicle_mask(const uint8_t* bev, int32_t n, int32_t n_classes, int32_t X, int32_t Y, float* out,
@@ -238,8 +238,7 @@ int lss_simbev_vehicle_mask(const uint8_t* bev, int32_t n, int32_t n_classes, in
     const long total = (long)n * X * Y;
     hipLaunchKernelGGL(k_vehicle_mask, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0,
                        (hipStream_t)stream, bev, n_classes, X, Y, total, out);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launch_status();
 }
 
 int lss_simbev_class_masks(const uint8_t* bev, int32_t n, int32_t n_classes, int32_t X, int32_t Y,
@@ -258,8 +257,7 @@ int lss_simbev_class_masks(const uint8_t* bev, int32_t n, int32_t n_classes, int
     const long total = (long)n * X * Y;
     hipLaunchKernelGGL(k_class_masks, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0,
                        (hipStream_t)stream, bev, n_classes, X, Y, total, g, used, K, out);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launch_status();
 }
 
 }  // extern "C"

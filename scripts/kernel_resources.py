@@ -1,10 +1,19 @@
-"""Print VGPR/SGPR/LDS/occupancy/scratch per kernel of lss_hip.hip (hipcc -Rpass-analysis)."""
+"""Print VGPR/SGPR/LDS/occupancy/scratch per kernel of one csrc/*.hip file (hipcc -Rpass-analysis).
+
+python scripts/kernel_resources.py [NAME_SUBSTRING [SOURCE.hip] [extra hipcc flags...]]: SOURCE defaults to
+lss_hip.hip and is looked up in lss-carla_amd/csrc/ when it is not a path.
+"""
+import os
 import re
 import subprocess
 import sys
 
+flags = sys.argv[2:]
+src = flags.pop(0) if flags and flags[0].endswith(".hip") else "lss_hip.hip"
+if not os.path.exists(src):
+    src = os.path.join("lss-carla_amd", "csrc", src)
 cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-Iinclude", "-c",
-       "-o", "/tmp/_lss_res.o", "lss-carla_amd/csrc/lss_hip.hip", "-Rpass-analysis=kernel-resource-usage"] + sys.argv[2:]
+       "-o", "/tmp/_lss_res.o", src, "-Rpass-analysis=kernel-resource-usage"] + flags
 out = subprocess.run(cmd, capture_output=True, text=True).stderr
 cur, rows = None, []
 for line in out.splitlines():

@@ -47,6 +47,29 @@ def test_debug_library_loads_and_exports_all_symbols():
     assert dbg.lss_debug_status(None, 0) == -1  # NULL output rejected without touching a device
 
 
+def test_build_lists_every_source_and_watches_every_header(tmp_path, monkeypatch):
+    """A csrc file the build does not know fails here, not as a missing symbol at load time."""
+    import glob
+
+    from lss_carla_amd import build
+
+    csrc = os.path.join(os.path.dirname(build.__file__), "csrc")
+    assert sorted(build.SOURCES) == sorted(glob.glob(os.path.join(csrc, "*.hip")))
+    assert len(set(build.SOURCES)) == len(build.SOURCES)
+    headers = glob.glob(os.path.join(csrc, "*.h")) + glob.glob(os.path.join(REPO, "include", "*.h"))
+    assert headers and set(headers) <= set(build.HEADERS), set(headers) - set(build.HEADERS)
+    # up_to_date() really looks at each of them: a library older than any one source or header is stale
+    out = tmp_path / "lib.so"
+    out.write_bytes(b"")
+    newest = max(os.path.getmtime(f) for f in build.SOURCES + build.HEADERS + [build.__file__])
+    os.utime(out, (newest + 1, newest + 1))
+    assert build.up_to_date(str(out))
+    real = os.path.getmtime
+    for f in build.SOURCES + build.HEADERS:
+        monkeypatch.setattr(os.path, "getmtime", lambda p, f=f: newest + 2 if p == f else real(p))
+        assert not build.up_to_date(str(out)), f
+
+
 def test_gridspec_matches_reference_quantiser_constants():
     gs = ops.GridSpec.from_conf(syn.grid_conf())
     dx, bx, nx = ref.gen_dx_bx([-50.0, 50.0, 0.5], [-50.0, 50.0, 0.5], [-10.0, 10.0, 20.0])

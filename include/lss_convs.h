@@ -33,6 +33,31 @@ enum { LSS_CONV_NCHW = 0, LSS_CONV_NHWC = 1 };
 enum { LSS_ACT_NONE = 0, LSS_ACT_RELU = 1, LSS_ACT_SWISH = 2 };
 enum { LSS_CONV_EINVAL = -1 };
 
+/* Which kernel a depthwise pass launches (ABI 27; host only: no HIP call, no allocation -- the launchers
+ * switch on the same rule). pass: the entry point; the other arguments as that entry point's (ngroups is
+ * read for LSS_DW_BWD_WEIGHT only). The rule depends on the shape alone: every lss_dwconv_* entry point
+ * already refuses pointers that are not 16-B aligned. Families:
+ *   LSS_DW_LDS_SEG    LDS-staged, segment map: forward (and stride-1 backward-data) of every (K, stride) but (3, 1)
+ *   LSS_DW_LDS_TILE   LDS-staged, tile map: forward / stride-1 backward-data of (3, 1); every weight gradient
+ *     both where Wo % 4 == 0 and the output reaches the whole padded input, (Wo - 1) stride + K >= pad_left + Wi
+ *     (rows alike); seg = 8 (Wo % 8 == 0) or 4 outputs per vector store; banded = 1 when a plane's staged rows
+ *     pass the LDS budget and it is cut into bands of rows (then pb = 1), else pb = planes per block
+ *   LSS_DW_PLANES22 / LSS_DW_PLANES11  whole narrow planes (Wo = 22 / 11) through LDS, pb planes per block:
+ *     forward with stride 1, every weight gradient, within the LDS budget
+ *   LSS_DW_REG        the register-tiled kernels: everything else (seg = banded = pb = 0)
+ *   LSS_DW_S2_PAR0..3 stride-2 backward-data, index 2 (pad_top & 1) + (pad_left & 1)
+ * Stride-1 backward-data is the forward on (Ho, Wo) -> (Hi, Wi) with paddings K - 1 - pad: the forward
+ * families, chosen for that mirrored shape. Returns 0, or LSS_CONV_EINVAL as the entry point would. */
+enum { LSS_DW_FWD = 0, LSS_DW_BWD_DATA = 1, LSS_DW_BWD_WEIGHT = 2 };
+enum { LSS_DW_LDS_SEG = 0, LSS_DW_LDS_TILE = 1, LSS_DW_PLANES22 = 2, LSS_DW_PLANES11 = 3, LSS_DW_REG = 4,
+       LSS_DW_S2_PAR0 = 5, LSS_DW_S2_PAR1 = 6, LSS_DW_S2_PAR2 = 7, LSS_DW_S2_PAR3 = 8, LSS_DW_FAMILIES = 9 };
+typedef struct lss_dw_arm {
+    int32_t family, seg, banded, pb;
+} lss_dw_arm_t;
+int lss_dwconv_arm(int32_t pass, int32_t dtype, int32_t N, int32_t C, int32_t Hi, int32_t Wi, int32_t K,
+                   int32_t stride, int32_t pad_top, int32_t pad_left, int32_t Ho, int32_t Wo, int32_t ngroups,
+                   lss_dw_arm_t* arm);
+
 /* y (N, C, Ho, Wo) = depthwise_conv(x (N, C, Hi, Wi), w) */
 int lss_dwconv_fwd(const void* x, int32_t dtype, const float* w, int32_t N, int32_t C, int32_t Hi, int32_t Wi,
                    int32_t K, int32_t stride, int32_t pad_top, int32_t pad_left, int32_t Ho, int32_t Wo, void* y,

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define LSS_ABI_VERSION 26
+#define LSS_ABI_VERSION 27
 
 typedef struct lss_dims {
     int32_t B, N, D, H, W, C;
@@ -167,6 +167,12 @@ int lss_csr_build_ordered(const int32_t* cell_of, const int32_t* rank_of, int32_
 int lss_lift_prep(const void* depthnet_out, int32_t in_dtype, const lss_dims_t* dims,
                   float* depth, void* ctx_t, int32_t ctx_dtype, lss_stream_t stream);
 
+/* Which k_lift_prep instantiation lss_lift_prep launches for dims (host only: no HIP call; the launcher
+ * switches on this value): the depth bins per wave part, 16 (D <= 64), 32 (D <= 128) or 64 (D <= 256);
+ * LSS_EINVAL for bad dims, LSS_EUNSUPPORTED for D > 256. The in / ctx element types pick the template's
+ * types and change nothing else. */
+int lss_lift_prep_arm(const lss_dims_t* dims);
+
 /* Depthnet + lift, part 1, fused (CamEncode.depthnet 1x1 conv + get_depth_dist + layout,
  * src/models.py:47, 55-59, 192-202): logits = weight . feat + bias on MFMA (bf16 in, fp32
  * accumulate, rounded to bf16 like the autocast conv output), depth (B*N, D, H, W) fp32 = softmax
@@ -241,6 +247,21 @@ int lss_splat_bwd(const void* g, int32_t g_dtype, int32_t rows_layout, const int
                   const float* depth, const void* ctx_t, int32_t ctx_dtype, const lss_dims_t* dims,
                   const lss_grid_t* grid, void* d_depthnet_out, int32_t d_dtype,
                   lss_stream_t stream);
+
+/* Which kernel lss_splat_bwd launches for gradient rows of g_dtype and dims (host only: no HIP call;
+ * the launcher switches on this value). A pixel tile needs whole tiles (B*N*H*W % px == 0), px <= H*W,
+ * H*W % 4 == 0 and, for 8 pixels, H*W % 8 == 0:
+ *   LSS_BWD_TILE4   the 4-pixel tile: bf16 rows, D <= 48
+ *   LSS_BWD_TILE48  the 8-pixel tile, up to 48 depth bins
+ *   LSS_BWD_TILE64  the 8-pixel tile, 49..64 depth bins
+ *   LSS_BWD_REG1 / REG2 / REG4  one wave per pixel, 1 / 2 / 4 chunks of 64 bins (D <= 64 / 128 / 256)
+ * fp32 rows never take LSS_BWD_TILE4, and bf16 rows never LSS_BWD_TILE48 (where the 8-pixel tile fits,
+ * so does the 4-pixel one): five arms per row type. The output, context and layout arguments pick the template's types
+ * and change nothing else. Negative: the error lss_splat_bwd returns for these arguments (LSS_EINVAL for
+ * bad dims or g_dtype, LSS_EUNSUPPORTED for D > 256). */
+enum { LSS_BWD_TILE4 = 0, LSS_BWD_TILE48 = 1, LSS_BWD_TILE64 = 2, LSS_BWD_REG1 = 3, LSS_BWD_REG2 = 4,
+       LSS_BWD_REG4 = 5, LSS_BWD_ARMS = 6 };
+int lss_splat_bwd_arm(int32_t g_dtype, const lss_dims_t* dims);
 
 /* Lifted-mode backward: dx[p, c] = g_row(cell_of[p])[c], 0 for dropped points (Nprime, C) fp32. */
 int lss_splat_bwd_lifted(const void* g, int32_t g_dtype, int32_t rows_layout, const int32_t* cell_of,

@@ -18,7 +18,7 @@ DEBUG_LIB_PATH = os.path.join(_HERE, "liblss_hip_debug.so")  # LSS_DEBUG=1: devi
 
 F32, BF16 = 0, 1
 NCHW, NHWC = 0, 1
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 
 class Dims(ctypes.Structure):
@@ -32,6 +32,12 @@ class ImgAug(ctypes.Structure):
                 ("rs_h", ctypes.c_int32), ("crop", ctypes.c_int32 * 4), ("flip", ctypes.c_int32),
                 ("rot_mode", ctypes.c_int32), ("affine", ctypes.c_int32 * 6), ("h_off", ctypes.c_int32),
                 ("h_ksize", ctypes.c_int32), ("v_off", ctypes.c_int32), ("v_ksize", ctypes.c_int32)]
+
+
+class DwArm(ctypes.Structure):
+    """lss_dw_arm_t of include/lss_convs.h: the kernel lss_dwconv_arm reports for a depthwise pass."""
+    _fields_ = [("family", ctypes.c_int32), ("seg", ctypes.c_int32), ("banded", ctypes.c_int32),
+                ("pb", ctypes.c_int32)]
 
 
 class Grid(ctypes.Structure):
@@ -66,6 +72,7 @@ SIGNATURES = {
     "lss_cells_from_geom_ordered": (ctypes.c_int, [_p, _i32, _i32, _GRID, _p, _p, _p, _p, _p, _p]),
     "lss_csr_build_ordered": (ctypes.c_int, [_p, _p, _i32, _p, _i32, _DIMS, _p, _p, _p, _p, _p, _p]),
     "lss_lift_prep": (ctypes.c_int, [_p, _i32, _DIMS, _p, _p, _i32, _p]),
+    "lss_lift_prep_arm": (ctypes.c_int, [_DIMS]),
     "lss_depthnet_lift": (ctypes.c_int, [_p, _p, _p, _i32, _i32, _DIMS, _p, _p, _i32, _p]),
     "lss_depthnet_lift_nhwc": (ctypes.c_int, [_p, _p, _p, _i32, _i32, _DIMS, _p, _p, _i32, _p]),
     "lss_depthnet_pack": (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _p, _p, _p, _p]),
@@ -74,6 +81,7 @@ SIGNATURES = {
     "lss_splat_fwd": (ctypes.c_int, [_p, _p, _i32, _p, _p, _p, _p, _DIMS, _GRID, _p, _i32, _i32, _p, _p, _p]),
     "lss_bev_rows": (ctypes.c_int, [_p, _i32, _p, _DIMS, _GRID, _p, _p]),
     "lss_splat_bwd": (ctypes.c_int, [_p, _i32, _i32, _p, _p, _p, _i32, _DIMS, _GRID, _p, _i32, _p]),
+    "lss_splat_bwd_arm": (ctypes.c_int, [_i32, _DIMS]),
     "lss_splat_bwd_lifted": (ctypes.c_int, [_p, _i32, _i32, _p, _i32, _DIMS, _GRID, _p, _p]),
     "lss_segment_scratch_bytes": (ctypes.c_size_t, [_i32]),
     "lss_segment_build": (ctypes.c_int, [_p, _i32, _p, _p, _p, _p, _p]),
@@ -86,6 +94,7 @@ SIGNATURES = {
     "lss_simbev_vehicle_mask": (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _p, _p]),
     "lss_simbev_class_masks": (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _p, _i32, _p, _p]),
     # include/lss_convs.h (conv-stack kernels, same library)
+    "lss_dwconv_arm": (ctypes.c_int, [_i32] * 13 + [ctypes.POINTER(DwArm)]),
     "lss_dwconv_fwd": (ctypes.c_int, [_p, _i32, _p] + [_i32] * 10 + [_p, _p]),
     "lss_dwconv_bwd_data": (ctypes.c_int, [_p, _i32, _p] + [_i32] * 10 + [_p, _p]),
     "lss_dwconv_bwd_weight": (ctypes.c_int, [_p, _p, _i32] + [_i32] * 11 + [_p, _p]),

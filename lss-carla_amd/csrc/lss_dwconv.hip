@@ -674,8 +674,7 @@ __global__ __launch_bounds__(kBlock) void k_dw_wgt_lds(const T* __restrict__ x, 
 
 // bands and planes per block for the LDS kernels: the whole plane when it fits, several planes per
 // block while the block has fewer than ~2 output segments per thread
-template <int K, int S>
-inline DwBand dw_band(const DwGeo& g, int seg, int max_planes, bool tile) {
+inline DwBand dw_band(int K, int S, const DwGeo& g, int seg, int max_planes, bool tile) {
     DwBand b;
     // row stride: the data at kDwCol, every compute read of the last (possibly partial) segment inside
     // the row; LW = 2 (mod 4): rows 8-B aligned for the staging writes, and consecutive rows start 2
@@ -699,21 +698,19 @@ inline DwBand dw_band(const DwGeo& g, int seg, int max_planes, bool tile) {
     return b;
 }
 
-// the LDS kernels' vector accesses need 16-B aligned tensors; the staged row holds the whole input row
+// the LDS kernels' vector accesses need 16-B aligned tensors (every lss_dwconv_* entry point refuses others,
+// so the rule itself depends on the shape only); the staged row holds the whole input row
 // (the right padding is not negative); and they run only where an output row splits into segments of
 // 4 or 8 (Wo % 4 == 0): on the trunk's narrow planes (Wo = 22, 11) the register-tiled kernels are
 // faster (c3 step, per layer: 15-55 vs 21-98 us), on the wide ones the LDS kernels (23-74 vs 50-181 us)
-template <int K, int S>
-inline bool dw_lds_ok(const DwGeo& g, const void* a, const void* b) {
-    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0 && g.Wo % 4 == 0 &&
-           (g.Wo - 1) * S + K >= g.pl + g.Wi && (g.Ho - 1) * S + K >= g.pt + g.Hi;
+inline bool dw_lds_ok(int K, int S, const DwGeo& g) {
+    return g.Wo % 4 == 0 && (g.Wo - 1) * S + K >= g.pl + g.Wi && (g.Ho - 1) * S + K >= g.pt + g.Hi;
 }
 
 inline int dw_seg(int Wo) { return Wo % 8 == 0 ? 8 : Wo % 4 == 0 ? 4 : Wo % 2 == 0 ? 2 : 1; }
 
 // the round-5 band for the segment kernel: LDS rows of exactly (Wo - 1) S + K floats
-template <int K, int S>
-inline DwBand dw_band_seg(const DwGeo& g, int seg, int max_planes) {
+inline DwBand dw_band_seg(int K, int S, const DwGeo& g, int seg, int max_planes) {
     DwBand b;
     b.LW = (g.Wo - 1) * S + K;
     const int full = (g.Ho - 1) * S + K;
@@ -733,10 +730,8 @@ inline DwBand dw_band_seg(const DwGeo& g, int seg, int max_planes) {
 }
 
 template <int K, int S, typename T>
-int dw_fwd_lds(const void* x, const float* w, DwGeo g, int flip, void* y, hipStream_t s) {
-    const int seg = dw_seg(g.Wo);
+int dw_fwd_lds(const void* x, const float* w, DwGeo g, int flip, void* y, int seg, const DwBand& b, hipStream_t s) {
     if constexpr (!dw_tile_map(K, S, true)) {
-        const DwBand b = dw_band_seg<K, S>(g, seg, g.nplanes);
         const long blocks = (long)b.nbands * ((g.nplanes + b.PB - 1) / b.PB);
         // slack past the staged rows: the last segment of a row reads up to (SEG - 1) * S columns past Wo
         const size_t lds = sizeof(float) * ((size_t)b.PB * K * K + (size_t)b.PB * b.LHmax * b.LW + 8 * S + K);
@@ -752,7 +747,6 @@ int dw_fwd_lds(const void* x, const float* w, DwGeo g, int flip, void* y, hipStr
 #undef LSS_DW_FWD_SEG
         return launch_status();
     }
-    const DwBand b = dw_band<K, S>(g, seg, g.nplanes, dw_tile_map(K, S, true));
     const long blocks = (long)b.nbands * ((g.nplanes + b.PB - 1) / b.PB);
     const size_t lds = sizeof(float) * ((size_t)b.PB * b.LHmax * b.LW + (size_t)b.PB * K * K);
     if (blocks > INT_MAX) return LSS_CONV_EINVAL;
@@ -769,10 +763,8 @@ int dw_fwd_lds(const void* x, const float* w, DwGeo g, int flip, void* y, hipStr
 }
 
 template <int K, int S, typename T>
-int dw_wgt_lds(const void* x, const void* dy, DwGeo g, int nimg, int ngroups, float* partial, DwFold fold,
-               hipStream_t s) {
-    const int seg = dw_seg(g.Wo);
-    const DwBand b = dw_band<K, S>(g, seg, (nimg + ngroups - 1) / ngroups, dw_tile_map(K, S, false));
+int dw_wgt_lds(const void* x, const void* dy, DwGeo g, int nimg, int ngroups, float* partial, DwFold fold, int seg,
+               const DwBand& b, hipStream_t s) {
     const size_t lds = sizeof(float) * ((size_t)b.PB * b.LHmax * b.LW);
 #define LSS_DW_WGT(SG) hipLaunchKernelGGL((k_dw_wgt_lds<K, S, SG, T>), dim3(g.C * ngroups), dim3(kBlock), lds, s, \
                                           (const T*)x, (const T*)dy, g, nimg, ngroups, b, partial, fold)
@@ -1011,55 +1003,82 @@ constexpr int kDwPlanesLdsMax = 48 * 1024;  // bytes of LDS a planes block may u
 
 // the planes kernels take Wo in {22, 11} (the trunk's narrow maps), a staged plane holding every input
 // element a tap reaches; PB = planes per block: one output row per thread, within the LDS budget
-template <int K, int S, int WO>
-inline int dw_planes_pb(const DwGeo& g, int extra_floats_per_plane, int elt) {
-    if (!LSS_DW_PLANES || g.Wo != WO) return 0;
-    using PG = PlaneGeo<K, S, WO>;
-    const int plane_bytes = 4 * (PG::LH(g.Ho) * PG::LW + extra_floats_per_plane) + elt * g.Ho * WO;
+inline int dw_planes_pb(int K, int S, const DwGeo& g, int extra_floats_per_plane, int elt) {
+    if (!LSS_DW_PLANES || (g.Wo != 22 && g.Wo != 11)) return 0;
+    const int WO = g.Wo, LW = (WO - 1) * S + K, LH = (g.Ho - 1) * S + K;  // PlaneGeo<K, S, WO>
+    const int plane_bytes = 4 * (LH * LW + extra_floats_per_plane) + elt * g.Ho * WO;
     int pb = std::max(1, kBlock / g.Ho);
     while (pb > 1 && pb * plane_bytes + 4 * pb * K * K + 64 > kDwPlanesLdsMax) --pb;
     return pb * plane_bytes + 4 * pb * K * K + 64 <= kDwPlanesLdsMax ? pb : 0;
 }
 
-template <int K, int S, typename T>
-int dw_fwd_planes(const void* x, const float* w, DwGeo g, int flip, void* y, hipStream_t s) {
-    // (stride 2: slower than the register-tiled kernel, 21.9 / 21.0 vs 15.3 / 19.1 us in the c3 step)
-    if (S != 1) return 1;
-    auto go = [&](auto wo_tag) -> int {
-        constexpr int WO = decltype(wo_tag)::value;
-        const int pb = dw_planes_pb<K, S, WO>(g, 0, (int)sizeof(T));
-        if (pb == 0) return 1;
-        using PG = PlaneGeo<K, S, WO>;
-        const size_t lds = 4 * ((((size_t)pb * K * K + 3) & ~(size_t)3) +
-                                (((size_t)pb * PG::LH(g.Ho) * PG::LW + 3) & ~(size_t)3)) +
-                           sizeof(T) * (size_t)pb * g.Ho * WO;
-        const long blocks = ((long)g.nplanes + pb - 1) / pb;
-        if (blocks > INT_MAX) return 1;
-        hipLaunchKernelGGL((k_dw_fwd_planes<K, S, WO, T>), dim3((unsigned)blocks), dim3(kBlock), lds, s, (const T*)x,
-                           w, g, flip, pb, (T*)y);
-        return 0;
-    };
-    if (g.Wo == 22) return go(std::integral_constant<int, 22>{});
-    if (g.Wo == 11) return go(std::integral_constant<int, 11>{});
-    return 1;
+template <int K, int S, int WO, typename T>
+int dw_fwd_planes(const void* x, const float* w, DwGeo g, int flip, void* y, int pb, hipStream_t s) {
+    using PG = PlaneGeo<K, S, WO>;
+    const size_t lds = 4 * ((((size_t)pb * K * K + 3) & ~(size_t)3) +
+                            (((size_t)pb * PG::LH(g.Ho) * PG::LW + 3) & ~(size_t)3)) +
+                       sizeof(T) * (size_t)pb * g.Ho * WO;
+    const long blocks = ((long)g.nplanes + pb - 1) / pb;  // (<= nplanes < 2^31)
+    hipLaunchKernelGGL((k_dw_fwd_planes<K, S, WO, T>), dim3((unsigned)blocks), dim3(kBlock), lds, s, (const T*)x, w, g,
+                       flip, pb, (T*)y);
+    return launch_status();
 }
 
-template <int K, int S, typename T>
-int dw_wgt_planes(const void* x, const void* dy, DwGeo g, int nimg, int ngroups, float* partial, DwFold fold,
+template <int K, int S, int WO, typename T>
+int dw_wgt_planes(const void* x, const void* dy, DwGeo g, int nimg, int ngroups, float* partial, DwFold fold, int pb,
                   hipStream_t s) {
-    auto go = [&](auto wo_tag) -> int {
-        constexpr int WO = decltype(wo_tag)::value;
-        const int pb = dw_planes_pb<K, S, WO>(g, g.Ho * WO, 0);
-        if (pb == 0) return 1;
-        using PG = PlaneGeo<K, S, WO>;
-        const size_t lds = 4 * (size_t)pb * (PG::LH(g.Ho) * PG::LW + g.Ho * WO);
-        hipLaunchKernelGGL((k_dw_wgt_planes<K, S, WO, T>), dim3(g.C * ngroups), dim3(kBlock), lds, s, (const T*)x,
-                           (const T*)dy, g, nimg, ngroups, pb, partial, fold);
-        return 0;
-    };
-    if (g.Wo == 22) return go(std::integral_constant<int, 22>{});
-    if (g.Wo == 11) return go(std::integral_constant<int, 11>{});
-    return 1;
+    using PG = PlaneGeo<K, S, WO>;
+    const size_t lds = 4 * (size_t)pb * (PG::LH(g.Ho) * PG::LW + g.Ho * WO);
+    hipLaunchKernelGGL((k_dw_wgt_planes<K, S, WO, T>), dim3(g.C * ngroups), dim3(kBlock), lds, s, (const T*)x,
+                       (const T*)dy, g, nimg, ngroups, pb, partial, fold);
+    return launch_status();
+}
+
+// ---- THE selection rule of the three passes: lss_dwconv_arm reports it, the launchers below switch on it.
+// Forward and weight gradient: the LDS kernels where dw_lds_ok (the segment map for the forward of every
+// (K, S) but (3, 1), the tile map otherwise), else the planes kernels (Wo 22 / 11 within the LDS budget;
+// forward: stride 1 only -- stride 2 is slower than the register-tiled kernel, 21.9 / 21.0 vs 15.3 / 19.1 us
+// in the c3 step), else the register-tiled kernels. Backward-data: stride 1 is the forward correlation with
+// the kernel flipped and the padding mirrored (g and flip below); stride 2 has one kernel per parity of the
+// paddings.
+struct DwArm {
+    int family, seg, banded, pb;
+    DwBand band;  // the LDS families' bands
+    DwGeo g;      // the geometry the kernel runs on (mirrored for stride-1 backward-data)
+    int flip;
+};
+
+inline DwArm dw_arm(int pass, int K, int S, int elt, const DwGeo& g0, int nimg, int ngroups) {
+    DwArm a{};
+    a.g = g0;
+    if (pass == LSS_DW_BWD_DATA) {
+        if (S == 2) {
+            a.family = LSS_DW_S2_PAR0 + (((g0.pt & 1) << 1) | (g0.pl & 1));
+            return a;
+        }
+        a.g = DwGeo{g0.C, g0.Ho, g0.Wo, g0.Hi, g0.Wi, K - 1 - g0.pt, K - 1 - g0.pl, g0.nplanes};
+        a.flip = 1;
+    }
+    const DwGeo& g = a.g;
+    const bool wgt = pass == LSS_DW_BWD_WEIGHT;
+    if (LSS_DW_LDS && dw_lds_ok(K, S, g)) {
+        const bool tile = dw_tile_map(K, S, !wgt);
+        a.family = tile ? LSS_DW_LDS_TILE : LSS_DW_LDS_SEG;
+        a.seg = dw_seg(g.Wo);
+        a.band = tile ? dw_band(K, S, g, a.seg, wgt ? (nimg + ngroups - 1) / ngroups : g.nplanes, true)
+                      : dw_band_seg(K, S, g, a.seg, g.nplanes);
+        a.banded = a.band.nbands > 1;
+        a.pb = a.band.PB;
+        return a;
+    }
+    const int pb = wgt ? dw_planes_pb(K, S, g, g.Ho * g.Wo, 0) : S == 1 ? dw_planes_pb(K, S, g, 0, elt) : 0;
+    if (pb > 0) {
+        a.family = g.Wo == 22 ? LSS_DW_PLANES22 : LSS_DW_PLANES11;
+        a.pb = pb;
+        return a;
+    }
+    a.family = LSS_DW_REG;
+    return a;
 }
 
 // dispatch over (K, S, T)
@@ -1079,32 +1098,43 @@ int dispatch_kst(int K, int S, int dtype, A... a) {
     return LSS_CONV_EINVAL;
 }
 
+// the forward kernels on arm a (the forward itself, or stride-1 backward-data re-entering it)
+template <int K, int S, typename T>
+int dw_fwd_run(const void* x, const float* w, const DwArm& a, void* y, hipStream_t s) {
+    const DwGeo& g = a.g;
+    switch (a.family) {
+        case LSS_DW_LDS_SEG:
+        case LSS_DW_LDS_TILE: return dw_fwd_lds<K, S, T>(x, w, g, a.flip, y, a.seg, a.band, s);
+        case LSS_DW_PLANES22: return dw_fwd_planes<K, S, 22, T>(x, w, g, a.flip, y, a.pb, s);
+        case LSS_DW_PLANES11: return dw_fwd_planes<K, S, 11, T>(x, w, g, a.flip, y, a.pb, s);
+        default: break;
+    }
+    constexpr int TH = Tile<S>::TH, TW = Tile<S>::TW;
+    const long n = (long)g.nplanes * ((g.Ho + TH - 1) / TH) * ((g.Wo + TW - 1) / TW);
+    hipLaunchKernelGGL((k_dw_fwd<K, S, TH, TW, T>), dim3(grid_blocks(n, kBlock)), dim3(kBlock), 0, s, (const T*)x, w, g,
+                       a.flip, (T*)y);
+    return launch_status();
+}
+
 template <int K, int S, typename T>
 struct Fwd {
-    static int run(const void* x, const float* w, DwGeo g, int flip, void* y, hipStream_t s) {
-        if (LSS_DW_LDS && dw_lds_ok<K, S>(g, x, y)) return dw_fwd_lds<K, S, T>(x, w, g, flip, y, s);
-        if (dw_fwd_planes<K, S, T>(x, w, g, flip, y, s) == 0) return launch_status();
-        constexpr int TH = Tile<S>::TH, TW = Tile<S>::TW;
-        const long n = (long)g.nplanes * ((g.Ho + TH - 1) / TH) * ((g.Wo + TW - 1) / TW);
-        hipLaunchKernelGGL((k_dw_fwd<K, S, TH, TW, T>), dim3(grid_blocks(n, kBlock)), dim3(kBlock), 0, s, (const T*)x, w, g,
-                           flip, (T*)y);
-        return launch_status();
+    static int run(const void* x, const float* w, DwGeo g, void* y, hipStream_t s) {
+        return dw_fwd_run<K, S, T>(x, w, dw_arm(LSS_DW_FWD, K, S, (int)sizeof(T), g, 0, 1), y, s);
     }
 };
 
 template <int K, int S, typename T>
 struct BwdData {
     static int run(const void* dy, const float* w, DwGeo g, void* dx, hipStream_t s) {
-        if (S == 1) {  // the forward correlation with the kernel flipped, padding mirrored
-            DwGeo t{g.C, g.Ho, g.Wo, g.Hi, g.Wi, K - 1 - g.pt, K - 1 - g.pl, g.nplanes};
-            return Fwd<K, 1, T>::run(dy, w, t, 1, dx, s);
-        }
+        const DwArm a = dw_arm(LSS_DW_BWD_DATA, K, S, (int)sizeof(T), g, 0, 1);
         const dim3 gr(grid_blocks((long)g.nplanes * ((g.Hi + 1) / 2) * ((g.Wi + 3) / 4), kBlock)), bl(kBlock);
-        const int par = ((g.pt & 1) << 1) | (g.pl & 1);
-        if (par == 0) hipLaunchKernelGGL((k_dw_bwd_data_s2<K, 0, 0, T>), gr, bl, 0, s, (const T*)dy, w, g, (T*)dx);
-        else if (par == 1) hipLaunchKernelGGL((k_dw_bwd_data_s2<K, 0, 1, T>), gr, bl, 0, s, (const T*)dy, w, g, (T*)dx);
-        else if (par == 2) hipLaunchKernelGGL((k_dw_bwd_data_s2<K, 1, 0, T>), gr, bl, 0, s, (const T*)dy, w, g, (T*)dx);
-        else hipLaunchKernelGGL((k_dw_bwd_data_s2<K, 1, 1, T>), gr, bl, 0, s, (const T*)dy, w, g, (T*)dx);
+        switch (a.family) {
+            case LSS_DW_S2_PAR0: hipLaunchKernelGGL((k_dw_bwd_data_s2<K, 0, 0, T>), gr, bl, 0, s, (const T*)dy, w, g, (T*)dx); break;
+            case LSS_DW_S2_PAR1: hipLaunchKernelGGL((k_dw_bwd_data_s2<K, 0, 1, T>), gr, bl, 0, s, (const T*)dy, w, g, (T*)dx); break;
+            case LSS_DW_S2_PAR2: hipLaunchKernelGGL((k_dw_bwd_data_s2<K, 1, 0, T>), gr, bl, 0, s, (const T*)dy, w, g, (T*)dx); break;
+            case LSS_DW_S2_PAR3: hipLaunchKernelGGL((k_dw_bwd_data_s2<K, 1, 1, T>), gr, bl, 0, s, (const T*)dy, w, g, (T*)dx); break;
+            default: return dw_fwd_run<K, 1, T>(dy, w, a, dx, s);  // stride 1 (the rule gives stride 2 a parity)
+        }
         return launch_status();
     }
 };
@@ -1113,9 +1143,13 @@ template <int K, int S, typename T>
 struct BwdWeight {
     static int run(const void* x, const void* dy, DwGeo g, int nimg, int ngroups, float* partial, DwFold fold,
                    hipStream_t s) {
-        if (LSS_DW_LDS && dw_lds_ok<K, S>(g, x, dy))
-            return dw_wgt_lds<K, S, T>(x, dy, g, nimg, ngroups, partial, fold, s);
-        if (dw_wgt_planes<K, S, T>(x, dy, g, nimg, ngroups, partial, fold, s) == 0) return launch_status();
+        const DwArm a = dw_arm(LSS_DW_BWD_WEIGHT, K, S, (int)sizeof(T), g, nimg, ngroups);
+        switch (a.family) {
+            case LSS_DW_LDS_TILE: return dw_wgt_lds<K, S, T>(x, dy, g, nimg, ngroups, partial, fold, a.seg, a.band, s);
+            case LSS_DW_PLANES22: return dw_wgt_planes<K, S, 22, T>(x, dy, g, nimg, ngroups, partial, fold, a.pb, s);
+            case LSS_DW_PLANES11: return dw_wgt_planes<K, S, 11, T>(x, dy, g, nimg, ngroups, partial, fold, a.pb, s);
+            default: break;
+        }
         hipLaunchKernelGGL((k_dw_bwd_weight<K, S, 4, S == 1 ? 4 : 2, T>), dim3(g.C * ngroups), dim3(kBlock), 0, s,
                            (const T*)x, (const T*)dy, g, nimg, ngroups, partial, fold);
         return launch_status();
@@ -1126,12 +1160,27 @@ struct BwdWeight {
 
 extern "C" {
 
+int lss_dwconv_arm(int32_t pass, int32_t dtype, int32_t N, int32_t C, int32_t Hi, int32_t Wi, int32_t K, int32_t stride,
+                   int32_t pad_top, int32_t pad_left, int32_t Ho, int32_t Wo, int32_t ngroups, lss_dw_arm_t* arm) {
+    if (!arm || pass < LSS_DW_FWD || pass > LSS_DW_BWD_WEIGHT || (dtype != LSS_CONV_F32 && dtype != LSS_CONV_BF16) ||
+        !geo_ok(N, C, Hi, Wi, K, stride, Ho, Wo))
+        return LSS_CONV_EINVAL;
+    if (pass == LSS_DW_BWD_WEIGHT && (ngroups <= 0 || ngroups > N)) return LSS_CONV_EINVAL;
+    const DwGeo g{C, Hi, Wi, Ho, Wo, pad_top, pad_left, N * C};
+    const DwArm a = dw_arm(pass, K, stride, dtype == LSS_CONV_BF16 ? 2 : 4, g, N, pass == LSS_DW_BWD_WEIGHT ? ngroups : 1);
+    arm->family = a.family;
+    arm->seg = a.seg;
+    arm->banded = a.banded;
+    arm->pb = a.pb;
+    return 0;
+}
+
 int lss_dwconv_fwd(const void* x, int32_t dtype, const float* w, int32_t N, int32_t C, int32_t Hi, int32_t Wi,
                    int32_t K, int32_t stride, int32_t pad_top, int32_t pad_left, int32_t Ho, int32_t Wo, void* y,
                    void* stream) {
     if (!x || !w || !y || !geo_ok(N, C, Hi, Wi, K, stride, Ho, Wo) || !aligned16(x, y)) return LSS_CONV_EINVAL;
     const DwGeo g{C, Hi, Wi, Ho, Wo, pad_top, pad_left, N * C};
-    return dispatch_kst<Fwd>(K, stride, dtype, x, w, g, 0, y, (hipStream_t)stream);
+    return dispatch_kst<Fwd>(K, stride, dtype, x, w, g, y, (hipStream_t)stream);
 }
 
 int lss_dwconv_bwd_data(const void* dy, int32_t dtype, const float* w, int32_t N, int32_t C, int32_t Hi, int32_t Wi,

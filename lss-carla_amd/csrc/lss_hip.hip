@@ -2836,23 +2836,32 @@ int lss_debug_status(int32_t* out4, int32_t clear) {
     return (int)r;
 }
 
+int lss_lift_prep_arm(const lss_dims_t* dims) {
+    if (!dims_ok(dims)) return LSS_EINVAL;
+    if (dims->D > 256) return LSS_EUNSUPPORTED;
+    // depth bins per wave part: 16 (D <= 64, the reference's D = 41), 32, 64
+    return dims->D <= 64 ? 16 : dims->D <= 128 ? 32 : 64;
+}
+
 int lss_lift_prep(const void* depthnet_out, int32_t in_dtype, const lss_dims_t* dims, float* depth, void* ctx_t,
                   int32_t ctx_dtype, lss_stream_t stream) {
     if (!dims_ok(dims) || !depthnet_out || !depth || !ctx_t) return LSS_EINVAL;
-    if (dims->D > 256) return LSS_EUNSUPPORTED;
+    const int arm = lss_lift_prep_arm(dims);
+    if (arm < 0) return arm;
     const int HW = dims->H * dims->W;
     const int npix = dims->B * dims->N * HW;
     const dim3 grid(xcd_grid(grid_blocks(npix, 64))), block(kBlock);
     hipStream_t s = (hipStream_t)stream;
-    // depth bins per wave part: 16 (D <= 64, the reference's D = 41), 32, 64
 #define LSS_PREP_NI(IT, CT, NI)                                                                                    \
     hipLaunchKernelGGL((k_lift_prep<IT, CT, NI>), grid, block, 0, s, (const IT*)depthnet_out, dims->D, HW, npix,  \
                        depth, (CT*)ctx_t)
 #define LSS_PREP(IT, CT)                                                                                           \
     do {                                                                                                           \
-        if (dims->D <= 64) LSS_PREP_NI(IT, CT, 16);                                                                \
-        else if (dims->D <= 128) LSS_PREP_NI(IT, CT, 32);                                                          \
-        else LSS_PREP_NI(IT, CT, 64);                                                                              \
+        switch (arm) {                                                                                             \
+            case 16: LSS_PREP_NI(IT, CT, 16); break;                                                               \
+            case 32: LSS_PREP_NI(IT, CT, 32); break;                                                               \
+            default: LSS_PREP_NI(IT, CT, 64); break;                                                               \
+        }                                                                                                          \
     } while (0)
     if (in_dtype == LSS_F32 && ctx_dtype == LSS_F32) LSS_PREP(float, float);
     else if (in_dtype == LSS_F32 && ctx_dtype == LSS_BF16) LSS_PREP(float, bf16);
@@ -3052,11 +3061,28 @@ int lss_bev_rows(const void* dbev, int32_t g_dtype, const int32_t* cell_start, c
     return launch_status();
 }
 
+int lss_splat_bwd_arm(int32_t g_dtype, const lss_dims_t* dims) {
+    if (!dims_ok(dims)) return LSS_EINVAL;
+    if (dims->D > 4 * kWave) return LSS_EUNSUPPORTED;  // D <= 256 (the register kernel's 4 chunks)
+    if (g_dtype != LSS_F32 && g_dtype != LSS_BF16) return LSS_EINVAL;
+    const int D = dims->D, HW = dims->H * dims->W;
+    const int npix = dims->B * dims->N * HW;
+    // pixel tiles (D <= 64; whole tiles, at most one image boundary per tile, store runs inside one
+    // image) or the register kernel, 64 depth bins per chunk
+    auto tile_ok = [&](int px) { return npix % px == 0 && px <= HW && HW % 4 == 0 && (px % 8 != 0 || HW % 8 == 0); };
+    if (g_dtype == LSS_BF16 && D <= 48 && tile_ok(kBwdBigWaves * kBwdBigPpw)) return LSS_BWD_TILE4;
+    if (D <= 48 && tile_ok(8)) return LSS_BWD_TILE48;
+    if (D <= 64 && tile_ok(8)) return LSS_BWD_TILE64;
+    return D <= kWave ? LSS_BWD_REG1 : D <= 2 * kWave ? LSS_BWD_REG2 : LSS_BWD_REG4;
+}
+
 int lss_splat_bwd(const void* g, int32_t g_dtype, int32_t rows_layout, const int32_t* cell_of, const float* depth,
                   const void* ctx_t, int32_t ctx_dtype, const lss_dims_t* dims, const lss_grid_t* grid,
                   void* d_depthnet_out, int32_t d_dtype, lss_stream_t stream) {
     if (!dims_ok(dims) || !grid_ok(grid) || !g || !cell_of || !depth || !ctx_t || !d_depthnet_out) return LSS_EINVAL;
-    if (dims->D > 4 * kWave) return LSS_EUNSUPPORTED;  // D <= 256 (the register kernel's 4 chunks)
+    if (ctx_dtype != LSS_F32 && ctx_dtype != LSS_BF16) return LSS_EINVAL;
+    const int arm = lss_splat_bwd_arm(g_dtype, dims);
+    if (arm < 0) return arm;
     SplatGeo sg = splat_geo(grid, dims);
     sg.nrows = sg.ncells;  // gradient rows: one per cell
     const int HW = dims->H * dims->W;
@@ -3066,43 +3092,33 @@ int lss_splat_bwd(const void* g, int32_t g_dtype, int32_t rows_layout, const int
     hipStream_t s = (hipStream_t)stream;
     const bool nhwc = rows_layout == LSS_NHWC;
     const int D = dims->D;
-    // pixel tiles (D <= 64; whole tiles, at most one image boundary per tile, store runs inside one
-    // image) or the register kernel, 64 depth bins per chunk
-    auto tile_ok = [&](int px) { return npix % px == 0 && px <= HW && HW % 4 == 0 && (px % 8 != 0 || HW % 8 == 0); };
-#define LSS_BWD_REGK(GT, DT, CT, NH)                                                                              \
-    do {                                                                                                          \
-        if (D <= kWave)                                                                                           \
-            hipLaunchKernelGGL((k_splat_bwd_reg<GT, DT, CT, NH, 1>), gr, bl, 0, s, (const GT*)g, cell_of, depth,  \
-                               (const CT*)ctx_t, D, HW, npix, sg, (DT*)d_depthnet_out);                           \
-        else if (D <= 2 * kWave)                                                                                  \
-            hipLaunchKernelGGL((k_splat_bwd_reg<GT, DT, CT, NH, 2>), gr, bl, 0, s, (const GT*)g, cell_of, depth,  \
-                               (const CT*)ctx_t, D, HW, npix, sg, (DT*)d_depthnet_out);                           \
-        else                                                                                                      \
-            hipLaunchKernelGGL((k_splat_bwd_reg<GT, DT, CT, NH, 4>), gr, bl, 0, s, (const GT*)g, cell_of, depth,  \
-                               (const CT*)ctx_t, D, HW, npix, sg, (DT*)d_depthnet_out);                           \
-    } while (0)
+#define LSS_BWD_REGK(GT, DT, CT, NH, CH)                                                                          \
+    hipLaunchKernelGGL((k_splat_bwd_reg<GT, DT, CT, NH, CH>), gr, bl, 0, s, (const GT*)g, cell_of, depth,         \
+                       (const CT*)ctx_t, D, HW, npix, sg, (DT*)d_depthnet_out)
 #define LSS_BWD_TILE(GT, DT, CT, NH, MAXD, WV, PPW, MINW)                                                        \
     hipLaunchKernelGGL((k_splat_bwd_tile<GT, DT, CT, NH, MAXD, WV, PPW, MINW>), dim3(xcd_grid(npix / ((WV) * (PPW)))), \
                        dim3((WV) * kWave), 0, s, (const GT*)g, cell_of, depth, (const CT*)ctx_t, D, HW, npix, sg,      \
                        (DT*)d_depthnet_out)
+    // (LSS_BWD_TILE4 is chosen for bf16 rows only: with fp32 rows its case names the 8-pixel tile again)
 #define LSS_BWD_NH(GT, DT, CT, NH)                                                                                \
     do {                                                                                                          \
         constexpr bool kB16 = sizeof(GT) == 2;                                                                    \
-        if (kB16 && D <= 48 && tile_ok(kBwdBigWaves * kBwdBigPpw))                                                \
-            LSS_BWD_TILE(GT, DT, CT, NH, 48, kB16 ? kBwdBigWaves : 8, kB16 ? kBwdBigPpw : 1,                     \
-                         kB16 ? kBwdBigMinW : 4);                                                                 \
-        else if (D <= 48 && tile_ok(8))                                                                           \
-            LSS_BWD_TILE(GT, DT, CT, NH, 48, 8, 1, kB16 ? 5 : 4);                                                 \
-        else if (D <= 64 && tile_ok(8))                                                                           \
-            LSS_BWD_TILE(GT, DT, CT, NH, 64, 8, 1, kB16 ? 5 : 4);                                                 \
-        else                                                                                                      \
-            LSS_BWD_REGK(GT, DT, CT, NH);                                                                         \
+        switch (arm) {                                                                                            \
+            case LSS_BWD_TILE4:                                                                                   \
+                LSS_BWD_TILE(GT, DT, CT, NH, 48, kB16 ? kBwdBigWaves : 8, kB16 ? kBwdBigPpw : 1,                 \
+                             kB16 ? kBwdBigMinW : 4);                                                             \
+                break;                                                                                            \
+            case LSS_BWD_TILE48: LSS_BWD_TILE(GT, DT, CT, NH, 48, 8, 1, kB16 ? 5 : 4); break;                     \
+            case LSS_BWD_TILE64: LSS_BWD_TILE(GT, DT, CT, NH, 64, 8, 1, kB16 ? 5 : 4); break;                     \
+            case LSS_BWD_REG1: LSS_BWD_REGK(GT, DT, CT, NH, 1); break;                                            \
+            case LSS_BWD_REG2: LSS_BWD_REGK(GT, DT, CT, NH, 2); break;                                            \
+            default: LSS_BWD_REGK(GT, DT, CT, NH, 4); break;                                                      \
+        }                                                                                                         \
     } while (0)
 #define LSS_BWD(GT, DT, CT)                                                                                       \
     do { if (nhwc) LSS_BWD_NH(GT, DT, CT, true); else LSS_BWD_NH(GT, DT, CT, false); } while (0)
 #define LSS_BWD2(GT, DT) \
     do { if (ctx_dtype == LSS_BF16) LSS_BWD(GT, DT, bf16); else LSS_BWD(GT, DT, float); } while (0)
-    if (ctx_dtype != LSS_F32 && ctx_dtype != LSS_BF16) return LSS_EINVAL;
     if (g_dtype == LSS_F32 && d_dtype == LSS_F32) LSS_BWD2(float, float);
     else if (g_dtype == LSS_F32 && d_dtype == LSS_BF16) LSS_BWD2(float, bf16);
     else if (g_dtype == LSS_BF16 && d_dtype == LSS_F32) LSS_BWD2(bf16, float);

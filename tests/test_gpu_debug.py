@@ -1,7 +1,8 @@
 """The LSS_DEBUG library (liblss_hip_debug.so): every data-derived global index of the kernels is checked
 on the device (include/lss_hip.h, lss_debug_status).
 
-* test_debug_build_parity_subset: the geometry / CSR / splat / backward / QuickCumsum parity tests and
+* test_debug_build_parity_subset: the geometry / CSR / splat / backward / QuickCumsum parity tests, every
+  kernel-selection arm of the lift / splat entry points (tests/test_gpu_dispatch_arms.py) and
   the fp32 NCHW module test (the one an illegal-address fault was once seen in, round 2) re-run in a
   child process on the debug library; conftest's fixture fails any test after which a check fired.
 * test_debug_checks_fire: in that child, a deliberately corrupted CSR (a context row and a point id out
@@ -28,6 +29,11 @@ SUBSET = ["tests/test_gpu_parity.py", "tests/test_gpu_quickcumsum.py",
           "tests/test_gpu_parity2.py::test_plan_workspace_is_ordered_across_streams",
           "tests/test_gpu_parity2.py::test_csr_build_ws_direct",
           "tests/test_gpu_parity2.py::test_two_z_bins_vs_reference",
+          # every kernel-selection arm of the lift / splat entry points (the depthwise kernels have no index checks)
+          "tests/test_gpu_dispatch_arms.py::test_splat_bwd_arm", "tests/test_gpu_dispatch_arms.py::test_lift_prep_arm",
+          "tests/test_gpu_dispatch_arms.py::test_splat_fwd_arm",
+          "tests/test_gpu_dispatch_arms.py::test_splat_bwd_refuses_more_than_256_bins",
+          "tests/test_gpu_dispatch_arms.py::test_lift_prep_refuses_more_than_256_bins",
           "tests/test_gpu_debug.py::test_debug_checks_fire"]
 
 

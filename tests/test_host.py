@@ -435,3 +435,140 @@ def test_dwconv_entry_points_refuse_bad_sizes_and_unaligned_pointers():
         assert calls(f[0] + off, f[1], f[2], good) == (_EINVAL,) * 4
         assert calls(f[0], f[1] + off, f[2], good) == (_EINVAL,) * 4
         assert calls(f[0] + off, f[1], f[2], good, dtype=_lib.F32) == (_EINVAL,) * 4
+
+
+# ---- kernel-selection arms (tests/arm_cases.py): the queries are host-only, so the table's coverage of the
+# arms is proved here; tests/test_gpu_dispatch_arms.py then runs every case on the GPU
+import ctypes  # noqa: E402
+
+import arm_cases as A  # noqa: E402
+
+
+def _dims(B, N, D, H, W):
+    return ctypes.byref(ops.make_dims(B, N, D, H, W))
+
+
+def _dw_arm(lib, pas, dtype, c):
+    Ho, Wo = A.dw_out(c)
+    pl, _, pt, _ = c.pads
+    a = _lib.DwArm()
+    assert lib.lss_dwconv_arm(pas, dtype, c.N, c.C, c.H, c.W, c.K, c.S, pt, pl, Ho, Wo, A.dw_groups(c),
+                              ctypes.byref(a)) == 0, c
+    assert a.pb >= (1 if a.family < 4 else 0) and a.seg in ((8, 4) if a.family < 2 else (0,)), (c, a.seg, a.pb)
+    assert not (a.banded and a.pb != 1), c
+    return A.dw_arm_name(a.family, a.seg, a.banded, a.pb)
+
+
+def test_arm_tables_cover_every_splat_and_lift_arm():
+    lib = _lib.load()
+    # splat backward: each case hits the arm it names; per row dtype the cases hit exactly the arms of the header
+    assert len(A.BWD_ARM_NAMES) == 6 and set(A.BWD_D) == {c.D for c in A.BWD_CASES}
+    for code, dt in ((_lib.F32, A.F32), (_lib.BF16, A.BF16)):
+        hit = {}
+        for c in A.BWD_CASES:
+            arm = lib.lss_splat_bwd_arm(code, _dims(*c.shape[:2], c.D, *c.shape[2:]))
+            assert arm == A.bwd_arm_of(c, dt), (c, A.BWD_ARM_NAMES[arm])
+            hit.setdefault(arm, set()).add(c.Z)
+        assert set(hit) == A.BWD_ARMS[dt]
+        assert all(z == {1, 2} for z in hit.values()), hit  # every arm with one and with two z bins
+        for shape, lo, hi, split in A.BWD_BOUNDARIES:
+            a, b = (lib.lss_splat_bwd_arm(code, _dims(*shape[:2], D, *shape[2:])) for D in (lo, hi))
+            assert (a != b) == split and a >= 0 and b >= 0, (shape, lo, a, b)
+            assert {(shape, lo), (shape, hi)} <= {(c.shape, c.D) for c in A.BWD_CASES}
+        assert lib.lss_splat_bwd_arm(code, _dims(1, 2, 256, 2, 4)) == A.REG4
+        assert lib.lss_splat_bwd_arm(code, _dims(1, 2, 257, 2, 4)) == A.EUNSUPPORTED
+        assert lib.lss_splat_bwd_arm(code, _dims(1, 2, 0, 2, 4)) == _EINVAL
+    assert A.BWD_ARMS[A.F32] | A.BWD_ARMS[A.BF16] == set(range(6))
+    assert lib.lss_splat_bwd_arm(2, _dims(1, 2, 41, 2, 4)) == _EINVAL and lib.lss_splat_bwd_arm(0, None) == _EINVAL
+    assert len(A.BWD_COMBOS) == 16
+    # lift prep
+    for BN, H, W in A.PREP_SHAPES:
+        assert {lib.lss_lift_prep_arm(_dims(1, BN, D, H, W)) for D in A.PREP_D} == A.PREP_ARMS
+        for D, ni in A.PREP_D.items():
+            assert lib.lss_lift_prep_arm(_dims(1, BN, D, H, W)) == ni and D <= 4 * ni, D
+        for lo, hi in A.PREP_BOUNDARIES:
+            assert A.PREP_D[lo] != A.PREP_D[hi]
+        assert lib.lss_lift_prep_arm(_dims(1, BN, 257, H, W)) == A.EUNSUPPORTED
+    assert lib.lss_lift_prep_arm(None) == _EINVAL and len(A.PREP_COMBOS) == 4
+    # splat forward: its 12 instantiations are its arguments themselves
+    assert {(layout, mode, out) for layout, mode, out, _ in A.FWD_CASES} == A.FWD_ARMS and len(A.FWD_ARMS) == 12
+    assert {z for *_, z in A.FWD_CASES} == {1, 2}
+    for Z in (1, 2):
+        cells = A.fwd_geometry(Z)[1]
+        kept = cells[cells >= 0]
+        B = A.FWD_DIMS[0]
+        assert 0 < (cells < 0).mean() < 0.5 and kept.max() < B * Z * 64
+        assert np.bincount(kept).max() >= A.FWD_CROWD
+
+
+def test_arm_table_covers_every_depthwise_arm():
+    lib = _lib.load()
+    hit = {}
+    for c in A.DW_CASES:
+        for pas, want in ((A.DW_FWD, c.fwd), (A.DW_BWD_DATA, c.bwd_data), (A.DW_BWD_WEIGHT, c.bwd_weight)):
+            got = {_dw_arm(lib, pas, dt, c) for dt in (_lib.F32, _lib.BF16)}
+            assert got == {want}, (c, pas, got)
+            hit.setdefault((pas, c.K, c.S), set()).add(want)
+    for pas in (A.DW_FWD, A.DW_BWD_DATA, A.DW_BWD_WEIGHT):
+        for K in (3, 5):
+            for S in (1, 2):
+                assert hit[pas, K, S] == A.dw_arms(pas, K, S), (pas, K, S, hit[pas, K, S] ^ A.dw_arms(pas, K, S))
+    families = {a.split("/")[0] for arms in hit.values() for a in arms}
+    assert families == set(A.DW_FAMILIES)
+    # the stride-2 parities on both odd-by-even maps; one and several image groups; N = 1 and 3
+    for hw in ((5, 6), (6, 5)):
+        for K in (3, 5):
+            assert {c.bwd_data for c in A.DW_CASES if (c.H, c.W, c.K) == (*hw, K)} == A.dw_arms(A.DW_BWD_DATA, K, 2)
+    assert {A.dw_groups(c) for c in A.DW_CASES} == {1, 2} and {1, 3} <= {c.N for c in A.DW_CASES}
+    assert {A.dw_groups(c) for c in A.DW_FOLD_OFF} == {1, 2}
+    # a covered right edge is what keeps a Wo % 4 == 0 plane on the LDS kernels
+    off = [c for c in A.DW_CASES if "not covered" in c.note]
+    assert {(c.K, c.S) for c in off} == {(3, 2), (5, 2)}
+    assert all(A.dw_out(c)[1] == 8 and c.fwd == "reg" and c.bwd_weight == "reg" for c in off)
+    # stride-1 backward-data chooses by the mirrored shape
+    assert any(c.S == 1 and c.fwd != c.bwd_data and c.bwd_data == "reg" for c in A.DW_CASES)
+    assert any(c.S == 1 and c.fwd == "reg" and c.bwd_data.startswith("lds") for c in A.DW_CASES)
+    a = _lib.DwArm()
+    assert lib.lss_dwconv_arm(3, 0, 2, 8, 6, 8, 3, 1, 1, 1, 6, 8, 1, ctypes.byref(a)) == _EINVAL  # pass
+    assert lib.lss_dwconv_arm(0, 2, 2, 8, 6, 8, 3, 1, 1, 1, 6, 8, 1, ctypes.byref(a)) == _EINVAL  # dtype
+    assert lib.lss_dwconv_arm(0, 0, 2, 8, 6, 8, 4, 1, 1, 1, 6, 8, 1, ctypes.byref(a)) == _EINVAL  # K
+    assert lib.lss_dwconv_arm(2, 0, 2, 8, 6, 8, 3, 1, 1, 1, 6, 8, 3, ctypes.byref(a)) == _EINVAL  # groups > N
+    assert lib.lss_dwconv_arm(0, 0, 2, 8, 6, 8, 3, 1, 1, 1, 6, 8, 1, None) == _EINVAL
+
+
+def _room(got, want, rtol, atol):
+    want = np.asarray(want, dtype=np.float64)
+    return float((np.abs(np.asarray(got, dtype=np.float64) - want) / (atol + rtol * np.abs(want))).max())
+
+
+def test_arm_references_fp32_margins():
+    """The bars of the arm tests leave a plain fp32 evaluation of each reference formula at least 4x room at
+    the largest case: a kernel that accumulates in fp32 in any order can meet them."""
+    big = max(A.BWD_CASES, key=lambda c: (c.D, np.prod(c.shape)))
+    assert big.D == 256
+    ins = A.bwd_inputs(big)
+    rooms = {"splat_bwd": _room(A.bwd_reference(*ins, dtype=np.float32), A.bwd_reference(*ins), **A.F32_TOL)}
+    x = A.prep_input(*A.PREP_SHAPES[-1][:1], 256, *A.PREP_SHAPES[-1][1:])
+    rooms["lift_prep"] = _room(A.prep_reference(x, 256, np.float32)[0], A.prep_reference(x, 256)[0], **A.F32_TOL)
+    cells = A.fwd_geometry(2)[1]
+    depth, ctx, rows = A.fwd_inputs(2)
+    rooms["splat_fwd"] = _room(A.fwd_reference(cells, 2, depth, ctx, dtype=np.float32),
+                               A.fwd_reference(cells, 2, depth, ctx), **A.F32_TOL)
+    rooms["splat_fwd_lifted"] = _room(A.fwd_reference(cells, 2, rows=rows, dtype=np.float32),
+                                      A.fwd_reference(cells, 2, rows=rows), **A.F32_TOL)
+    import torch.nn.functional as Fn
+    tall = max(A.DW_CASES, key=lambda c: c.H)
+    most = max(A.DW_CASES, key=lambda c: c.N * c.H * c.W)
+    for name, c in (("dw_tall", tall), ("dw_groups", most)):
+        x, w, dy = A.dw_inputs(c, A.F32)
+        outs = []
+        for dt in (torch.float32, torch.float64):
+            xr, wr = x.detach().to(dt).clone().requires_grad_(True), w.detach().to(dt).clone().requires_grad_(True)
+            y = Fn.conv2d(Fn.pad(xr, c.pads), wr, stride=c.S, groups=c.C)
+            y.backward(dy.to(dt))
+            outs.append((y.detach().numpy(), xr.grad.numpy(), wr.grad.numpy()))
+        tol, wtol = A.dw_tols(A.F32)
+        rooms[name] = max(_room(outs[0][0], outs[1][0], **tol), _room(outs[0][1], outs[1][1], **tol))
+        rooms[name + "_dw"] = _room(outs[0][2], outs[1][2], **wtol)
+    print({k: round(v, 4) for k, v in rooms.items()})
+    assert all(v <= 0.25 for v in rooms.values()), rooms

@@ -308,6 +308,28 @@ int lss_bn_bwd_rank1(const void* g1, const float* w1, const void* x, int32_t N, 
                      int32_t act, int32_t ngroups, float* partial, float* coef, float* dgamma, float* dbeta, void* dx,
                      void* stream);
 
+/* (ABI 28) Eval-mode batch norm fused with an activation and a residual add, for inference
+ * (model.eval() under no_grad, then out.sigmoid(): src/explore.py:244-246 eval_model_iou and 317-328
+ * viz_model_preds) over the same layers as lss_bn_fwd (Up's BN + ReLU, src/models.py:22-28, and BevEncode,
+ * src/models.py:97-115, and the EfficientNet-B0 trunk):
+ *   y = act(fmaf(x, scale_c, shift_c) [+ residual]), rounded to the element type once,
+ *   scale_c = gamma_c * rsqrtf(running_var_c + eps), shift_c = beta_c - running_mean_c * scale_c
+ * -- the training kernels' expression with the running statistics in place of the batch's. act is
+ * LSS_ACT_NONE, LSS_ACT_RELU or LSS_ACT_SWISH; residual (nullable) is allowed with each. One launch: the
+ * kernel computes the coefficients it needs from the four arrays itself. Nothing but y is written:
+ * gamma, beta (both nullable: 1 and 0) and the running statistics are read-only.
+ * Layouts, element types and alignment of x, residual, y: exactly lss_bn_fwd's (NCHW any C; LSS_CONV_NHWC
+ * with C % 8 == 0 and 256 % (C / 8) == 0; 16 B, 8 B for NCHW bf16 with HW % 8 == 4, else one element);
+ * the fp32 arrays 4 B. LSS_CONV_EINVAL before any launch for anything else. */
+int lss_bn_eval(const void* x, const void* residual, int32_t dtype, int32_t layout, int32_t N, int32_t C, int32_t HW,
+                const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                float eps, int32_t act, void* y, void* stream);
+/* (ABI 28) The same coefficients as the (4, C) fp32 array lss_head1_fwd2 / lss_headk_fwd take as bn_stats
+ * (rows: running_mean, rstd, scale, shift): BevEncode's tail (src/models.py:111-115) in eval mode without
+ * the normalised map, as src/explore.py:244-246, 317-328 run it. One small launch. */
+int lss_bn_eval_coef(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                     float eps, int32_t C, float* stats /* (4, C) */, void* stream);
+
 /* Bilinear upsampling with align_corners=True (nn.Upsample(mode="bilinear", align_corners=True),
  * src/models.py:19, 109) fused with Up's channel concatenation (torch.cat([x2, x1], 1),
  * src/models.py:33). All tensors channels-last bf16, 16-byte aligned, C1 and C2 multiples of 8,

@@ -18,7 +18,7 @@ DEBUG_LIB_PATH = os.path.join(_HERE, "liblss_hip_debug.so")  # LSS_DEBUG=1: devi
 
 F32, BF16 = 0, 1
 NCHW, NHWC = 0, 1
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 
 class Dims(ctypes.Structure):
@@ -140,6 +140,8 @@ SIGNATURES = {
                                    _p, _p, _p, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p]),
     "lss_bn_bwd2": (ctypes.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _i32, _i32, _p, _p,
                                    _p, _p, _p, _p, _p, _p]),
+    "lss_bn_eval": (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, ctypes.c_float, _i32, _p, _p]),
+    "lss_bn_eval_coef": (ctypes.c_int, [_p, _p, _p, _p, ctypes.c_float, _i32, _p, _p]),
     "lss_upsample_cat_fwd": (ctypes.c_int, [_p, _p] + [_i32] * 7 + [_p, _p]),
     "lss_upsample_bwd": (ctypes.c_int, [_p] + [_i32] * 7 + [_p, _p]),
     "lss_upsample_cat_fwd2": (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p]),

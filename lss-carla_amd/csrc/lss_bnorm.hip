@@ -18,6 +18,8 @@
 // NCHW: block = (channel, group of images), the channel is block-uniform (scalar loads / SGPR
 // operands), V consecutive elements per thread. NHWC: block = group of pixels x all channels,
 // 8 consecutive channels per thread, per-channel coefficients staged in LDS.
+// Eval mode (lss_bn_eval, lss_bn_eval_coef; inference as src/explore.py:244-246, 317-328 runs it): the same
+// apply with the coefficients of the running statistics, one launch, no statistics pass.
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
@@ -168,15 +170,25 @@ struct BnParams {
     long long* batches;  // nn.BatchNorm2d.num_batches_tracked (nullable), +1 per forward
 };
 
+// y = x * scale + shift for a channel of mean / variance (mean, var): the one expression of the
+// coefficients, shared by the training kernels (batch statistics, finalize_channel) and the eval-mode
+// kernels (running statistics, eval_coef)
+// (gamma / beta nullable: 1 and 0; read here, in this order, so the training kernels compile as before)
+__device__ __forceinline__ void bn_coef(const float* gamma, const float* beta, int c, float mean, float var, float eps,
+                                        float& rstd, float& scale, float& shift) {
+    rstd = rsqrtf(var + eps);
+    scale = (gamma ? gamma[c] : 1.f) * rstd;
+    shift = (beta ? beta[c] : 0.f) - mean * scale;
+}
+
 // statistics of channel c from its folded sums; the writer block stores running / saved values
 __device__ __forceinline__ void finalize_channel(float s1, float s2, float k, float n, int c, int C,
                                                  const BnParams& P, bool writer, float& scale, float& shift) {
     const float d = s1 / n;
     const float mean = k + d;
     const float var = fmaxf(s2 / n - d * d, 0.f);  // biased, used to normalise
-    const float rstd = rsqrtf(var + P.eps);
-    scale = (P.gamma ? P.gamma[c] : 1.f) * rstd;
-    shift = (P.beta ? P.beta[c] : 0.f) - mean * scale;
+    float rstd;
+    bn_coef(P.gamma, P.beta, c, mean, var, P.eps, rstd, scale, shift);
     if (writer) {
         if (c == 0 && P.batches) *P.batches += 1;
         if (P.run_mean) P.run_mean[c] = (1.f - P.momentum) * P.run_mean[c] + P.momentum * mean;
@@ -1189,6 +1201,126 @@ __global__ __launch_bounds__(kBlock) void k_bn_bwd_apply_rows_nhwc(const T* __re
     });
 }
 
+// ============================================================================= eval mode
+// y = act(x * scale_c + shift_c [+ residual]) with the coefficients of the RUNNING statistics (model.eval(),
+// src/explore.py:244-246, 317-328): no statistics pass, nothing written but y. One launch; every block (NCHW)
+// or thread (NHWC) computes the coefficients it needs from the four per-channel arrays in its prologue.
+// Every load is issued unconditionally from an address clamped into the block's range (a load under a
+// bounds branch is waited for before the next is issued), kEvalU 16-B loads per tensor in flight per
+// thread; only the stores are conditional. 64-bit element offsets.
+struct BnEval {
+    const float* gamma;  // nullable: 1
+    const float* beta;   // nullable: 0
+    const float* mean;   // running_mean
+    const float* var;    // running_var
+    float eps;
+};
+__device__ __forceinline__ void eval_coef(const BnEval& E, int c, float& rstd, float& scale, float& shift) {
+    bn_coef(E.gamma, E.beta, c, E.mean[c], E.var[c], E.eps, rstd, scale, shift);
+}
+
+constexpr int kEvalU = 4;        // vectors (NCHW) / rows (NHWC) per thread and iteration
+constexpr int kEvalBlocks = 1024;  // 256 CUs x 4 blocks of 4 waves: all resident at the kernels' 30-106 VGPRs
+
+// NCHW: unit u = (channel c = u / G, chunk q = u % G) of kBlock * kEvalU vectors out of the channel's
+// N * HW / V (image after image); the channel is uniform over the block, so its four parameters are
+// scalar loads and the coefficients sit in SGPRs. Blocks stride over the units.
+template <int V, typename T>
+__global__ __launch_bounds__(kBlock) void k_bn_eval_nchw(const T* __restrict__ x, const T* __restrict__ res, BnGeo g,
+                                                         int G, BnEval E, int act, T* __restrict__ y) {
+    const int per = g.HW / V, cnt = per * g.N;
+    const long units = (long)g.C * G;
+    for (long u = blockIdx.x; u < units; u += gridDim.x) {
+        const int c = (int)(u / G), q = (int)(u - (long)c * G);
+        float rstd, sc, sh;
+        eval_coef(E, c, rstd, sc, sh);
+        const long e0 = (long)q * (kBlock * kEvalU) + threadIdx.x;
+        size_t off[kEvalU];
+        float v[kEvalU][V], r[kEvalU][V];
+#pragma unroll
+        for (int it = 0; it < kEvalU; ++it) {
+            const long e = e0 + it * kBlock;
+            const int ec = (int)(e < cnt ? e : cnt - 1);
+            const int nl = ec / per;
+            off[it] = ((size_t)nl * g.C + c) * g.HW + (size_t)(ec - nl * per) * V;
+            ldv<V>(x + off[it], v[it]);
+        }
+        if (res) {
+#pragma unroll
+            for (int it = 0; it < kEvalU; ++it) ldv<V>(res + off[it], r[it]);
+        }
+#pragma unroll
+        for (int it = 0; it < kEvalU; ++it) {
+            if (e0 + it * kBlock < cnt) {
+#pragma unroll
+                for (int j = 0; j < V; ++j) {
+                    float z = fmaf(v[it][j], sc, sh);
+                    if (res) z += r[it][j];
+                    v[it][j] = act_fwd(z, act);
+                }
+                stv<V>(y + off[it], v[it]);
+            }
+        }
+    }
+}
+
+// NHWC: block q of the grid takes the pixel rows [M q / G, M (q + 1) / G); a thread keeps one channel
+// octet (kBlock % (C / 8) == 0), whose 16 coefficients it computes once and holds in registers, and walks
+// the block's rows kEvalU at a time.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_bn_eval_nhwc(const T* __restrict__ x, const T* __restrict__ res, BnGeo g,
+                                                         BnEval E, int act, T* __restrict__ y) {
+    const int cg = g.C >> 3, step = kBlock / cg;
+    const int c0 = ((int)threadIdx.x % cg) * 8;
+    float sc[8], sh[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        float rstd;
+        eval_coef(E, c0 + j, rstd, sc[j], sh[j]);
+    }
+    const long M = (long)g.N * g.HW;
+    const long r0 = M * blockIdx.x / gridDim.x, r1 = M * (blockIdx.x + 1) / gridDim.x;
+    if (r0 >= r1) return;
+    for (long r = r0 + (int)threadIdx.x / cg; r < r1; r += (long)kEvalU * step) {
+        size_t off[kEvalU];
+        float v[kEvalU][8], rv[kEvalU][8];
+#pragma unroll
+        for (int u = 0; u < kEvalU; ++u) {
+            const long rr = r + (long)u * step;
+            off[u] = (size_t)(rr < r1 ? rr : r1 - 1) * g.C + c0;
+            ldv<8>(x + off[u], v[u]);
+        }
+        if (res) {
+#pragma unroll
+            for (int u = 0; u < kEvalU; ++u) ldv<8>(res + off[u], rv[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < kEvalU; ++u) {
+            if (r + (long)u * step < r1) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    float z = fmaf(v[u][j], sc[j], sh[j]);
+                    if (res) z += rv[u][j];
+                    v[u][j] = act_fwd(z, act);
+                }
+                stv<8>(y + off[u], v[u]);
+            }
+        }
+    }
+}
+
+// the (4, C) array the head kernels take as bn_stats (running_mean, rstd, scale, shift), one thread per channel
+__global__ __launch_bounds__(kBlock) void k_bn_eval_coef(BnEval E, int C, float* __restrict__ stats) {
+    const int c = blockIdx.x * kBlock + threadIdx.x;
+    if (c >= C) return;
+    float rstd, sc, sh;
+    eval_coef(E, c, rstd, sc, sh);
+    stats[c] = E.mean[c];
+    stats[C + c] = rstd;
+    stats[2 * C + c] = sc;
+    stats[3 * C + c] = sh;
+}
+
 // ============================================================================= host side
 inline bool bn_ok(const BnGeo& g, int layout) {
     if (g.N <= 0 || g.C <= 0 || g.HW <= 0 || (long)g.N * g.C * g.HW >= INT_MAX) return false;
@@ -1513,6 +1645,55 @@ int lss_bn_bwd_rank1(const void* g1, const float* w1, const void* x, int32_t N, 
     hipLaunchKernelGGL((k_bn_bwd_apply_rows_nhwc<bf16, true>), dim3(apply_blocks(g)), dim3(kBlock), 0, s,
                        (const bf16*)nullptr, xx, (const bf16*)nullptr, g, save_mean, coef, (int)act, (bf16*)dx,
                        (bf16*)nullptr, r1);
+    return launch_status();
+}
+int lss_bn_eval(const void* x, const void* residual, int32_t dtype, int32_t layout, int32_t N, int32_t C, int32_t HW,
+                const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                float eps, int32_t act, void* y, void* stream) {
+    const BnGeo g{N, C, HW};
+    if (!x || !y || !running_mean || !running_var || !bn_ok(g, layout)) return LSS_CONV_EINVAL;
+    if (act != LSS_ACT_NONE && act != LSS_ACT_RELU && act != LSS_ACT_SWISH) return LSS_CONV_EINVAL;
+    if (dtype != LSS_CONV_F32 && dtype != LSS_CONV_BF16) return LSS_CONV_EINVAL;
+    if (!ptrs_ok(bn_align_mask(dtype, layout, HW), x, residual, y) ||
+        !ptrs_ok(3, gamma, beta, running_mean, running_var))
+        return LSS_CONV_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const BnEval E{gamma, beta, running_mean, running_var, eps};
+#define LSS_BN_EVAL(T)                                                                                             \
+    do {                                                                                                           \
+        const T* xx = (const T*)x;                                                                                 \
+        const T* rr = (const T*)residual;                                                                          \
+        T* yy = (T*)y;                                                                                             \
+        if (layout == LSS_CONV_NHWC) {                                                                             \
+            const long rows = (long)N * HW, per_block = (long)(kBlock / (C / 8)) * kEvalU;                         \
+            const long b = (rows + per_block - 1) / per_block;                                                     \
+            hipLaunchKernelGGL(k_bn_eval_nhwc<T>, dim3((int)(b < kEvalBlocks ? b : kEvalBlocks)), dim3(kBlock), 0, \
+                               s, xx, rr, g, E, (int)act, yy);                                                     \
+        } else {                                                                                                   \
+            /* bf16 with HW % 8 == 4 and fp32 with HW % 4 == 0: V = 4 */                                           \
+            const int V8 = vec_nchw(HW), V = (V8 == 8 && sizeof(T) == 4) ? 4 : V8;                                 \
+            const long cnt = (long)N * (HW / V);                                                                   \
+            const int G = (int)((cnt + kBlock * kEvalU - 1) / (kBlock * kEvalU));                                  \
+            const long units = (long)C * G;                                                                        \
+            const dim3 gr((int)(units < kEvalBlocks ? units : kEvalBlocks)), bl(kBlock);                           \
+            if (V == 8) hipLaunchKernelGGL((k_bn_eval_nchw<8, T>), gr, bl, 0, s, xx, rr, g, G, E, (int)act, yy);   \
+            else if (V == 4) hipLaunchKernelGGL((k_bn_eval_nchw<4, T>), gr, bl, 0, s, xx, rr, g, G, E, (int)act, yy); \
+            else hipLaunchKernelGGL((k_bn_eval_nchw<1, T>), gr, bl, 0, s, xx, rr, g, G, E, (int)act, yy);          \
+        }                                                                                                          \
+    } while (0)
+    if (dtype == LSS_CONV_F32) LSS_BN_EVAL(float);
+    else LSS_BN_EVAL(bf16);
+#undef LSS_BN_EVAL
+    return launch_status();
+}
+
+int lss_bn_eval_coef(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                     float eps, int32_t C, float* stats, void* stream) {
+    if (!running_mean || !running_var || !stats || C <= 0) return LSS_CONV_EINVAL;
+    if (!ptrs_ok(3, gamma, beta, running_mean, running_var, stats)) return LSS_CONV_EINVAL;
+    const BnEval E{gamma, beta, running_mean, running_var, eps};
+    hipLaunchKernelGGL(k_bn_eval_coef, dim3((C + kBlock - 1) / kBlock), dim3(kBlock), 0, (hipStream_t)stream, E,
+                       (int)C, stats);
     return launch_status();
 }
 

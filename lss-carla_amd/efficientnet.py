@@ -27,7 +27,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .norm import bn_act
+from .norm import bn_act, eval_eligible
 
 # (repeats, kernel, stride, expand, in, out) for the 7 stages of B0, SE ratio 0.25.
 B0_STAGES = (
@@ -386,8 +386,14 @@ class MBConvBlock(nn.Module):
             x = self._depthwise_conv(x)
         x = bn_act(self._bn1, x, "swish")
         x = squeeze_excite(x, self._se_reduce, self._se_expand)
-        x = bn_act(self._bn2, pointwise_conv(self._project_conv, x))
-        if self.stride == 1 and self.in_f == self.out_f:
+        x = pointwise_conv(self._project_conv, x)
+        skip = self.stride == 1 and self.in_f == self.out_f
+        if skip and not self.training and eval_eligible(self._bn2, x, inputs):
+            # inference: the identity skip inside bn2's one pass (no drop-connect in eval mode) -- one pass
+            # over the map and one rounding less than bn2 followed by the add
+            return bn_act(self._bn2, x, "none", residual=inputs)
+        x = bn_act(self._bn2, x)
+        if skip:
             x = drop_connect_add(x, inputs, drop_connect_rate, self.training)
         return x
 

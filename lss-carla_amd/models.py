@@ -586,20 +586,56 @@ class _BnReluHeadK(torch.autograd.Function):
         return dx, dgamma, dbeta, dw, db, None
 
 
+def _bn_eval_head(bn: nn.BatchNorm2d, head: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
+    """The tail in eval mode without gradients (inference, src/explore.py:244-246): lss_bn_eval_coef fills the
+    (4, C) array from the running statistics, then the head kernel applies bf16(relu(fmaf(x, scale, shift)))
+    -- the value lss_bn_eval would have stored -- as it reads x. The normalised map is never written, and the
+    logits are those of conv1x1(head, bn_act(bn, x, "relu")) bit for bit."""
+    lib = _lib.load()
+    N, C, H, W = x.shape
+    K, HW, P = head.out_channels, H * W, N * H * W
+    dev = x.device
+    st = _lib.stream_handle(dev)
+    x = _lib.aligned(x)
+    stats = torch.empty(4, C, device=dev, dtype=torch.float32)  # running_mean, rstd, scale, shift
+    _lib.check(lib.lss_bn_eval_coef(_lib.ptr(bn.weight), _lib.ptr(bn.bias), _lib.ptr(bn.running_mean),
+                                    _lib.ptr(bn.running_var), float(bn.eps), C, _lib.ptr(stats), st),
+               "lss_bn_eval_coef")
+    y = torch.empty(N, K, H, W, device=dev, dtype=torch.bfloat16)
+    if K == 1:
+        w = head.weight.detach().to(torch.bfloat16).reshape(C).float()  # the bf16 operands, as _Head1x1 takes them
+        b = head.bias.detach().to(torch.bfloat16).float().reshape(1) if head.bias is not None else None
+        _lib.check(lib.lss_head1_fwd2(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), P, C, _lib.ptr(stats), _lib.ptr(y), st),
+                   "lss_head1_fwd2")
+    else:
+        w, b = _headk_params(head.weight, head.bias, K, C)
+        _lib.check(lib.lss_headk_fwd(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), P, HW, C, K, _lib.ptr(stats), _lib.ptr(y),
+                                     st), "lss_headk_fwd")
+    return y
+
+
 def bn_relu_head1(bn: nn.BatchNorm2d, head: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
     """head(relu(bn(x))) with head a 1x1 conv: to one channel, _BnReluHead1 where eligible (the benched
     BevEncode: training mode, channels-last bf16 under autocast); to 2..8 channels, _BnReluHeadK under the
-    same conditions when the head is marked as the model's logits head (logits_head); else bn_act + conv1x1."""
+    same conditions when the head is marked as the model's logits head (logits_head); in eval mode without
+    gradients (norm.eval_eligible), the same two head kernels on the running statistics (_bn_eval_head); else
+    bn_act + conv1x1."""
     C = x.shape[1] if x.dim() == 4 else 0
-    common = (USE_BN_HEAD and norm.USE_HIP_BN and bn.training and bn.affine and x.is_cuda
-              and norm.params_fp32(bn) and x.dim() == 4 and x.dtype == torch.bfloat16
-              and x.is_contiguous(memory_format=torch.channels_last)
-              and head.kernel_size == (1, 1) and head.stride == (1, 1) and head.groups == 1
-              and C % 8 == 0 and 64 % (C // 8) == 0 and 256 % (C // 8) == 0)
+    shape = (USE_BN_HEAD and norm.USE_HIP_BN and bn.affine and x.is_cuda
+             and norm.params_fp32(bn) and x.dim() == 4 and x.dtype == torch.bfloat16
+             and x.is_contiguous(memory_format=torch.channels_last)
+             and head.kernel_size == (1, 1) and head.stride == (1, 1) and head.groups == 1
+             and C % 8 == 0 and 64 % (C // 8) == 0 and 256 % (C // 8) == 0)
+    common = shape and bn.training
     if common and USE_HIP_HEAD1 and head.out_channels == 1 and _head1_eligible(head, x):
         return _BnReluHead1.apply(x, bn.weight, bn.bias, head.weight, head.bias, bn)
     if common and head.padding in ((0, 0), "valid") and _headk_eligible(head, x):
         return _BnReluHeadK.apply(x, bn.weight, bn.bias, head.weight, head.bias, bn)
+    if (shape and not bn.training and head.padding in ((0, 0), "valid") and norm.eval_eligible(bn, x)
+            and norm.no_grad_wanted(head.weight, head.bias)
+            and ((USE_HIP_HEAD1 and head.out_channels == 1 and _head1_eligible(head, x)) or _headk_eligible(head, x))):
+        with torch.no_grad():
+            return _bn_eval_head(bn, head, x)
     return conv1x1(head, bn_act(bn, x, "relu"))
 
 

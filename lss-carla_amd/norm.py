@@ -3,8 +3,14 @@
 ``bn_act(bn, x, act, residual)`` computes ``act(bn(x) [+ residual])`` for a BatchNorm2d module in
 training mode with the module's own parameters and buffers (running statistics updated as PyTorch
 does, ``num_batches_tracked`` incremented), so state_dicts are unchanged. Used where the reference
-applies BN followed by swish (EfficientNet-B0) or ReLU (``Up``, ResNet-18 BevEncode). In eval mode,
-on CPU tensors, or with ``USE_HIP_BN = False``, it runs the same computation with stock PyTorch ops.
+applies BN followed by swish (EfficientNet-B0) or ReLU (``Up``, ResNet-18 BevEncode).
+
+In eval mode with no gradient wanted (inference: ``model.eval()`` under ``no_grad``) it runs
+``lss_bn_eval``: one launch that applies the coefficients of the running statistics, the residual and the
+activation, and writes nothing but the output (``USE_HIP_BN_EVAL``; ``eval_eligible`` is the guard).
+Eval mode with gradients (frozen-BN fine-tuning), CPU tensors, a module whose parameters are not fp32,
+``affine=False``, ``track_running_stats=False`` in eval mode, channels-last maps whose channel count the
+kernels do not take, or ``USE_HIP_BN = False`` run the same computation with stock PyTorch ops.
 """
 from __future__ import annotations
 
@@ -17,6 +23,8 @@ from torch import nn
 from . import _lib
 
 USE_HIP_BN = True
+# eval mode without gradients on lss_bn_eval (needs USE_HIP_BN too); off: the stock op, as before ABI 28
+USE_HIP_BN_EVAL = True
 # channels-last ReLU without a residual: the backward recomputes the output from x (lss_bn_bwd with
 # y = NULL) instead of keeping and re-reading it
 RECOMPUTE_RELU_Y = True
@@ -138,12 +146,50 @@ def params_fp32(bn: nn.BatchNorm2d) -> bool:
                for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var))
 
 
+def _shape_ok(bn: nn.BatchNorm2d, x: torch.Tensor, layout: Optional[int]) -> bool:
+    """What both kernel families ask of the module and the map (the mode apart)."""
+    return (x.is_cuda and x.dim() == 4 and layout is not None and bn.affine
+            and x.dtype in (torch.float32, torch.bfloat16) and params_fp32(bn)
+            and (layout == NCHW or (x.shape[1] % 8 == 0 and 256 % (x.shape[1] // 8) == 0)))
+
+
+def no_grad_wanted(*tensors) -> bool:
+    return not torch.is_grad_enabled() or not any(t is not None and t.requires_grad for t in tensors)
+
+
+def eval_eligible(bn: nn.BatchNorm2d, x: torch.Tensor, residual: Optional[torch.Tensor] = None) -> bool:
+    """Whether bn_act(bn, x, ., residual) takes lss_bn_eval: both switches on, the module in eval mode with
+    its running statistics, no gradient wanted, and the layout / dtype / parameter rules of the training path."""
+    return (USE_HIP_BN and USE_HIP_BN_EVAL and not bn.training and bn.track_running_stats
+            and bn.running_mean is not None and bn.running_var is not None
+            and no_grad_wanted(x, residual, bn.weight, bn.bias) and _shape_ok(bn, x, _layout(x))
+            and (residual is None or residual.shape == x.shape))
+
+
+def _bn_eval(bn: nn.BatchNorm2d, x: torch.Tensor, act: int, residual: Optional[torch.Tensor], layout: int):
+    lib = _lib.load()
+    N, C, H, W = x.shape
+    x = _lib.aligned(x)
+    if residual is not None:
+        residual = residual.to(x.dtype)
+        residual = _lib.aligned(residual.contiguous(memory_format=torch.channels_last if layout == NHWC else
+                                                    torch.contiguous_format))
+    y = torch.empty_like(x)
+    _lib.check(lib.lss_bn_eval(_lib.ptr(x), _lib.ptr(residual), _lib.dtype_code(x.dtype), layout, N, C, H * W,
+                               _lib.ptr(bn.weight), _lib.ptr(bn.bias), _lib.ptr(bn.running_mean),
+                               _lib.ptr(bn.running_var), float(bn.eps), act, _lib.ptr(y),
+                               _lib.stream_handle(x.device)), "lss_bn_eval")
+    return y
+
+
 def bn_act(bn: nn.BatchNorm2d, x: torch.Tensor, act: str = "none", residual: Optional[torch.Tensor] = None):
     """act(bn(x) [+ residual]) with act in {'none', 'relu', 'swish'}."""
+    if not bn.training:
+        if eval_eligible(bn, x, residual):
+            with torch.no_grad():
+                return _bn_eval(bn, x, ACT[act], residual, _layout(x))
+        return _torch_bn_act(bn, x, act, residual)
     layout = _layout(x)
-    use = (USE_HIP_BN and bn.training and x.is_cuda and x.dim() == 4 and layout is not None and bn.affine
-           and x.dtype in (torch.float32, torch.bfloat16) and params_fp32(bn)
-           and (layout == NCHW or (x.shape[1] % 8 == 0 and 256 % (x.shape[1] // 8) == 0)))
-    if not use:
+    if not (USE_HIP_BN and _shape_ok(bn, x, layout)):
         return _torch_bn_act(bn, x, act, residual)
     return _BnAct.apply(x, bn.weight, bn.bias, residual, bn, ACT[act], layout)

@@ -1,0 +1,355 @@
+"""Inference: ``Predictor`` and ``python -m lss_carla_amd.predict``.
+
+What the reference's users do with a trained network (``src/explore.py:244-246`` eval_model_iou, ``:317-328``
+viz_model_preds: ``model.eval()``, ``no_grad``, ``out.sigmoid()``), built from the pieces the training loop
+already has -- static inputs, ``ops.HostInverses`` behind ``model.static_inverses``, ``FlatParams`` for the
+bf16 working weights and the prepacked depthnet weight, autocast, one HIP graph -- so a caller does not have to
+rebuild ``EvalStep`` by hand:
+
+    p = L.Predictor(model, bsz, device, amp_dtype=torch.bfloat16, threshold=0.5, graph=True)
+    p.load(path)                     # explore.py's plain state_dict, or train_simbev.py's {"model_state_dict": ...}
+    logits = p(imgs, rots, trans, intrins, post_rots, post_trans)    # host or device tensors, b <= bsz samples
+    p.probs(); p.masks()             # sigmoid as fp32; uint8 (b, K, X, Y) = logits > logit(threshold)
+
+The forward runs in eval mode without gradients, so every batch norm takes ``lss_bn_eval`` (norm.py), the
+MBConv skips ride in bn2's pass and BevEncode's tail never writes its normalised map. The working parameters
+are materialised once (construction, ``load()``, ``refresh()``): the replayed graph holds no weight casts.
+Eval mode has no op across samples, so a batch of b < bsz samples fills samples 0..b-1 of the static inputs and
+reads the first b of the outputs; the rest keep whatever they held. Returned tensors are views of static
+buffers, valid until the next call. A call does not synchronise the host, HostInverses' bounded wait (two
+calls ahead at most) apart -- except for a rig handed over as device tensors without host copies attached
+(``t._lss_host``, as simbev.finish_batch attaches them), which is read back once: pass the rig on the host.
+
+The model's parameters are moved into the Predictor's flat fp32 master (FlatParams; same values, same
+state_dict): build it on a model no training step is bound to. The hot path has no CPU fallback.
+
+    python -m lss_carla_amd.predict --modelf CKPT --dataroot ROOT --out DIR [--bsz N] [--label_groups "0;1,2,3"]
+                                    [--dtype bf16|fp32] [--graph 0|1]
+
+runs the val split through ``BatchStager`` and the Predictor and writes one uint8 mask array per sample
+(``DIR/<index>.npy``, (K, X, Y)) and ``DIR/metrics.json``: loss, IoU and per-class IoU from get_val_info's
+accumulators (``tools.val_accumulate``), and frames/s. The matplotlib figures of explore.py are not drawn.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import math
+import os
+import time
+from typing import Optional, Sequence
+
+import torch
+
+HEAD_WEIGHT = "bevencode.up2.4.weight"  # BevEncode's last conv (src/models.py:115): (outC, 128, 1, 1)
+
+
+def threshold_logit(threshold: float) -> float:
+    """The logit a probability threshold corresponds to: sigmoid(x) > t  <=>  x > log(t / (1 - t)).
+    0.5 -> 0.0 exactly, get_batch_iou's predicate (src/tools.py:232-240: ``preds > 0``)."""
+    t = float(threshold)
+    if not 0.0 < t < 1.0:
+        raise ValueError(f"threshold {threshold!r}: a probability strictly between 0 and 1")
+    return 0.0 if t == 0.5 else math.log(t / (1.0 - t))
+
+
+def model_state_dict(ckpt) -> dict:
+    """The model's state dict out of either checkpoint format: train_simbev.py's dict with
+    ``"model_state_dict"`` (train_simbev.py:206-212), or explore.py's plain ``model.state_dict()``."""
+    if isinstance(ckpt, dict) and "model_state_dict" in ckpt:
+        ckpt = ckpt["model_state_dict"]
+    if not isinstance(ckpt, dict) or not ckpt or not all(isinstance(k, str) and torch.is_tensor(v)
+                                                         for k, v in ckpt.items()):
+        raise ValueError("not a model checkpoint: neither a state_dict nor a dict holding 'model_state_dict'")
+    return ckpt
+
+
+def checkpoint_format(ckpt) -> str:
+    """'trainer' (a dict holding "model_state_dict") or 'state_dict' (the bare dict); ValueError otherwise."""
+    model_state_dict(ckpt)
+    return "trainer" if "model_state_dict" in ckpt else "state_dict"
+
+
+def check_head(sd: dict, n_out: int, what: str = "checkpoint") -> None:
+    """A state dict whose head has another number of output classes than the model cannot be loaded: say so
+    with both numbers, before anything else happens."""
+    w = sd.get(HEAD_WEIGHT)
+    if w is not None and int(w.shape[0]) != int(n_out):
+        raise RuntimeError(f"{what}: a head of {int(w.shape[0])} output classes ({HEAD_WEIGHT} {tuple(w.shape)}), "
+                           f"the model has {int(n_out)}")
+
+
+def _require_gpu(device) -> torch.device:
+    dev = torch.device(device)
+    if dev.type != "cuda" or not torch.cuda.is_available():
+        raise RuntimeError("lss_carla_amd.predict: needs an MI355X (the hot path has no CPU fallback)")
+    return dev
+
+
+class Predictor:
+    RIG = ("rots", "trans", "intrins", "post_rots", "post_trans")
+
+    def __init__(self, model: torch.nn.Module, bsz: int, device, amp_dtype: Optional[torch.dtype] = torch.bfloat16,
+                 threshold: float = 0.5, graph: bool = True, ncams: Optional[int] = None, stager=None):
+        """model: a LiftSplatShoot on `device` (memory formats as the caller set them). bsz: the static batch.
+        amp_dtype: autocast dtype (None: fp32). stager: a staging.BatchStager whose static tensors and
+        inverses to run on (``run(b)`` after its ``commit()``); None: buffers of the Predictor's own, filled by
+        ``__call__``. The graph is captured by the first call, on that call's inputs."""
+        from . import ops
+        from .flat_params import FlatParams
+
+        dev = _require_gpu(device)
+        self.logit = threshold_logit(threshold)
+        self.model, self.device, self.bsz, self.amp_dtype = model, dev, int(bsz), amp_dtype
+        self.use_graph = bool(graph)
+        conf = model.data_aug_conf
+        N = int(ncams if ncams is not None else conf.get("Ncams", 6))
+        fH, fW = (int(v) for v in conf["final_dim"])
+        self.ncams = N
+        self.n_out = int(model.state_dict()[HEAD_WEIGHT].shape[0])
+        self.stager = stager
+        if stager is not None:
+            if stager.B != self.bsz or stager.N != N or tuple(stager.final_dim) != (fH, fW):
+                raise ValueError("Predictor: the stager's batch, cameras or image size differ from the model's")
+            self.inputs = tuple(stager.inputs)
+            self.hinv = stager.hinv
+        else:
+            B = self.bsz
+            eye = torch.eye(3, device=dev).expand(B, N, 3, 3)
+            self.inputs = (torch.zeros(B, N, 3, fH, fW, device=dev), eye.clone(), torch.zeros(B, N, 3, device=dev),
+                           eye.clone(), eye.clone(), torch.zeros(B, N, 3, device=dev))
+            self.hinv = ops.HostInverses(B * N, dev)
+            # the host rig HostInverses inverts: samples past a partial batch keep their previous matrices
+            self._host_post_rots = torch.eye(3).repeat(B, N, 1, 1)
+            self._host_intrins = torch.eye(3).repeat(B, N, 1, 1)
+        was_training = model.training
+        try:
+            self.flat = FlatParams(model, cast_dtype=amp_dtype)
+            self.params = None
+            self.refresh()
+        finally:
+            model.train(was_training)
+        self.graph = None
+        self._out = None
+        self._b = 0
+
+    # ------------------------------------------------------------------ weights
+    def refresh(self) -> None:
+        """Materialise the working parameters from the module's current ones (after changing them in place)."""
+        with torch.no_grad():
+            params = self.flat.tensors()  # writes work16 / work32 (and the packed depthnet weight) in place
+        if self.params is None:
+            self.params = {k: v.detach() for k, v in params.items()}  # views of the static working buffers
+
+    def load(self, path) -> None:
+        """Load a checkpoint of either format into the module in place and refresh the working parameters; the
+        head's width is checked first (nothing is loaded, materialised or captured when it differs)."""
+        sd = model_state_dict(torch.load(path, map_location="cpu"))
+        check_head(sd, self.n_out, f"checkpoint {path}")
+        self.model.load_state_dict(sd)  # copies into the parameters (the master's memory) and the buffers
+        self.refresh()
+
+    # ------------------------------------------------------------------ forward
+    def _forward(self) -> torch.Tensor:
+        """One forward over the static inputs: eval mode, no_grad, autocast; the mode flag restored."""
+        model = self.model
+        was_training = model.training
+        saved_inv = model.static_inverses
+        model.eval()
+        model.static_inverses = (self.hinv.pinv, self.hinv.kinv)
+        try:
+            capturing = torch.cuda.is_current_stream_capturing()
+            with torch.no_grad(), torch.autocast("cuda", dtype=self.amp_dtype or torch.bfloat16,
+                                                 enabled=self.amp_dtype is not None, cache_enabled=not capturing):
+                return torch.func.functional_call(model, self.params, self.inputs, strict=False)
+        finally:
+            model.static_inverses = saved_inv
+            model.train(was_training)
+
+    def _capture(self) -> None:
+        dev = self.device
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            self._forward()  # warm-up: allocations, MIOpen's choices, the per-device workspaces
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._out = self._forward()
+        self.graph = g
+
+    def run(self, b: Optional[int] = None) -> torch.Tensor:
+        """Launch the forward over the static inputs as they are (a stager's commit() filled them and staged
+        the inverses); the first b samples' logits."""
+        b = self.bsz if b is None else int(b)
+        if not 0 < b <= self.bsz:
+            raise ValueError(f"Predictor: a batch of {b} samples against bsz={self.bsz}")
+        if not self.use_graph:
+            self._out = self._forward()
+        else:
+            if self.graph is None:
+                self._capture()
+            self.graph.replay()
+        self._b = b
+        return self._out[:b]
+
+    def __call__(self, imgs, rots, trans, intrins, post_rots, post_trans) -> torch.Tensor:
+        if self.stager is not None:
+            raise RuntimeError("Predictor: built on a stager -- stage / commit there, then run(b)")
+        b = int(imgs.shape[0])
+        if not 0 < b <= self.bsz:
+            raise ValueError(f"Predictor: a batch of {b} samples against bsz={self.bsz}")
+        for dst, src in zip(self.inputs, (imgs, rots, trans, intrins, post_rots, post_trans)):
+            if tuple(src.shape) != (b,) + tuple(dst.shape[1:]):
+                raise ValueError(f"Predictor: an input of shape {tuple(src.shape)}, expected {(b,) + tuple(dst.shape[1:])}")
+            dst[:b].copy_(src, non_blocking=True)
+        self._host_post_rots[:b].copy_(_host(post_rots))
+        self._host_intrins[:b].copy_(_host(intrins))
+        self.hinv.update(self._host_post_rots, self._host_intrins)
+        return self.run(b)
+
+    # ------------------------------------------------------------------ outputs of the last call
+    def logits(self) -> torch.Tensor:
+        if self._out is None:
+            raise RuntimeError("Predictor: no call yet")
+        return self._out[:self._b]
+
+    def probs(self) -> torch.Tensor:
+        """sigmoid of the last call's logits, fp32 (``out.sigmoid()``, src/explore.py:322)."""
+        return self.logits().float().sigmoid()
+
+    def masks(self) -> torch.Tensor:
+        """uint8 (b, K, X, Y): probability > threshold, as logits > logit(threshold)."""
+        return (self.logits() > self.logit).to(torch.uint8)
+
+
+def _host(t: torch.Tensor) -> torch.Tensor:
+    """A rig tensor's host values: itself, its attached host copy while still valid (ops.camera_inverses'
+    rule), or one device read."""
+    if not t.is_cuda:
+        return t
+    h = getattr(t, "_lss_host", None)
+    if (h is not None and tuple(h.shape) == tuple(t.shape) and not h.is_cuda
+            and getattr(t, "_lss_host_version", None) == t._version):
+        return h
+    return t.detach().cpu()
+
+
+# ---------------------------------------------------------------------- command line
+def parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(prog="python -m lss_carla_amd.predict",
+                                description="Run a trained LSS over a SimBEV val split on the MI355X: masks and metrics")
+    p.add_argument("--modelf", type=str, required=True, help="checkpoint: a state_dict or a trainer checkpoint")
+    p.add_argument("--dataroot", type=str, required=True, help="SimBEV dataset root directory")
+    p.add_argument("--out", type=str, required=True, help="directory for <index>.npy and metrics.json")
+    p.add_argument("--bsz", type=int, default=4)
+    p.add_argument("--label_groups", type=str, default=None,
+                   help='BEV channel groups, one output class each: "0;1,2,3;6,7" (default: the vehicle mask 1,2,3)')
+    p.add_argument("--pos_weight", type=str, default="2.13", help="one positive-class weight, or one per class")
+    p.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
+    p.add_argument("--graph", type=int, default=1, choices=[0, 1], help="0: the same forward, eager")
+    p.add_argument("--threshold", type=float, default=0.5)
+    p.add_argument("--gpuid", type=int, default=0)
+    p.add_argument("--nworkers", type=int, default=4)
+    p.add_argument("--H", type=int, default=224)
+    p.add_argument("--W", type=int, default=480)
+    p.add_argument("--final_h", type=int, default=128)
+    p.add_argument("--final_w", type=int, default=352)
+    p.add_argument("--miopen_find", type=int, default=1)
+    return p
+
+
+def confs(a) -> tuple:
+    """(grid_conf, data_aug_conf) of the reference's defaults (train_simbev.py:23-98) at the given sizes; the
+    val split draws no augmentation."""
+    grid_conf = {"xbound": [-50.0, 50.0, 0.5], "ybound": [-50.0, 50.0, 0.5], "zbound": [-10.0, 10.0, 20.0],
+                 "dbound": [4.0, 45.0, 1.0]}
+    data_aug_conf = {"resize_lim": (1.0, 1.0), "final_dim": (a.final_h, a.final_w), "rot_lim": (0.0, 0.0), "H": a.H,
+                     "W": a.W, "rand_flip": False, "bot_pct_lim": (0.0, 0.0), "Ncams": 6}
+    return grid_conf, data_aug_conf
+
+
+def predict(a, grid_conf=None, data_aug_conf=None, model: Optional[torch.nn.Module] = None) -> dict:
+    """The command line's work for parsed arguments `a`; returns metrics.json's dict. grid_conf / data_aug_conf
+    override the defaults of ``confs``; model: an already built (and loaded) module instead of --modelf."""
+    if a.gpuid < 0:
+        raise RuntimeError("lss_carla_amd.predict: needs an MI355X (the hot path has no CPU fallback)")
+    dev = _require_gpu(f"cuda:{a.gpuid}")
+
+    import numpy as np
+
+    import lss_carla_amd as L
+    from . import simbev, tools
+    from .staging import BatchStager
+    from .trainer import _class_setup, parse_label_groups, parse_pos_weight
+
+    torch.cuda.set_device(dev)
+    torch.backends.cudnn.benchmark = bool(a.miopen_find)
+    gc, dac = confs(a)
+    grid_conf, data_aug_conf = grid_conf or gc, data_aug_conf or dac
+    groups, K, pos_weight = _class_setup(parse_label_groups(a.label_groups), parse_pos_weight(a.pos_weight))
+    amp_dtype = torch.bfloat16 if a.dtype == "bf16" else None
+    if model is None:
+        sd = model_state_dict(torch.load(a.modelf, map_location="cpu"))
+        check_head(sd, K, f"checkpoint {a.modelf}")  # before anything is built
+        model = L.compile_model(grid_conf, data_aug_conf, outC=K).to(dev)
+        model.load_state_dict(sd)
+    model.bevencode.to(memory_format=torch.channels_last)
+    model.camencode.up1.to(memory_format=torch.channels_last)
+    _, valloader = simbev.compile_data("unused", a.dataroot, data_aug_conf, grid_conf, a.bsz, a.nworkers,
+                                       "segmentationdata", device=dev, label_groups=groups)
+    val_raw, n_val = valloader.loader, len(valloader.dataset)
+    stager = BatchStager(data_aug_conf["final_dim"], a.bsz, len(simbev.CAMERA_ORDER),
+                         (data_aug_conf["H"], data_aug_conf["W"]), grid_conf, dev, label_groups=groups)
+    p = Predictor(model, a.bsz, dev, amp_dtype=amp_dtype, threshold=a.threshold, graph=bool(a.graph), stager=stager)
+    if K > 1 or not tools.is_scalar_weight(pos_weight):
+        pos_weight = tools.class_weights(pos_weight, K, dev)
+    totals = torch.zeros(1 + 2 * K, device=dev, dtype=torch.float64)
+    os.makedirs(a.out, exist_ok=True)
+    masks, frames = [], 0
+    it = iter(val_raw)
+    nxt = next(it, None)
+    if nxt is not None:
+        stager.stage(nxt)
+    torch.cuda.synchronize(dev)
+    t0 = None
+    while nxt is not None:
+        b = stager.commit()
+        logits = p.run(b)  # (the first call captures the graph: timed from the second batch on)
+        tools.val_accumulate(p._out, stager.binimgs, totals, n_valid=stager.n_valid, pos_weight=pos_weight)
+        masks.append(p.masks())  # a fresh tensor per batch; the logits are static
+        nxt = next(it, None)
+        if nxt is not None:
+            stager.stage(nxt)
+        if t0 is None:
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+        else:
+            frames += b
+    torch.cuda.synchronize(dev)
+    elapsed = time.perf_counter() - t0 if t0 is not None else 0.0
+    index = 0
+    for m in masks:
+        for s in m.cpu().numpy():
+            np.save(os.path.join(a.out, f"{index}.npy"), s)
+            index += 1
+    t = totals.tolist()
+    info = {"loss": t[0] / n_val, **tools.iou_summary(t[1:1 + K], t[1 + K:1 + 2 * K]),
+            "intersection": t[1:1 + K], "union": t[1 + K:1 + 2 * K], "samples": index, "classes": K,
+            "dtype": a.dtype, "graph": bool(a.graph), "bsz": a.bsz,
+            "frames_per_s": frames / elapsed if frames and elapsed > 0 else None}
+    with open(os.path.join(a.out, "metrics.json"), "w") as f:
+        json.dump(info, f, indent=1)
+    return info
+
+
+def main(argv: Optional[Sequence[str]] = None) -> dict:
+    a = parser().parse_args(argv)
+    info = predict(a)
+    print(json.dumps(info))
+    return info
+
+
+if __name__ == "__main__":
+    main()

@@ -24,6 +24,12 @@ Steps:
                                       written to a temporary directory): frames/s of (a) the loop with 14 loader
                                       workers, (b) the loop cycling pre-decoded host batches, (c) bench.py's default,
                                       (d) bench.py --caller reference, in train_loop.json
+  infer[:PARENT_DIR]                  the eval-mode forward with and without the lss_bn_eval path: bench.py --config c2
+                                      on a checkout of the parent commit (PARENT_DIR, library built there) and on this
+                                      tree alternately, three runs each, and --hip-bn 0 here; scripts/infer_ab.py (the
+                                      Predictor at c3 sizes, norm.USE_HIP_BN_EVAL on / off alternately, bsz 8 and 1); the
+                                      default training line on each side; kernel traces of the Predictor, switch on and
+                                      off, in runs of their own: infer.json, infer_kernels.txt
   lib:VARIANT                         later steps load lss-carla_amd/variants/VARIANT.so (product: the default)
 """
 from __future__ import annotations
@@ -240,6 +246,99 @@ def step_train_loop(out, spec):
     return 0
 
 
+def _bench_value(cmd, log, cwd, limit=600):
+    import json
+    rc = run(cmd, log, limit, cwd=cwd)
+    last = tail(log, 1).strip()
+    if rc != 0 or not last.startswith("{"):
+        print(tail(log, 15), flush=True)
+        return rc or 1, None
+    got = json.loads(last)
+    return 0, {"value": got.get("value"), "unit": got.get("unit"), "ms_per_step": got.get("ms_per_step")}
+
+
+def step_infer(out, spec):
+    """infer:PARENT_DIR -- the eval-mode forward before and after the lss_bn_eval path, in one session: bench.py
+    --config c2 (fp32 forward, the project's own line) on a checkout of the parent commit (PARENT_DIR, with its own
+    build of the library) and on this tree alternately, three runs each, and --hip-bn 0 on this tree; the Predictor
+    at c3 sizes with norm.USE_HIP_BN_EVAL on / off alternately (scripts/infer_ab.py, bsz 8 and 1); the default
+    training line once on each side; then rocprofv3 --kernel-trace --stats runs of their own, switch on and off.
+    Writes infer.json and infer_kernels.txt."""
+    import json
+    parent = os.path.abspath(spec) if spec else None
+    result = {"c2": {"parent": [], "this": []}, "predictor": {}, "train_default": {}}
+    sides = ([("parent", parent)] if parent else []) + [("this", REPO)]
+    for i in range(3):
+        for side, cwd in sides:
+            rc, got = _bench_value([PY, "-u", "bench.py", "--config", "c2"], os.path.join(out, f"c2_{side}_{i}.log"), cwd)
+            if rc != 0:
+                return rc
+            result["c2"][side].append(got)
+            print(f"  c2 {side} {i}: {got}", flush=True)
+    rc, got = _bench_value([PY, "-u", "bench.py", "--config", "c2", "--hip-bn", "0"], os.path.join(out, "c2_hip_bn_0.log"), REPO)
+    if rc != 0:
+        return rc
+    result["c2"]["this_hip_bn_0"] = got
+    print(f"  c2 this --hip-bn 0: {got}", flush=True)
+    for bsz in (8, 1):
+        log = os.path.join(out, f"predictor_bsz{bsz}.log")
+        rc = run([PY, "-u", os.path.join("scripts", "infer_ab.py"), "--bsz", str(bsz), "--frames", "400", "--legs", "3"],
+                 log, 600)
+        last = tail(log, 1).strip()
+        if rc != 0 or not last.startswith("{"):
+            print(tail(log, 15), flush=True)
+            return rc or 1
+        result["predictor"][f"bsz{bsz}"] = json.loads(last)
+        print(f"  predictor bsz {bsz}: {last}", flush=True)
+    for side, cwd in sides:
+        rc, got = _bench_value([PY, "-u", "bench.py"], os.path.join(out, f"train_{side}.log"), cwd)
+        if rc != 0:
+            return rc
+        result["train_default"][side] = got
+        print(f"  default training line, {side}: {got}", flush=True)
+    # kernel traces, each in a run of its own: launches and time per forward by kernel class
+    replays = 20
+    classes = (("k_bn_eval*", re.compile(r"k_bn_eval")), ("stock batch norm", re.compile(r"(?i)batch_?norm|BatchNorm")),
+               ("elementwise", re.compile(r"(?i)elementwise")), ("everything else", re.compile(r"")))
+    n = replays + 2
+    lines = [f"# rocprofv3 --kernel-trace --stats over scripts/infer_ab.py --bsz 8 --only on|off --calls {replays}: one eager "
+             f"warm-up forward, the first call's replay and {replays} more = {n} forwards (plus the Predictor's construction "
+             f"and the input copies of each call: a few launches); per forward = totals / {n}"]
+    result["kernels"] = {}
+    for sw in ("on", "off"):
+        d = f"/tmp/measure_infer_{sw}"
+        shutil.rmtree(d, ignore_errors=True)
+        rc = run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "run", "--", PY, "-u",
+                  os.path.join(REPO, "scripts", "infer_ab.py"), "--bsz", "8", "--only", sw, "--calls", str(replays)],
+                 os.path.join(out, f"trace_{sw}.log"), 600, env=prof_env(), cwd="/tmp")
+        st = (glob.glob(f"{d}/**/run_kernel_stats.csv", recursive=True) or [None])[0]
+        if rc != 0 or not st:
+            print(tail(os.path.join(out, f"trace_{sw}.log"), 15), flush=True)
+            return rc or 1
+        shutil.copy(st, os.path.join(out, f"infer_{sw}_kernel_stats.csv"))
+        tot = collections.OrderedDict((name, [0, 0.0]) for name, _ in classes)
+        for r in csv.DictReader(open(st)):
+            name = next(n for n, pat in classes if pat.search(r["Name"]))
+            tot[name][0] += int(r["Calls"])
+            tot[name][1] += float(r["TotalDurationNs"]) / 1e3
+        lines.append(f"USE_HIP_BN_EVAL {sw}")
+        result["kernels"][sw] = {}
+        for name, (calls, us) in tot.items():
+            lines.append(f"   {name:18s} {calls / n:8.1f} launches / forward   {us / n:10.1f} us / forward")
+            result["kernels"][sw][name] = {"launches_per_forward": round(calls / n, 1), "us_per_forward": round(us / n, 1)}
+        all_calls, all_us = sum(c for c, _ in tot.values()), sum(u for _, u in tot.values())
+        lines.append(f"   {'total':18s} {all_calls / n:8.1f} launches / forward   {all_us / n:10.1f} us / forward")
+        result["kernels"][sw]["total"] = {"launches_per_forward": round(all_calls / n, 1), "us_per_forward": round(all_us / n, 1)}
+        shutil.rmtree(d, ignore_errors=True)
+    with open(os.path.join(out, "infer_kernels.txt"), "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    with open(os.path.join(out, "infer.json"), "w") as fh:
+        json.dump(result, fh, indent=1)
+        fh.write("\n")
+    print("\n".join(lines), flush=True)
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tag", required=True)
@@ -249,7 +348,7 @@ def main():
     os.makedirs(out, exist_ok=True)
     os.chdir(REPO)
     fns = {"tests": step_tests, "smoke": step_smoke, "bench": step_bench, "trace": step_trace, "pmc": step_pmc,
-           "kbench": step_kbench, "py": step_py, "train_loop": step_train_loop}
+           "kbench": step_kbench, "py": step_py, "train_loop": step_train_loop, "infer": step_infer}
     for s in a.steps:
         kind, _, spec = s.partition(":")
         print(f"== {s}", flush=True)

@@ -221,6 +221,37 @@ int lss_bce_iou_accum_pc(const void* x, int32_t dtype, const float* target, int6
                          void* partial, void* stream);
 int64_t lss_bce_iou_pc_partial_bytes(int64_t n, int32_t K);
 
+/* (ABI 29) Focal loss for imbalanced classes, loss and input gradient in one pass. params: K x 3 fp32 in DEVICE
+ * memory, row k = (w_pos, w_neg, gamma) of class k = (i / plane) % K (a captured graph replays with the current
+ * values). Labels are hard, q = (t != 0). With softplus(z) = log1p(exp(-|z|)) + max(z, 0) and p = sigmoid(x):
+ *   q = 1:  l = exp(-gamma softplus(x)) w_pos softplus(-x),
+ *           dl/dx = -exp(-gamma softplus(x)) w_pos (gamma p softplus(-x) + sigmoid(-x))
+ *   q = 0:  l = exp(-gamma softplus(-x)) w_neg softplus(x),
+ *           dl/dx = exp(-gamma softplus(-x)) w_neg (gamma sigmoid(-x) softplus(x) + p)
+ * i.e. (1 - p_t)^gamma times the weighted BCE, the power written as exp(gamma log(1 - p_t)): no division and no
+ * difference of near-equal terms, so 0 < gamma < 1 is finite at saturated logits. (pw, 1, 0) is lss_bce_logits_pc's
+ * loss for hard labels; focal(alpha, gamma) is (alpha, 1 - alpha, gamma). loss[0] = mean over the n elements,
+ * grad = dl/dx / n in the logits' type (rounded once). Otherwise lss_bce_logits_pc's contract: fp32 arithmetic,
+ * x / grad / target 16-B aligned, partial = lss_bce_partials(n) fp32, fixed-order folds (two runs give equal
+ * bits), two launches. K = 1: plane = the elements of a sample. The backward is lss_bce_logits_bwd. */
+int lss_focal_logits_pc(const void* x, int32_t dtype, const float* target, int64_t n, int64_t plane, int32_t K,
+                        const float* params, float* partial, float* loss, void* grad, void* stream);
+/* (ABI 29) Validation in one pass for either loss and a ladder of thresholds: thetas = T ascending fp32 logit
+ * thresholds in device memory (1 <= T <= 16), params as above (K <= 32, per_sample = K * plane). Over the first
+ * n_valid[0] samples (as lss_bce_iou_accum), for class k and threshold j, compared in fp32 with a strict >:
+ *   P_k = #(t != 0),  TP_kj = #(x > theta_j and t != 0),  PP_kj = #(x > theta_j)
+ * totals (1 + K + 2 K T doubles in device memory, +=):
+ *   [0] the sum of lss_focal_logits_pc's per-element l (fp64) / per_sample,  [1 + k] P_k,
+ *   [1 + K + k T + j] TP_kj,  [1 + K + K T + k T + j] PP_kj
+ * so the intersection at j is TP and the union PP + P - TP. Counts are exact integers. partial:
+ * lss_seg_metrics_partial_bytes(batch * per_sample, K, T) bytes (0 for sizes out of range), 8-B aligned. Each element
+ * adds one to its block's histogram over (class, #thresholds below x, label); the fold kernel takes suffix sums.
+ * Two launches, no host read, capturable; one captured launch serves any n_valid. */
+int lss_seg_metrics_accum(const void* x, int32_t dtype, const float* target, int64_t per_sample, int32_t batch,
+                          const int32_t* n_valid, int64_t plane, int32_t K, const float* params, const float* thetas,
+                          int32_t T, double* totals, void* partial, void* stream);
+int64_t lss_seg_metrics_partial_bytes(int64_t n, int32_t K, int32_t T);
+
 /* out[c] = sum over (n, pixel) of x[n][c][pixel] (fp32, fixed order), x (N, C, HW) NCHW fp32 or bf16: the
  * bias gradient of the fused lift's depthnet conv (src/models.py:47) from d(logits). One launch. */
 int lss_channel_sums(const void* x, int32_t dtype, int32_t N, int32_t C, int32_t HW, float* out, void* stream);

@@ -18,7 +18,7 @@ DEBUG_LIB_PATH = os.path.join(_HERE, "liblss_hip_debug.so")  # LSS_DEBUG=1: devi
 
 F32, BF16 = 0, 1
 NCHW, NHWC = 0, 1
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 
 class Dims(ctypes.Structure):
@@ -110,6 +110,10 @@ SIGNATURES = {
     "lss_bce_iou_accum_pc": (ctypes.c_int, [_p, _i32, _p, ctypes.c_int64, _i32, _p, ctypes.c_int64, _i32, _p, _p, _p,
                                             _p]),
     "lss_bce_iou_pc_partial_bytes": (ctypes.c_int64, [ctypes.c_int64, _i32]),
+    "lss_focal_logits_pc": (ctypes.c_int, [_p, _i32, _p, ctypes.c_int64, ctypes.c_int64, _i32, _p, _p, _p, _p, _p]),
+    "lss_seg_metrics_accum": (ctypes.c_int, [_p, _i32, _p, ctypes.c_int64, _i32, _p, ctypes.c_int64, _i32, _p, _p,
+                                             _i32, _p, _p, _p]),
+    "lss_seg_metrics_partial_bytes": (ctypes.c_int64, [ctypes.c_int64, _i32, _i32]),
     "lss_bn_bwd_rank1": (ctypes.c_int, [_p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _i32, _i32, _p, _p, _p, _p, _p,
                                         _p]),
     "lss_scale_add": (ctypes.c_int, [_p, _p, ctypes.c_float, _p, ctypes.c_int64, ctypes.c_int64, _p, _p]),

@@ -379,6 +379,184 @@ __global__ __launch_bounds__(kBlock) void k_bce_iou_fold_pc(const double* __rest
     }
 }
 
+// ---- Focal loss (ABI 29) for imbalanced classes: per element, with q = (t != 0) (the IoU predicate's reading of
+// a label), z = q ? x : -x (so p_t = sigmoid(z)) and the class's row (w_pos, w_neg, gamma) of params,
+//   l = exp(-gamma softplus(z)) w softplus(-z),   dl/dz = -exp(-gamma softplus(z)) w (gamma sigmoid(z) softplus(-z) + sigmoid(-z)),
+// w = q ? w_pos : w_neg and dl/dx = q ? dl/dz : -dl/dz: (1 - p_t)^gamma times the weighted BCE with the power written
+// as exp(gamma log(1 - p_t)), so the gradient has no division and no difference of near-equal terms (0 < gamma < 1
+// at a saturated, correct element is 0, not inf * 0). softplus(z) = log1p(exp(-|x|)) + max(z, 0); the sigmoids are
+// k_bce_fwd's. Partition, loads, stores and folds are k_bce_fwd_pc's; gamma = 0 with (pw, 1) is SimpleLoss(pw).
+struct FocalTerm {
+    float l, g;  // the loss term and dl/dx
+};
+__device__ __forceinline__ FocalTerm focal_term(float xx, float tt, float wp, float wn, float gamma) {
+    const bool q = tt != 0.f;
+    const float z = q ? xx : -xx;
+    const float e = expf(-fabsf(xx));
+    const float lp = log1pf(e);
+    const float spz = lp + fmaxf(z, 0.f), spm = lp + fmaxf(-z, 0.f);  // softplus(z), softplus(-z)
+    const float sp = 1.f / (1.f + e), sn = e / (1.f + e);             // sigmoid(|x|), sigmoid(-|x|)
+    const float sz = z >= 0.f ? sp : sn, sm = z >= 0.f ? sn : sp;     // sigmoid(z), sigmoid(-z)
+    const float mw = expf(-gamma * spz) * (q ? wp : wn);
+    const float gz = mw * (gamma * sz * spm + sm);  // -dl/dz
+    return {mw * spm, q ? -gz : gz};
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_focal_fwd_pc(const T* __restrict__ x, const float* __restrict__ t,
+                                                         long long n, long long plane, int K,
+                                                         const float* __restrict__ params, float inv_n,
+                                                         float* __restrict__ partial, T* __restrict__ grad) {
+    __shared__ float s_w[kBlock / kWave];
+    const long long i0 = ((long long)blockIdx.x * kBlock + threadIdx.x) * kBceVpt;
+    float xv[kBceVpt], tv[kBceVpt], gv[kBceVpt];
+    const bool full = i0 + kBceVpt <= n;
+    if (full) {
+        ldv<8>(x + i0, xv);
+        const float4 a = *reinterpret_cast<const float4*>(t + i0), b = *reinterpret_cast<const float4*>(t + i0 + 4);
+        tv[0] = a.x; tv[1] = a.y; tv[2] = a.z; tv[3] = a.w; tv[4] = b.x; tv[5] = b.y; tv[6] = b.z; tv[7] = b.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < kBceVpt; ++j) {
+            xv[j] = i0 + j < n ? ld(x + i0 + j) : 0.f;
+            tv[j] = i0 + j < n ? t[i0 + j] : 0.f;
+        }
+    }
+    ClassWalk cw(i0, plane, K);
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < kBceVpt; ++j) {
+        const float* pr = params + 3 * cw.k;
+        const float wp = pr[0], wn = pr[1], gamma = pr[2];
+        cw.next();
+        const FocalTerm f = focal_term(xv[j], tv[j], wp, wn, gamma);
+        gv[j] = f.g * inv_n;
+        if (i0 + j < n) s += f.l;
+    }
+    if (full) stv<8>(grad + i0, gv);
+    else {
+#pragma unroll
+        for (int j = 0; j < kBceVpt; ++j)
+            if (i0 + j < n) st(grad + i0 + j, gv[j]);
+    }
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, kWave);
+    if ((threadIdx.x & (kWave - 1)) == 0) s_w[threadIdx.x / kWave] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float b = 0.f;
+#pragma unroll
+        for (int w = 0; w < kBlock / kWave; ++w) b += s_w[w];
+        partial[blockIdx.x] = b;
+    }
+}
+
+// ---- Validation for either loss and a ladder of T ascending logit thresholds, one pass (ABI 29). Since theta
+// ascends, x > theta_j holds exactly for j < bin(x) = #(j: x > theta_j): an element adds one to the block's LDS
+// histogram h[class][bin][q], q = (t != 0), and the fold kernel turns the histograms into the counts by suffix sums:
+//   P_k = sum_b h[k][b][1],  TP_kj = sum_{b > j} h[k][b][1],  PP_kj = sum_{b > j} (h[k][b][0] + h[k][b][1]).
+// Block record: partial = nb doubles (the loss terms of focal_term, summed in fp64 as k_bce_iou_pc sums its own), then
+// nb x K (T + 1) 2 int32. n_valid masking, partition and loads are k_bce_iou_pc's.
+constexpr int kSegMaxThresholds = 16;
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_seg_metrics(const T* __restrict__ x, const float* __restrict__ t,
+                                                        long long per_sample, int batch, const int* __restrict__ n_valid,
+                                                        long long plane, int K, const float* __restrict__ params,
+                                                        const float* __restrict__ thetas, int nt, int vec,
+                                                        double* __restrict__ ploss, int* __restrict__ pcount) {
+    __shared__ double s_l[kBlock / kWave];
+    __shared__ int s_h[kIouMaxClasses * (kSegMaxThresholds + 1) * 2];
+    __shared__ float s_th[kSegMaxThresholds];
+    const int nh = K * (nt + 1) * 2;
+    for (int c = threadIdx.x; c < nh; c += kBlock) s_h[c] = 0;
+    if (threadIdx.x < nt) s_th[threadIdx.x] = thetas[threadIdx.x];
+    __syncthreads();
+    int nv = n_valid ? n_valid[0] : batch;
+    nv = nv < 0 ? 0 : (nv > batch ? batch : nv);
+    const long long limit = (long long)nv * per_sample;
+    const long long i0 = ((long long)blockIdx.x * kBlock + threadIdx.x) * kBceVpt;
+    double s = 0.0;
+    if (i0 < limit) {
+        float xv[kBceVpt], tv[kBceVpt];
+        if (vec && i0 + kBceVpt <= limit) {
+            ldv<8>(x + i0, xv);
+            const float4 a = *reinterpret_cast<const float4*>(t + i0), b = *reinterpret_cast<const float4*>(t + i0 + 4);
+            tv[0] = a.x; tv[1] = a.y; tv[2] = a.z; tv[3] = a.w; tv[4] = b.x; tv[5] = b.y; tv[6] = b.z; tv[7] = b.w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < kBceVpt; ++j) {
+                xv[j] = i0 + j < limit ? ld(x + i0 + j) : 0.f;
+                tv[j] = i0 + j < limit ? t[i0 + j] : 0.f;
+            }
+        }
+        ClassWalk cw(i0, plane, K);
+#pragma unroll
+        for (int j = 0; j < kBceVpt; ++j) {
+            const float xx = xv[j], tt = tv[j];
+            const int k = cw.k;
+            const float* pr = params + 3 * k;
+            const float wp = pr[0], wn = pr[1], gamma = pr[2];
+            cw.next();
+            const FocalTerm f = focal_term(xx, tt, wp, wn, gamma);
+            if (i0 + j < limit) {
+                s += (double)f.l;
+                int bin = 0;
+                for (int m = 0; m < nt; ++m) bin += xx > s_th[m] ? 1 : 0;
+                atomicAdd(&s_h[(k * (nt + 1) + bin) * 2 + (tt != 0.f ? 1 : 0)], 1);
+            }
+        }
+    }
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, kWave);
+    if ((threadIdx.x & (kWave - 1)) == 0) s_l[threadIdx.x / kWave] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double l = 0.0;
+#pragma unroll
+        for (int w = 0; w < kBlock / kWave; ++w) l += s_l[w];
+        ploss[blockIdx.x] = l;
+    }
+    for (int c = threadIdx.x; c < nh; c += kBlock) pcount[(size_t)blockIdx.x * nh + c] = s_h[c];
+}
+
+// totals[0] += the loss records folded as k_bce_iou_fold_pc folds them; the histograms are summed over the blocks
+// (integers) into LDS, then totals[1 + k] += P_k, totals[1 + K + k T + j] += TP_kj, totals[1 + K + K T + k T + j] += PP_kj.
+__global__ __launch_bounds__(kBlock) void k_seg_metrics_fold(const double* __restrict__ ploss,
+                                                             const int* __restrict__ pcount, int nb, int K, int nt,
+                                                             double per_sample, double* __restrict__ totals) {
+    __shared__ double s_l[kBlock / kWave];
+    __shared__ long long s_h[kIouMaxClasses * (kSegMaxThresholds + 1) * 2];
+    double s = 0.0;
+    for (int b = threadIdx.x; b < nb; b += kBlock) s += ploss[b];
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, kWave);
+    if ((threadIdx.x & (kWave - 1)) == 0) s_l[threadIdx.x / kWave] = s;
+    const int nh = K * (nt + 1) * 2;
+    for (int c = threadIdx.x; c < nh; c += kBlock) {
+        long long a = 0;
+        for (int b = 0; b < nb; ++b) a += pcount[(size_t)b * nh + c];
+        s_h[c] = a;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double l = 0.0;
+#pragma unroll
+        for (int w = 0; w < kBlock / kWave; ++w) l += s_l[w];
+        totals[0] += l / per_sample;
+    }
+    for (int c = threadIdx.x; c < K + 2 * K * nt; c += kBlock) {
+        long long a = 0;
+        if (c < K) {
+            for (int b = 0; b <= nt; ++b) a += s_h[(c * (nt + 1) + b) * 2 + 1];
+        } else {
+            const int r = c - K, pp = r >= K * nt, kj = pp ? r - K * nt : r, k = kj / nt, j = kj - k * nt;
+            for (int b = j + 1; b <= nt; ++b)
+                a += s_h[(k * (nt + 1) + b) * 2 + 1] + (pp ? s_h[(k * (nt + 1) + b) * 2] : 0);
+        }
+        totals[1 + c] += (double)a;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -502,6 +680,63 @@ int lss_bce_iou_accum_pc(const void* x, int32_t dtype, const float* target, int6
                            vec, pl, pc);
     hipLaunchKernelGGL(k_bce_iou_fold_pc, dim3(1), dim3(kBlock), 0, s, (const double*)pl, (const int*)pc, (int)nb, (int)K,
                        (double)per_sample, totals);
+    return launch_status();
+}
+
+int lss_focal_logits_pc(const void* x, int32_t dtype, const float* target, int64_t n, int64_t plane, int32_t K,
+                        const float* params, float* partial, float* loss, void* grad, void* stream) {
+    const int esz = dtype == LSS_CONV_BF16 ? 2 : dtype == LSS_CONV_F32 ? 4 : 0;
+    if (!x || !target || !params || !partial || !loss || !grad || !esz || n <= 0 || plane <= 0 || K <= 0 ||
+        ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(grad)) & 15) ||
+        (reinterpret_cast<uintptr_t>(target) & 15) || (reinterpret_cast<uintptr_t>(params) & 3))
+        return LSS_CONV_EINVAL;
+    const long long nb = (n + (long long)kBlock * kBceVpt - 1) / ((long long)kBlock * kBceVpt);
+    if (nb > INT_MAX) return LSS_CONV_EINVAL;
+    const float inv_n = 1.0f / (float)n;
+    hipStream_t s = (hipStream_t)stream;
+    if (esz == 2)
+        hipLaunchKernelGGL(k_focal_fwd_pc<bf16>, dim3((unsigned)nb), dim3(kBlock), 0, s, (const bf16*)x, target,
+                           (long long)n, (long long)plane, (int)K, params, inv_n, partial, (bf16*)grad);
+    else
+        hipLaunchKernelGGL(k_focal_fwd_pc<float>, dim3((unsigned)nb), dim3(kBlock), 0, s, (const float*)x, target,
+                           (long long)n, (long long)plane, (int)K, params, inv_n, partial, (float*)grad);
+    hipLaunchKernelGGL(k_bce_total, dim3(1), dim3(kWave), 0, s, partial, (int)nb, inv_n, loss);
+    return launch_status();
+}
+
+int64_t lss_seg_metrics_partial_bytes(int64_t n, int32_t K, int32_t T) {
+    return n <= 0 || K <= 0 || K > kIouMaxClasses || T <= 0 || T > kSegMaxThresholds
+               ? 0
+               : lss_bce_partials(n) * (int64_t)(sizeof(double) + 2 * (size_t)K * (size_t)(T + 1) * sizeof(int));
+}
+
+int lss_seg_metrics_accum(const void* x, int32_t dtype, const float* target, int64_t per_sample, int32_t batch,
+                          const int32_t* n_valid, int64_t plane, int32_t K, const float* params, const float* thetas,
+                          int32_t T, double* totals, void* partial, void* stream) {
+    const int esz = dtype == LSS_CONV_BF16 ? 2 : dtype == LSS_CONV_F32 ? 4 : 0;
+    if (!x || !target || !params || !thetas || !totals || !partial || !esz || per_sample <= 0 || batch <= 0 ||
+        plane <= 0 || K <= 0 || K > kIouMaxClasses || T <= 0 || T > kSegMaxThresholds || per_sample != plane * K ||
+        per_sample > LLONG_MAX / batch || (reinterpret_cast<uintptr_t>(partial) & 7) ||
+        (reinterpret_cast<uintptr_t>(totals) & 7) ||
+        ((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(thetas)) & 3))
+        return LSS_CONV_EINVAL;
+    const long long n = (long long)per_sample * batch;
+    const long long nb = (n + (long long)kBlock * kBceVpt - 1) / ((long long)kBlock * kBceVpt);
+    if (nb > INT_MAX) return LSS_CONV_EINVAL;
+    const int vec = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(target)) & 15) == 0;
+    hipStream_t s = (hipStream_t)stream;
+    double* pl = (double*)partial;
+    int* pc = (int*)(pl + nb);
+    if (esz == 2)
+        hipLaunchKernelGGL(k_seg_metrics<bf16>, dim3((unsigned)nb), dim3(kBlock), 0, s, (const bf16*)x, target,
+                           (long long)per_sample, (int)batch, (const int*)n_valid, (long long)plane, (int)K, params,
+                           thetas, (int)T, vec, pl, pc);
+    else
+        hipLaunchKernelGGL(k_seg_metrics<float>, dim3((unsigned)nb), dim3(kBlock), 0, s, (const float*)x, target,
+                           (long long)per_sample, (int)batch, (const int*)n_valid, (long long)plane, (int)K, params,
+                           thetas, (int)T, vec, pl, pc);
+    hipLaunchKernelGGL(k_seg_metrics_fold, dim3(1), dim3(kBlock), 0, s, (const double*)pl, (const int*)pc, (int)nb,
+                       (int)K, (int)T, (double)per_sample, totals);
     return launch_status();
 }
 

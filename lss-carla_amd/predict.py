@@ -24,11 +24,15 @@ The model's parameters are moved into the Predictor's flat fp32 master (FlatPara
 state_dict): build it on a model no training step is bound to. The hot path has no CPU fallback.
 
     python -m lss_carla_amd.predict --modelf CKPT --dataroot ROOT --out DIR [--bsz N] [--label_groups "0;1,2,3"]
-                                    [--dtype bf16|fp32] [--graph 0|1]
+                                    [--dtype bf16|fp32] [--graph 0|1] [--threshold 0.5 | 0.45,0.5,0.35]
+                                    [--loss bce|focal] [--focal_gamma G] [--focal_alpha A] [--iou_thresholds 0.35,...]
 
 runs the val split through ``BatchStager`` and the Predictor and writes one uint8 mask array per sample
 (``DIR/<index>.npy``, (K, X, Y)) and ``DIR/metrics.json``: loss, IoU and per-class IoU from get_val_info's
-accumulators (``tools.val_accumulate``), and frames/s. The matplotlib figures of explore.py are not drawn.
+accumulators (``tools.val_accumulate``), and frames/s. ``--threshold`` takes one probability or one per class.
+With ``--loss focal`` or ``--iou_thresholds`` the totals come from ``tools.seg_metrics_accumulate`` instead: the loss
+is the chosen one (``loss_kind``), the IoU keys are the 0.5 column's, and a ladder adds ``iou_at``,
+``iou_max_per_class``, ``best_threshold_per_class`` and ``iou_max``. The matplotlib figures of explore.py are not drawn.
 """
 from __future__ import annotations
 
@@ -90,8 +94,11 @@ class Predictor:
     RIG = ("rots", "trans", "intrins", "post_rots", "post_trans")
 
     def __init__(self, model: torch.nn.Module, bsz: int, device, amp_dtype: Optional[torch.dtype] = torch.bfloat16,
-                 threshold: float = 0.5, graph: bool = True, ncams: Optional[int] = None, stager=None):
+                 threshold=0.5, graph: bool = True, ncams: Optional[int] = None, stager=None):
         """model: a LiftSplatShoot on `device` (memory formats as the caller set them). bsz: the static batch.
+        threshold: one probability, or one per output class (a sequence of K: e.g. the
+        ``best_threshold_per_class`` of a validation over a ladder; ``masks()`` then compares in fp32 with the
+        K logit thresholds, the predicate ``lss_seg_metrics_accum`` counts with).
         amp_dtype: autocast dtype (None: fp32). stager: a staging.BatchStager whose static tensors and
         inverses to run on (``run(b)`` after its ``commit()``); None: buffers of the Predictor's own, filled by
         ``__call__``. The graph is captured by the first call, on that call's inputs."""
@@ -99,7 +106,9 @@ class Predictor:
         from .flat_params import FlatParams
 
         dev = _require_gpu(device)
-        self.logit = threshold_logit(threshold)
+        per_class = not isinstance(threshold, (int, float)) and getattr(threshold, "ndim", None) != 0
+        self.logit = None if per_class else threshold_logit(threshold)
+        self.thetas = None
         self.model, self.device, self.bsz, self.amp_dtype = model, dev, int(bsz), amp_dtype
         self.use_graph = bool(graph)
         conf = model.data_aug_conf
@@ -107,6 +116,11 @@ class Predictor:
         fH, fW = (int(v) for v in conf["final_dim"])
         self.ncams = N
         self.n_out = int(model.state_dict()[HEAD_WEIGHT].shape[0])
+        if per_class:
+            logits = [threshold_logit(v) for v in threshold]
+            if len(logits) != self.n_out:
+                raise ValueError(f"Predictor: {len(logits)} thresholds for {self.n_out} output classes")
+            self.thetas = torch.tensor(logits, device=dev, dtype=torch.float32)
         self.stager = stager
         if stager is not None:
             if stager.B != self.bsz or stager.N != N or tuple(stager.final_dim) != (fH, fW):
@@ -220,7 +234,9 @@ class Predictor:
         return self.logits().float().sigmoid()
 
     def masks(self) -> torch.Tensor:
-        """uint8 (b, K, X, Y): probability > threshold, as logits > logit(threshold)."""
+        """uint8 (b, K, X, Y): probability > threshold, as logits > logit(threshold) (per class: in fp32)."""
+        if self.thetas is not None:
+            return (self.logits().float() > self.thetas.view(-1, 1, 1)).to(torch.uint8)
         return (self.logits() > self.logit).to(torch.uint8)
 
 
@@ -237,6 +253,17 @@ def _host(t: torch.Tensor) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------- command line
+def threshold_arg(text):
+    """``--threshold 0.5`` -> 0.5; ``--threshold 0.5,0.4,0.35`` -> [0.5, 0.4, 0.35] (one per class)."""
+    try:
+        vals = [float(v) for v in str(text).split(",") if v.strip()]
+    except ValueError:
+        vals = []
+    if not vals:
+        raise argparse.ArgumentTypeError(f"--threshold {text!r}: a probability, or a comma list of one per class")
+    return vals[0] if len(vals) == 1 else vals
+
+
 def parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="python -m lss_carla_amd.predict",
                                 description="Run a trained LSS over a SimBEV val split on the MI355X: masks and metrics")
@@ -246,10 +273,18 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--bsz", type=int, default=4)
     p.add_argument("--label_groups", type=str, default=None,
                    help='BEV channel groups, one output class each: "0;1,2,3;6,7" (default: the vehicle mask 1,2,3)')
-    p.add_argument("--pos_weight", type=str, default="2.13", help="one positive-class weight, or one per class")
+    p.add_argument("--pos_weight", type=str, default=None,
+                   help="one positive-class weight, or one per class (default 2.13; with --loss focal: w_pos, default 1)")
+    p.add_argument("--loss", default="bce", choices=["bce", "focal"], help="the loss metrics.json reports")
+    p.add_argument("--focal_gamma", type=str, default="2.0", help="focal loss: one gamma, or one per class")
+    p.add_argument("--focal_alpha", type=str, default=None,
+                   help="focal loss: one alpha in (0, 1), or one per class (instead of --pos_weight)")
+    p.add_argument("--iou_thresholds", type=str, default=None,
+                   help="also report the IoU at these probability thresholds: 0.35,0.4,0.45,0.5,0.55,0.6,0.65")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     p.add_argument("--graph", type=int, default=1, choices=[0, 1], help="0: the same forward, eager")
-    p.add_argument("--threshold", type=float, default=0.5)
+    p.add_argument("--threshold", type=threshold_arg, default=0.5,
+                   help="the masks' probability threshold, or one per class: 0.5,0.4,0.35")
     p.add_argument("--gpuid", type=int, default=0)
     p.add_argument("--nworkers", type=int, default=4)
     p.add_argument("--H", type=int, default=224)
@@ -282,13 +317,25 @@ def predict(a, grid_conf=None, data_aug_conf=None, model: Optional[torch.nn.Modu
     import lss_carla_amd as L
     from . import simbev, tools
     from .staging import BatchStager
-    from .trainer import _class_setup, parse_label_groups, parse_pos_weight
+    from .trainer import _class_setup, _loss_setup, parse_label_groups, parse_per_class, parse_thresholds
 
     torch.cuda.set_device(dev)
     torch.backends.cudnn.benchmark = bool(a.miopen_find)
     gc, dac = confs(a)
     grid_conf, data_aug_conf = grid_conf or gc, data_aug_conf or dac
-    groups, K, pos_weight = _class_setup(parse_label_groups(a.label_groups), parse_pos_weight(a.pos_weight))
+    loss_kind = getattr(a, "loss", "bce")
+    pw_arg = getattr(a, "pos_weight", None)
+    pos_weight, focal = _loss_setup(loss_kind, None if pw_arg is None else parse_per_class(pw_arg, "--pos_weight"),
+                                    parse_per_class(getattr(a, "focal_gamma", "2.0"), "--focal_gamma"),
+                                    None if getattr(a, "focal_alpha", None) is None
+                                    else parse_per_class(a.focal_alpha, "--focal_alpha"))
+    ladder = parse_thresholds(getattr(a, "iou_thresholds", None))
+    threshold = threshold_arg(a.threshold) if isinstance(a.threshold, str) else a.threshold
+    groups, K, pos_weight = _class_setup(parse_label_groups(a.label_groups), pos_weight)
+    if focal is not None:
+        focal = tools.focal_rows(K, **focal)  # (argument errors before anything is built)
+    if not tools.is_scalar_weight(threshold) and len(threshold) != K:
+        raise ValueError(f"--threshold names {len(threshold)} classes, label_groups {K}")
     amp_dtype = torch.bfloat16 if a.dtype == "bf16" else None
     if model is None:
         sd = model_state_dict(torch.load(a.modelf, map_location="cpu"))
@@ -302,10 +349,22 @@ def predict(a, grid_conf=None, data_aug_conf=None, model: Optional[torch.nn.Modu
     val_raw, n_val = valloader.loader, len(valloader.dataset)
     stager = BatchStager(data_aug_conf["final_dim"], a.bsz, len(simbev.CAMERA_ORDER),
                          (data_aug_conf["H"], data_aug_conf["W"]), grid_conf, dev, label_groups=groups)
-    p = Predictor(model, a.bsz, dev, amp_dtype=amp_dtype, threshold=a.threshold, graph=bool(a.graph), stager=stager)
+    p = Predictor(model, a.bsz, dev, amp_dtype=amp_dtype, threshold=threshold, graph=bool(a.graph), stager=stager)
     if K > 1 or not tools.is_scalar_weight(pos_weight):
         pos_weight = tools.class_weights(pos_weight, K, dev)
     totals = torch.zeros(1 + 2 * K, device=dev, dtype=torch.float64)
+    ladder_mode = focal is not None or ladder is not None
+    if ladder_mode:  # lss_seg_metrics_accum at the ladder and 0.5: either loss term, every threshold, one pass
+        columns = sorted(set((ladder or []) + [0.5]))
+        if len(columns) > 16:
+            raise ValueError(f"--iou_thresholds: {len(columns)} thresholds (0.5 included); at most 16")
+        thetas = torch.tensor([threshold_logit(v) for v in columns], device=dev, dtype=torch.float32)
+        if focal is not None:
+            params = torch.tensor(focal, device=dev, dtype=torch.float32)
+        else:
+            w = tools.class_weights(pos_weight, K, dev)
+            params = torch.stack([w, torch.ones_like(w), torch.zeros_like(w)], dim=1).contiguous()
+        totals = torch.zeros(1 + K + 2 * K * len(columns), device=dev, dtype=torch.float64)
     os.makedirs(a.out, exist_ok=True)
     masks, frames = [], 0
     it = iter(val_raw)
@@ -317,7 +376,10 @@ def predict(a, grid_conf=None, data_aug_conf=None, model: Optional[torch.nn.Modu
     while nxt is not None:
         b = stager.commit()
         logits = p.run(b)  # (the first call captures the graph: timed from the second batch on)
-        tools.val_accumulate(p._out, stager.binimgs, totals, n_valid=stager.n_valid, pos_weight=pos_weight)
+        if ladder_mode:
+            tools.seg_metrics_accumulate(p._out, stager.binimgs, totals, stager.n_valid, params, thetas)
+        else:
+            tools.val_accumulate(p._out, stager.binimgs, totals, n_valid=stager.n_valid, pos_weight=pos_weight)
         masks.append(p.masks())  # a fresh tensor per batch; the logits are static
         nxt = next(it, None)
         if nxt is not None:
@@ -335,8 +397,20 @@ def predict(a, grid_conf=None, data_aug_conf=None, model: Optional[torch.nn.Modu
             np.save(os.path.join(a.out, f"{index}.npy"), s)
             index += 1
     t = totals.tolist()
-    info = {"loss": t[0] / n_val, **tools.iou_summary(t[1:1 + K], t[1 + K:1 + 2 * K]),
-            "intersection": t[1:1 + K], "union": t[1 + K:1 + 2 * K], "samples": index, "classes": K,
+    extra = {}
+    if ladder_mode:
+        P, TP, PP = tools.seg_metrics_counts(t, K, len(columns))
+        c = columns.index(0.5)
+        inter, union = [TP[k][c] for k in range(K)], [PP[k][c] + P[k] - TP[k][c] for k in range(K)]
+        if ladder is not None:
+            cols = [columns.index(v) for v in ladder]
+            sub = t[:1 + K] + [TP[k][j] for k in range(K) for j in cols] + [PP[k][j] for k in range(K) for j in cols]
+            extra = {k: v for k, v in tools.seg_metrics_summary(sub, K, ladder, n_val).items() if k != "loss"}
+            extra["iou_thresholds"] = ladder
+    else:
+        inter, union = t[1:1 + K], t[1 + K:1 + 2 * K]
+    info = {"loss": t[0] / n_val, **tools.iou_summary(inter, union), **extra, "loss_kind": loss_kind,
+            "threshold": threshold, "intersection": inter, "union": union, "samples": index, "classes": K,
             "dtype": a.dtype, "graph": bool(a.graph), "bsz": a.bsz,
             "frames_per_s": frames / elapsed if frames and elapsed > 0 else None}
     with open(os.path.join(a.out, "metrics.json"), "w") as f:

@@ -176,6 +176,126 @@ class SimpleLoss(torch.nn.Module):
         return self.loss_fn(ypred.float() if ypred.dtype == torch.bfloat16 else ypred, ytgt)
 
 
+def focal_terms(x: torch.Tensor, q: torch.Tensor, w_pos, w_neg, gamma):
+    """(l, dl/dx) of the focal loss per element, in x's dtype, from the closed form (include/lss_convs.h,
+    lss_focal_logits_pc): q the boolean labels, w_pos / w_neg / gamma numbers or tensors broadcasting against x.
+    exp(-gamma softplus(z)) is (1 - p_t)^gamma; nothing here divides or subtracts near-equal terms, so the
+    gradient is finite where autograd through ``(1 - p_t) ** gamma`` is not (0 < gamma < 1, saturated logits)."""
+    z = torch.where(q, x, -x)
+    e = torch.exp(-x.abs())
+    lp = torch.log1p(e)
+    spz, spm = lp + z.clamp(min=0), lp + (-z).clamp(min=0)  # softplus(z), softplus(-z)
+    sp, sn = 1.0 / (1.0 + e), e / (1.0 + e)                 # sigmoid(|x|), sigmoid(-|x|)
+    sz, sm = torch.where(z >= 0, sp, sn), torch.where(z >= 0, sn, sp)
+    mw = torch.exp(-gamma * spz) * torch.where(q, torch.as_tensor(w_pos, dtype=x.dtype, device=x.device),
+                                               torch.as_tensor(w_neg, dtype=x.dtype, device=x.device))
+    gz = mw * (gamma * sz * spm + sm)
+    return mw * spm, torch.where(q, -gz, gz)
+
+
+class _FocalTorch(torch.autograd.Function):
+    """The focal loss where the kernel does not apply (CPU, strided or misaligned logits): focal_terms in fp32,
+    mean over the elements, the gradient (times 1 / n) kept in the logits' type."""
+
+    @staticmethod
+    def forward(ctx, x, target, params: torch.Tensor):
+        p = params.to(device=x.device, dtype=torch.float32)
+        if p.shape[0] > 1:
+            p = p.view(p.shape[0], 1, 1, 3)
+        l, g = focal_terms(x.detach().float(), target != 0, p[..., 0], p[..., 1], p[..., 2])
+        ctx.save_for_backward((g / x.numel()).to(x.dtype))
+        return l.mean()
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return (grad.float() * g.float()).to(grad.dtype), None, None
+
+
+class _FocalLogits(torch.autograd.Function):
+    """``lss_focal_logits_pc``: loss and gradient in one pass plus the fold, as _BceLogitsPerClass; params is the
+    (K, 3) device buffer of (w_pos, w_neg, gamma) rows, read by the kernel."""
+
+    @staticmethod
+    def forward(ctx, x, target, params: torch.Tensor):
+        from . import _lib
+        lib = _lib.load()
+        n = x.numel()
+        K = params.shape[0]
+        partial = torch.empty(int(lib.lss_bce_partials(n)), device=x.device, dtype=torch.float32)
+        loss = torch.empty((), device=x.device, dtype=torch.float32)
+        grad = torch.empty_like(x)
+        _lib.check(lib.lss_focal_logits_pc(_lib.ptr(x), _lib.dtype_code(x.dtype), _lib.ptr(target), n,
+                                           n // (x.shape[0] * K), K, _lib.ptr(params), _lib.ptr(partial),
+                                           _lib.ptr(loss), _lib.ptr(grad), _lib.stream_handle(x.device)),
+                   "lss_focal_logits_pc")
+        ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        return _BceLogits.backward(ctx, g)
+
+
+def _per_class(value, K: int, name: str) -> list:
+    """K floats from a number or a sequence of K."""
+    vals = [float(value)] * K if is_scalar_weight(value) else [float(v) for v in value]
+    if len(vals) != K:
+        raise ValueError(f"FocalLoss: {name} names {len(vals)} classes, not {K}")
+    return vals
+
+
+def focal_rows(classes: int, gamma=2.0, alpha=None, pos_weight=None) -> list:
+    """The K rows (w_pos, w_neg, gamma) of the focal loss's parameters: focal(alpha, gamma) is
+    (alpha, 1 - alpha, gamma), a pos_weight (pw, 1, gamma), neither (1, 1, gamma); SimpleLoss(pw) is (pw, 1, 0).
+    gamma, alpha, pos_weight: a float or `classes` floats each."""
+    K = int(classes)
+    if K < 1:
+        raise ValueError(f"FocalLoss: {classes!r} classes")
+    if alpha is not None and pos_weight is not None:
+        raise ValueError("FocalLoss: alpha and pos_weight both set the class balance: give one")
+    g = _per_class(gamma, K, "gamma")
+    if any(not v >= 0.0 for v in g):
+        raise ValueError(f"FocalLoss: gamma {gamma!r} is negative")
+    if alpha is not None:
+        a = _per_class(alpha, K, "alpha")
+        if any(not 0.0 < v < 1.0 for v in a):
+            raise ValueError(f"FocalLoss: alpha {alpha!r} is not strictly between 0 and 1")
+        return [(v, 1.0 - v, gk) for v, gk in zip(a, g)]
+    w = [1.0] * K if pos_weight is None else _per_class(pos_weight, K, "pos_weight")
+    return [(v, 1.0, gk) for v, gk in zip(w, g)]
+
+
+class FocalLoss(torch.nn.Module):
+    """Focal loss on logits for imbalanced classes: mean of (1 - p_t)^gamma x weighted BCE over hard labels
+    (t != 0), per class k of (N, K, H, W) logits the row (w_pos, w_neg, gamma) of the device buffer
+    ``focal_params`` (K, 3) -- changed in place, a captured step follows. On the GPU under SimpleLoss's conditions
+    (fp32 or bf16 contiguous 16-B aligned logits, fp32 labels of the same shape) loss and gradient come from
+    ``lss_focal_logits_pc``, computed in fp32; otherwise from the same closed form in torch (focal_terms), which
+    is finite where autograd through the power is not. Drops in wherever SimpleLoss does."""
+
+    computes_in_fp32 = True
+
+    def __init__(self, classes: int, gamma=2.0, alpha=None, pos_weight=None):
+        super().__init__()
+        rows = focal_rows(classes, gamma, alpha, pos_weight)
+        self.classes = len(rows)
+        self.register_buffer("focal_params", torch.tensor(rows, dtype=torch.float32), persistent=False)
+
+    def forward(self, ypred, ytgt):
+        K, p = self.classes, self.focal_params
+        if K > 1 and not (ypred.dim() == 4 and ypred.shape[1] == K):
+            raise RuntimeError(f"FocalLoss: {K} classes for logits {tuple(ypred.shape)}")
+        if ytgt.shape != ypred.shape:
+            raise RuntimeError(f"FocalLoss: labels {tuple(ytgt.shape)} for logits {tuple(ypred.shape)}")
+        if (ypred.is_cuda and ypred.dtype in (torch.float32, torch.bfloat16) and ytgt.dtype == torch.float32
+                and ytgt.device == ypred.device and ypred.is_contiguous() and ytgt.is_contiguous()
+                and ypred.data_ptr() % 16 == 0 and ytgt.data_ptr() % 16 == 0 and ypred.numel() > 0 and ypred.dim() >= 1
+                and p.device == ypred.device and p.dtype == torch.float32 and p.is_contiguous()):
+            return _FocalLogits.apply(ypred, ytgt, p)
+        return _FocalTorch.apply(ypred, ytgt, p)
+
+
 def get_batch_iou(preds: torch.Tensor, binimgs: torch.Tensor):
     """Intersection, union and IoU of (logit > 0) vs the labels, as Python floats (src/tools.py:232-240)."""
     intersect, union = get_batch_iou_device(preds, binimgs)
@@ -272,6 +392,90 @@ def val_accumulate(preds: torch.Tensor, binimgs: torch.Tensor, totals: torch.Ten
                                      _lib.ptr(n_valid), float(pos_weight), _lib.ptr(totals), _lib.ptr(partial),
                                      _lib.stream_handle(x.device)), "lss_bce_iou_accum")
     return totals
+
+
+def seg_metrics_accumulate(preds: torch.Tensor, binimgs: torch.Tensor, totals: torch.Tensor, n_valid, params: torch.Tensor,
+                           thetas: torch.Tensor) -> torch.Tensor:
+    """One validation batch into the accumulators of a threshold ladder, ``lss_seg_metrics_accum``
+    (include/lss_convs.h): params the (K, 3) fp32 device rows (w_pos, w_neg, gamma) of the loss term
+    (FocalLoss.focal_params; (pw, 1, 0) is SimpleLoss), thetas T ascending fp32 logit thresholds on the device.
+    totals (1 + K + 2 K T float64 on the device) += the loss term, P_k, TP_kj, PP_kj over the first ``n_valid``
+    samples (one int32 on the device; None: all). Device tensors only; two launches, no host synchronisation,
+    capturable (the scratch is kept per device and size, as val_accumulate's)."""
+    from . import _lib
+    if not (preds.is_cuda and all(v.device == preds.device for v in (binimgs, totals, params, thetas))):
+        raise RuntimeError("seg_metrics_accumulate: device tensors only (no CPU fallback)")
+    K = preds.shape[1] if preds.dim() >= 2 else 1
+    T = thetas.numel()
+    if (binimgs.dtype != torch.float32 or binimgs.shape != preds.shape or totals.dtype != torch.float64
+            or not 1 <= T <= 16 or not 1 <= K <= 32 or totals.numel() != 1 + K + 2 * K * T
+            or not totals.is_contiguous() or preds.numel() == 0 or tuple(params.shape) != (K, 3)
+            or params.dtype != torch.float32 or thetas.dtype != torch.float32 or not params.is_contiguous()
+            or not thetas.is_contiguous()):
+        raise RuntimeError(f"seg_metrics_accumulate: preds {tuple(preds.shape)} {preds.dtype}, labels "
+                           f"{tuple(binimgs.shape)} {binimgs.dtype}, totals {tuple(totals.shape)} {totals.dtype}, "
+                           f"params {tuple(params.shape)} {params.dtype}, thetas {tuple(thetas.shape)} {thetas.dtype}")
+    if n_valid is not None and not (n_valid.device == preds.device and n_valid.dtype == torch.int32
+                                    and n_valid.numel() == 1):
+        raise RuntimeError("seg_metrics_accumulate: n_valid must be one int32 on the logits' device")
+    lib = _lib.load()
+    x, t = preds.detach().contiguous(), binimgs.contiguous()
+    batch = x.shape[0]
+    per_sample = x.numel() // batch
+    nbytes = int(lib.lss_seg_metrics_partial_bytes(x.numel(), K, T))
+    key = (x.device, nbytes)
+    partial = _VAL_PARTIAL.get(key)
+    if partial is None:
+        partial = _VAL_PARTIAL[key] = torch.empty(nbytes // 8, device=x.device, dtype=torch.float64)
+    _lib.check(lib.lss_seg_metrics_accum(_lib.ptr(x), _lib.dtype_code(x.dtype), _lib.ptr(t), per_sample, batch,
+                                         _lib.ptr(n_valid), per_sample // K, K, _lib.ptr(params), _lib.ptr(thetas), T,
+                                         _lib.ptr(totals), _lib.ptr(partial), _lib.stream_handle(x.device)),
+               "lss_seg_metrics_accum")
+    return totals
+
+
+def seg_metrics_counts(totals, K: int, T: int):
+    """(P[k], TP[k][j], PP[k][j]) as lists from the 1 + K + 2 K T totals of lss_seg_metrics_accum."""
+    t = [float(v) for v in (totals.tolist() if torch.is_tensor(totals) else totals)]
+    P = t[1:1 + K]
+    TP = [t[1 + K + k * T:1 + K + (k + 1) * T] for k in range(K)]
+    PP = [t[1 + K + K * T + k * T:1 + K + K * T + (k + 1) * T] for k in range(K)]
+    return P, TP, PP
+
+
+def seg_metrics_summary(totals, K: int, thresholds, n_samples) -> dict:
+    """The totals of lss_seg_metrics_accum (a sequence or a tensor of 1 + K + 2 K T numbers; `thresholds`: the T
+    probabilities of its columns) as a report: "loss" (the total over n_samples), "iou_at" (per threshold, a list
+    over classes of TP / (PP + P - TP), None where that union is 0), "iou_max_per_class" and
+    "best_threshold_per_class" (the largest IoU of a class over the ladder; ties go to the threshold nearest 0.5,
+    then to the lower one; None for a class without any), "iou_max" (their mean over the classes that have one,
+    None if none has). Never raises for counts of any value: what cannot be computed is None."""
+    K, th = int(K), [float(v) for v in thresholds]
+    T = len(th)
+    t = [float(v) for v in (totals.tolist() if torch.is_tensor(totals) else totals)]
+    t += [0.0] * max(0, 1 + K + 2 * K * T - len(t))
+    P, TP, PP = seg_metrics_counts(t, K, T)
+    iou_at = []
+    for j in range(T):
+        row = []
+        for k in range(K):
+            union = PP[k][j] + P[k] - TP[k][j]
+            row.append(TP[k][j] / union if union > 0 else None)
+        iou_at.append(row)
+    best_iou, best_th = [], []
+    for k in range(K):
+        # (the distance rounded: 0.45 and 0.55 are equally near 0.5, whatever their binary fractions say)
+        cand = [(-iou_at[j][k], round(abs(th[j] - 0.5), 9), th[j]) for j in range(T) if iou_at[j][k] is not None]
+        if cand:
+            top = min(cand)
+            best_iou.append(-top[0])
+            best_th.append(top[2])
+        else:
+            best_iou.append(None)
+            best_th.append(None)
+    seen = [v for v in best_iou if v is not None]
+    return {"loss": t[0] / n_samples if n_samples else None, "iou_at": iou_at, "iou_max_per_class": best_iou,
+            "best_threshold_per_class": best_th, "iou_max": sum(seen) / len(seen) if seen else None}
 
 
 def val_totals(model, loader, loss_fn, device):

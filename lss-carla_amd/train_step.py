@@ -205,7 +205,13 @@ class EvalStep:
 
     def __init__(self, model: torch.nn.Module, forward: Callable[..., torch.Tensor], inputs: Sequence[torch.Tensor],
                  labels: torch.Tensor, n_valid: Optional[torch.Tensor] = None, pos_weight=2.13,
-                 amp_dtype: Optional[torch.dtype] = torch.bfloat16, n_samples: Optional[int] = None):
+                 amp_dtype: Optional[torch.dtype] = torch.bfloat16, n_samples: Optional[int] = None,
+                 loss=None, thresholds=None):
+        """loss: a tools.FocalLoss whose term the loss total sums (its ``focal_params`` buffer is read on the device;
+        None: SimpleLoss(pos_weight)). thresholds: a ladder of probability thresholds to count the IoU at. With
+        either, the step accumulates through ``tools.seg_metrics_accumulate`` (``lss_seg_metrics_accum``) at the
+        ladder and 0.5, sorted, into 1 + K + 2 K T totals; ``read()`` keeps its keys -- the IoU from the 0.5 column --
+        and, for a ladder, adds ``tools.seg_metrics_summary``'s. With neither, nothing differs from before."""
         self.model, self.forward, self.inputs, self.labels = model, forward, tuple(inputs), labels
         self.n_samples = n_samples  # len(valloader.dataset): what read() divides the loss total by
         self.n_valid, self.amp_dtype = n_valid, amp_dtype
@@ -218,6 +224,24 @@ class EvalStep:
         else:
             self.pos_weight = float(pos_weight)
         self.totals = torch.zeros(1 + 2 * self.classes, device=labels.device, dtype=torch.float64)
+        self.ladder = None if thresholds is None else [float(v) for v in thresholds]
+        self.columns = self.params = self.thetas = None
+        if loss is not None or thresholds is not None:
+            from .predict import threshold_logit
+            K, dev = self.classes, labels.device
+            self.columns = sorted(set((self.ladder or []) + [0.5]))
+            if not 1 <= len(self.columns) <= 16:
+                raise ValueError(f"EvalStep: {len(self.columns)} thresholds (0.5 included); at most 16")
+            self.thetas = torch.tensor([threshold_logit(v) for v in self.columns], device=dev, dtype=torch.float32)
+            if loss is not None:
+                params = getattr(loss, "focal_params", None)
+                if params is None or tuple(params.shape) != (K, 3):
+                    raise ValueError(f"EvalStep: loss must be a tools.FocalLoss of {K} classes")
+                self.params = params if params.device == dev else params.to(dev)
+            else:
+                w = tools.class_weights(pos_weight, K, dev)
+                self.params = torch.stack([w, torch.ones_like(w), torch.zeros_like(w)], dim=1).contiguous()
+            self.totals = torch.zeros(1 + K + 2 * K * len(self.columns), device=dev, dtype=torch.float64)
         self.graph = None
         self.static_preds = None
 
@@ -237,8 +261,12 @@ class EvalStep:
                                     enabled=self.amp_dtype is not None, cache_enabled=not capturing):
                     preds = self.forward(*self.inputs)
                 self.static_preds = preds
-                tools.val_accumulate(preds, self.labels, self.totals, n_valid=self.n_valid,
-                                     pos_weight=self.pos_weight)
+                if self.columns is None:
+                    tools.val_accumulate(preds, self.labels, self.totals, n_valid=self.n_valid,
+                                         pos_weight=self.pos_weight)
+                else:
+                    tools.seg_metrics_accumulate(preds, self.labels, self.totals, self.n_valid, self.params,
+                                                 self.thetas)
         finally:
             self.model.train(was_training)
 
@@ -277,5 +305,17 @@ class EvalStep:
         from . import tools
         t = self.totals.tolist()
         K = self.classes
-        return {"loss": t[0] / (self.n_samples if n_samples is None else n_samples),
-                **tools.iou_summary(t[1:1 + K], t[1 + K:1 + 2 * K])}
+        n = self.n_samples if n_samples is None else n_samples
+        if self.columns is None:
+            return {"loss": t[0] / n, **tools.iou_summary(t[1:1 + K], t[1 + K:1 + 2 * K])}
+        # the ladder's totals: intersection = TP, union = PP + P - TP, at the 0.5 column for today's keys
+        P, TP, PP = tools.seg_metrics_counts(t, K, len(self.columns))
+        c = self.columns.index(0.5)
+        info = {"loss": t[0] / n, **tools.iou_summary([TP[k][c] for k in range(K)],
+                                                      [PP[k][c] + P[k] - TP[k][c] for k in range(K)])}
+        if self.ladder is not None:
+            cols = [self.columns.index(v) for v in self.ladder]
+            sub = t[:1 + K] + [TP[k][j] for k in range(K) for j in cols] + [PP[k][j] for k in range(K) for j in cols]
+            extra = tools.seg_metrics_summary(sub, K, self.ladder, n)
+            info.update({k: v for k, v in extra.items() if k != "loss"})
+        return info

@@ -118,6 +118,47 @@ def parse_pos_weight(text):
     return vals[0] if len(vals) == 1 else vals
 
 
+def parse_per_class(text, name="value"):
+    """A flag that takes one number or one per class, as --pos_weight: "2.0" -> 2.0; "2.0,1.5,0.5" -> [2.0, 1.5, 0.5]."""
+    items = [v.strip() for v in str(text).split(",") if v.strip()]
+    if not items:
+        raise ValueError(f"{name} {text!r}: no value")
+    vals = [float(v) for v in items]
+    return vals[0] if len(vals) == 1 else vals
+
+
+def parse_thresholds(text):
+    """``--iou_thresholds 0.35,0.4,0.45,0.5,0.55,0.6,0.65`` (or a sequence of numbers) -> the ladder as an ascending
+    list of distinct probabilities, each strictly between 0 and 1, 15 at most (0.5 makes 16); None or empty: None."""
+    if text is None or (isinstance(text, str) and not text.strip()):
+        return None
+    items = [v for v in text.split(",") if v.strip()] if isinstance(text, str) else list(text)
+    vals = sorted({float(v) for v in items})
+    if not vals:
+        return None
+    if any(not 0.0 < v < 1.0 for v in vals):
+        raise ValueError(f"--iou_thresholds {text!r}: probabilities strictly between 0 and 1")
+    if len(set(vals + [0.5])) > 16:
+        raise ValueError(f"--iou_thresholds {text!r}: at most 16 thresholds, 0.5 included")
+    return vals
+
+
+def _loss_setup(loss, pos_weight, focal_gamma, focal_alpha):
+    """(pos_weight, focal): the weight SimpleLoss / validation take (None: the reference's 2.13) and, for
+    loss == "focal", tools.FocalLoss's keyword arguments -- pos_weight becomes w_pos unless focal_alpha is given;
+    giving both is an error."""
+    if loss not in ("bce", "focal"):
+        raise ValueError(f"loss {loss!r}: bce or focal")
+    if loss == "bce":
+        if focal_alpha is not None:
+            raise ValueError("focal_alpha is the focal loss's: it needs loss=focal")
+        return (2.13 if pos_weight is None else pos_weight), None
+    if focal_alpha is not None and pos_weight is not None:
+        raise ValueError("loss=focal: pos_weight and focal_alpha both set the class balance: give one")
+    return (1.0 if pos_weight is None else pos_weight), {"gamma": focal_gamma, "alpha": focal_alpha,
+                                                          "pos_weight": pos_weight}
+
+
 def _class_setup(label_groups, pos_weight):
     """(groups or None, K, the loss's pos_weight): a list of weights must name one per class; a single-class
     run keeps a float (the one-weight kernels), a list of one collapsing to it."""
@@ -136,12 +177,15 @@ def _class_setup(label_groups, pos_weight):
 
 
 def build_step(grid_conf, data_aug_conf, bsz, device, *, dtype="bf16", lr=1e-3, weight_decay=1e-7,
-               max_grad_norm=5.0, pos_weight=2.13, skip_nonfinite=True, n_val=None, label_groups=None) -> dict:
+               max_grad_norm=5.0, pos_weight=2.13, skip_nonfinite=True, n_val=None, label_groups=None,
+               loss="bce", focal_gamma=2.0, focal_alpha=None, iou_thresholds=None) -> dict:
     """The model and its steps as bench.py's train branch builds them -- unused parameters frozen, one flat
     fp32 master per backward group, fused capturable Adam, TrainStep without a pre_step (the stager's
     commit stages the inverses) -- plus the stager and the EvalStep over the same static tensors. Nothing is
     captured yet. label_groups: K lists of BEV channels -> a model with outC = K and (B, K, X, Y) labels
-    (None: the reference's vehicle mask, outC = 1); pos_weight: a float, or one weight per class."""
+    (None: the reference's vehicle mask, outC = 1); pos_weight: a float, or one weight per class.
+    loss: "bce" (SimpleLoss) or "focal" (tools.FocalLoss(outC, focal_gamma, focal_alpha), pos_weight its w_pos
+    when focal_alpha is None); iou_thresholds: a ladder of probabilities the EvalStep also counts the IoU at."""
     import lss_carla_amd as L
     from . import parallel, simbev, tools
     from .flat_params import FlatParamGroups, lss_backward_groups
@@ -161,13 +205,21 @@ def build_step(grid_conf, data_aug_conf, bsz, device, *, dtype="bf16", lr=1e-3, 
     stager = BatchStager(data_aug_conf["final_dim"], bsz, len(simbev.CAMERA_ORDER),
                          (data_aug_conf["H"], data_aug_conf["W"]), grid_conf, device, label_groups=label_groups)
     model.static_inverses = (stager.hinv.pinv, stager.hinv.kinv)  # staged by the stager's commit
-    loss_fn = tools.SimpleLoss(pos_weight).to(device)
+    if loss not in ("bce", "focal"):
+        raise ValueError(f"loss {loss!r}: bce or focal")
+    if loss == "focal":
+        loss_fn = tools.FocalLoss(outC, gamma=focal_gamma, alpha=focal_alpha,
+                                  pos_weight=None if focal_alpha is not None else pos_weight).to(device)
+    else:
+        loss_fn = tools.SimpleLoss(pos_weight).to(device)
+    iou_thresholds = parse_thresholds(iou_thresholds)
     forward = flat.bind(model)
     step = TrainStep(forward, stager.inputs, stager.binimgs, loss_fn, opt, masters, all_reduce=False,
                      amp_dtype=amp_dtype, max_grad_norm=max_grad_norm, pre_step=None,
                      skip_nonfinite=bool(skip_nonfinite), keep_preds=True)
     evaluate = EvalStep(model, forward, stager.inputs, stager.binimgs, n_valid=stager.n_valid,
-                        pos_weight=pos_weight, amp_dtype=amp_dtype, n_samples=n_val)
+                        pos_weight=pos_weight, amp_dtype=amp_dtype, n_samples=n_val,
+                        loss=loss_fn if loss == "focal" else None, thresholds=iou_thresholds)
     return {"model": model, "flat": flat, "masters": masters, "opt": opt, "stager": stager, "step": step,
             "evaluate": evaluate, "loss_fn": loss_fn, "forward": forward, "label_groups": label_groups}
 
@@ -185,7 +237,7 @@ def train(
     rand_flip=False,
     ncams=6,
     max_grad_norm=5.0,
-    pos_weight=2.13,
+    pos_weight=None,
     logdir="./runs/simbev",
     xbound=[-50.0, 50.0, 0.5],
     ybound=[-50.0, 50.0, 0.5],
@@ -214,6 +266,10 @@ def train(
     cycle_batches=0,
     on_start: Optional[Callable[[dict], None]] = None,
     label_groups=None,
+    loss="bce",
+    focal_gamma=2.0,
+    focal_alpha=None,
+    iou_thresholds=None,
 ):
     """Train LiftSplatShoot on a SimBEV tree; the reference's arguments (train_simbev.py:23-98) plus:
 
@@ -227,16 +283,26 @@ def train(
     label_groups: K lists of BEV channels, one output class each (outC = K; None: the reference's vehicle
     mask [[1, 2, 3]], outC = 1); pos_weight is then a float or a list of K. With K > 1 the ``val`` and
     ``train_iou`` events carry ``iou_per_class`` and ``iou`` is the mean over the classes seen.
+    pos_weight: None is the reference's 2.13. loss: "bce", or "focal" -- tools.FocalLoss(K, focal_gamma,
+    focal_alpha), each a float or a list of K; pos_weight is then the focal loss's w_pos (None: 1) unless
+    focal_alpha is given, and giving both raises ValueError before anything is built. iou_thresholds: a ladder of
+    probability thresholds; validation then also counts the IoU at each, and the ``val`` events carry ``iou_max``,
+    ``iou_max_per_class`` and ``best_threshold_per_class``. ``model_best.pt`` is chosen by ``iou`` (at 0.5) all the
+    same. With either option metrics.jsonl starts with a ``config`` event naming the loss and the ladder.
     Returns a summary dict (counter, epoch, best_val_iou, skipped, frames_per_s of the training steps)."""
     from . import checkpoint, simbev, tools
 
+    pos_weight, focal = _loss_setup(loss, pos_weight, focal_gamma, focal_alpha)
+    iou_thresholds = parse_thresholds(iou_thresholds)
+    label_groups, n_out, pos_weight = _class_setup(label_groups, pos_weight)
+    if focal is not None:
+        tools.focal_rows(n_out, **focal)  # (argument errors come before anything is looked for or built)
     if gpuid < 0 or not torch.cuda.is_available():
         raise RuntimeError("lss_carla_amd.trainer: needs an MI355X (the hot path has no CPU fallback)")
     if ncams != len(simbev.CAMERA_ORDER):
         raise NotImplementedError("ncams must be 6: validation uses every camera and the step's shape is static")
     if dtype not in ("bf16", "fp32"):
         raise ValueError(f"dtype {dtype!r}: bf16 or fp32")
-    label_groups, n_out, pos_weight = _class_setup(label_groups, pos_weight)
     if resume is not None and os.path.exists(resume):
         _check_head_classes(resume, n_out)  # before anything is built, loaded or captured
     os.makedirs(logdir, exist_ok=True)
@@ -250,7 +316,17 @@ def train(
               "dtype": dtype, "seed": seed}
     if label_groups is not None:
         config["label_groups"] = label_groups
+    if focal is not None or iou_thresholds is not None:
+        config["loss"] = loss
+        config["iou_thresholds"] = iou_thresholds
+        if focal is not None:
+            config["focal_gamma"], config["focal_alpha"] = focal_gamma, focal_alpha
+            if focal_alpha is not None:
+                config["pos_weight"] = None  # (alpha sets the class balance)
     log = _Log(logdir, use_wandb, {"project": wandb_project, "name": wandb_name, "entity": wandb_entity}, config)
+
+    if "loss" in config:
+        log.event("config", 0, **config)
 
     device = torch.device(f"cuda:{gpuid}")
     torch.cuda.set_device(device)
@@ -270,7 +346,8 @@ def train(
 
     ctx = build_step(grid_conf, data_aug_conf, bsz, device, dtype=dtype, lr=lr, weight_decay=weight_decay,
                      max_grad_norm=max_grad_norm, pos_weight=pos_weight, skip_nonfinite=skip_nonfinite,
-                     n_val=n_val, label_groups=label_groups)
+                     n_val=n_val, label_groups=label_groups, loss=loss, focal_gamma=focal_gamma,
+                     focal_alpha=focal_alpha, iou_thresholds=iou_thresholds)
     model, flat, masters, opt = ctx["model"], ctx["flat"], ctx["masters"], ctx["opt"]
     stager, step, evaluate = ctx["stager"], ctx["step"], ctx["evaluate"]
 
@@ -377,6 +454,8 @@ def train(
                 info = validate()
                 print(f"  Validation at {counter} - Loss: {info['loss']:.4f}, IoU: {info['iou']:.4f}")
                 extra = {"iou_per_class": info["iou_per_class"]} if n_out > 1 else {}
+                if iou_thresholds is not None:
+                    extra.update({k: info[k] for k in ("iou_max", "iou_max_per_class", "best_threshold_per_class")})
                 log.event("val", counter, epoch=epoch, loss=info["loss"], iou=info["iou"], **extra)
                 if info["iou"] > best_val_iou:
                     best_val_iou = info["iou"]
@@ -452,7 +531,15 @@ def main(argv=None):
     p.add_argument("--skip_nonfinite", type=int, default=1)
     p.add_argument("--label_groups", type=str, default=None,
                    help='BEV channel groups, one output class each: "0;1,2,3;6,7" (default: the vehicle mask 1,2,3)')
-    p.add_argument("--pos_weight", type=str, default="2.13", help="one positive-class weight, or one per class: 1.0,2.13,5.0")
+    p.add_argument("--pos_weight", type=str, default=None,
+                   help="one positive-class weight, or one per class: 1.0,2.13,5.0 (default 2.13; with --loss focal: w_pos, default 1)")
+    p.add_argument("--loss", default="bce", choices=["bce", "focal"])
+    p.add_argument("--focal_gamma", type=str, default="2.0", help="focal loss: one gamma, or one per class: 2.0,2.0,1.0")
+    p.add_argument("--focal_alpha", type=str, default=None,
+                   help="focal loss: one alpha in (0, 1), or one per class (instead of --pos_weight)")
+    p.add_argument("--iou_thresholds", type=str, default=None,
+                   help="validation also reports the IoU at these probability thresholds and the best per class: "
+                        "0.35,0.4,0.45,0.5,0.55,0.6,0.65")
     a = p.parse_args(argv)
     return train(dataroot=a.dataroot, nepochs=a.nepochs, gpuid=a.gpuid, H=a.H, W=a.W, final_dim=(a.final_h, a.final_w),
                  ncams=a.ncams, bsz=a.bsz, nworkers=a.nworkers, lr=a.lr, weight_decay=a.weight_decay, logdir=a.logdir,
@@ -460,7 +547,12 @@ def main(argv=None):
                  wandb_project=a.wandb_project, wandb_name=a.wandb_name, wandb_entity=a.wandb_entity,
                  graph=bool(a.graph), dtype=a.dtype, miopen_find=bool(a.miopen_find), seed=a.seed,
                  max_steps=a.max_steps, skip_nonfinite=bool(a.skip_nonfinite),
-                 label_groups=parse_label_groups(a.label_groups), pos_weight=parse_pos_weight(a.pos_weight))
+                 label_groups=parse_label_groups(a.label_groups),
+                 pos_weight=parse_pos_weight(a.pos_weight) if a.pos_weight is not None
+                 else (None if a.loss == "focal" else 2.13), loss=a.loss,
+                 focal_gamma=parse_per_class(a.focal_gamma, "--focal_gamma"),
+                 focal_alpha=None if a.focal_alpha is None else parse_per_class(a.focal_alpha, "--focal_alpha"),
+                 iou_thresholds=parse_thresholds(a.iou_thresholds))
 
 
 if __name__ == "__main__":

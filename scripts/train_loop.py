@@ -7,6 +7,7 @@ train_loop step): one JSON line {"frames_per_s", "steps", "nworkers", "cycle_bat
   python scripts/train_loop.py --make DIR --samples 2000                           write the tree and exit
   python scripts/train_loop.py --dataroot DIR --label-groups "0;1,2;3"             a multi-class run (on a tree made
                                                                                     with --box-classes 0,1,2,3)
+  python scripts/train_loop.py --dataroot DIR --loss focal [--focal-gamma 2.0]     the focal loss (--pos-weight its w_pos)
 """
 from __future__ import annotations
 
@@ -33,6 +34,8 @@ def main():
     ap.add_argument("--miopen-find", type=int, default=0)
     ap.add_argument("--label-groups", default="", help='trainer --label_groups, e.g. "0;1,2;3" (default: the vehicle mask)')
     ap.add_argument("--pos-weight", default="2.13", help="trainer --pos_weight: one weight, or one per class")
+    ap.add_argument("--loss", default="bce", choices=["bce", "focal"], help="trainer --loss")
+    ap.add_argument("--focal-gamma", default="2.0", help="trainer --focal_gamma")
     ap.add_argument("--box-classes", default="1,2,3", help="--make: the BEV channels the boxes are drawn in")
     a = ap.parse_args()
     from lss_carla_amd import miopen_db
@@ -50,10 +53,12 @@ def main():
                             val_step=10 ** 9, save_step=10 ** 9, use_wandb=False, graph=bool(a.graph),
                             miopen_find=bool(a.miopen_find), seed=0, max_steps=a.steps,
                             cycle_batches=a.cycle_batches, label_groups=trainer.parse_label_groups(a.label_groups),
-                            pos_weight=trainer.parse_pos_weight(a.pos_weight))
+                            pos_weight=trainer.parse_pos_weight(a.pos_weight), loss=a.loss,
+                            focal_gamma=trainer.parse_per_class(a.focal_gamma, "--focal-gamma"))
     print(json.dumps({"frames_per_s": out["frames_per_s"], "steps": out["counter"], "bsz": a.bsz,
                       "nworkers": a.nworkers, "cycle_batches": a.cycle_batches, "graph": a.graph,
-                      "skipped": out["skipped"], "loss": out["loss"], "label_groups": a.label_groups or None}))
+                      "skipped": out["skipped"], "loss": out["loss"], "label_groups": a.label_groups or None,
+                      "loss_kind": a.loss}))
 
 
 if __name__ == "__main__":

@@ -279,6 +279,31 @@ int lss_clip_adam_guarded(int32_t count, float* const* params, const float* cons
                           float* const* exp_avg_sq, float* const* step, const int64_t* numel, float max_norm,
                           float lr, float beta1, float beta2, float eps, float weight_decay, float* partial,
                           int32_t* skipped, void* stream);
+/* (ABI 30) Either update with the learning rate computed on the device and, optionally, an exponential moving
+ * average (EMA) of the weights, so that a captured update follows a schedule. skipped: NULL = lss_clip_adam's
+ * form (two launches), else lss_clip_adam_guarded's (three). lr is the base rate; with t the value Adam's bias
+ * correction uses for this update (each tensor's own count, after its advance) and s = t - 1, in fp32:
+ *   warm  = warmup_steps > 0 ? warmup_factor + (1 - warmup_factor) * min(s, W) / W : 1
+ *   x     = clamp((s - W) / (T - W), 0, 1)            W = warmup_steps, T = total_steps, m = min_factor
+ *   decay = 1 (kind 0, constant) | m + (1 - m)(1 - x) (1, linear) | m + (1 - m) * 0.5 * (1 + cos(pi x)) (2, cosine)
+ *   lr_t  = lr * warm * decay                          (past T: lr * m)
+ * (the cosine is evaluated as sin^2(pi (1 - x) / 2), the same function without the cancellation at x -> 1).
+ * A skipped step does not advance t, hence not the schedule; a constant schedule without warm-up, ema = NULL,
+ * computes what the entries above compute, bit for bit. lr_out (device, nullable): tensor 0's lr_t of the
+ * update just applied, written by one thread of the Adam pass; a skipped step leaves it alone.
+ * ema (NULL, or `count` device pointers, ema[k] of numel[k] fp32, distinct from each other and from every
+ * params / exp_avg / exp_avg_sq pointer): after the parameter's update, same thread, same pass,
+ *   e = fmaf(1 - d, p_new - e, e),  d = ema_warmup ? min(ema_decay, (1 + t) / (10 + t)) : ema_decay;
+ * a skipped step writes no EMA element; a tensor whose EMA is not 16-B aligned takes the scalar loop.
+ * LSS_CONV_EINVAL before any launch: kind outside 0..2, warmup_steps < 0, warmup_factor or min_factor outside
+ * [0, 1], kind != 0 with total_steps <= warmup_steps, ema_decay outside [0, 1), a NULL or repeated ema entry,
+ * an ema pointer equal to a params / exp_avg / exp_avg_sq pointer, and what the entries above refuse. */
+int lss_clip_adam_sched(int32_t count, float* const* params, const float* const* grads, float* const* exp_avg,
+                        float* const* exp_avg_sq, float* const* step, const int64_t* numel, float max_norm,
+                        float lr, float beta1, float beta2, float eps, float weight_decay, float* partial,
+                        int32_t* skipped, int32_t kind, int32_t warmup_steps, float warmup_factor,
+                        int32_t total_steps, float min_factor, float* lr_out, float* const* ema, float ema_decay,
+                        int32_t ema_warmup, void* stream);
 
 /* Training-mode batch norm fused with an activation (and, for ReLU, a residual add), for
  * nn.BatchNorm2d followed by swish (EfficientNet-B0, src/models.py:68 and the MBConv blocks) or

@@ -18,7 +18,7 @@ DEBUG_LIB_PATH = os.path.join(_HERE, "liblss_hip_debug.so")  # LSS_DEBUG=1: devi
 
 F32, BF16 = 0, 1
 NCHW, NHWC = 0, 1
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 
 class Dims(ctypes.Structure):
@@ -131,6 +131,10 @@ SIGNATURES = {
     "lss_clip_adam_guarded": (ctypes.c_int, [_i32, _p, _p, _p, _p, _p, _p, ctypes.c_float, ctypes.c_float,
                                              ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _p, _p,
                                              _p]),
+    "lss_clip_adam_sched": (ctypes.c_int, [_i32, _p, _p, _p, _p, _p, _p, ctypes.c_float, ctypes.c_float,
+                                           ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _p, _p,
+                                           _i32, _i32, ctypes.c_float, _i32, ctypes.c_float, _p, _p, ctypes.c_float,
+                                           _i32, _p]),
     "lss_pw_wrw_workspace_bytes": (ctypes.c_int64, [_i32, _i32, _i32, _i32]),
     "lss_pw_wrw": (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _i32, _p, _i32, _p, ctypes.c_int64, _p]),
     "lss_pw_conv": (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p]),

@@ -11,6 +11,10 @@ their addresses.
 Parameters that never receive a gradient carry no optimizer state, as in torch: the constants ``dx``,
 ``bx``, ``nx``, ``frustum`` (nn.Parameters without requires_grad, src/models.py:143-152) and whatever
 ``parallel.freeze_unused`` froze (EfficientNet's unused head) take an index and nothing else.
+
+When the flat parameters keep an EMA of the weights (``enable_ema``), the file gains one key, ``ema_state_dict``: a
+full state dict the reference's ``model.load_state_dict`` can load as it is. ``load_checkpoint`` copies it into the
+EMA tensors in place; a file without it starts the EMA from the loaded weights and says so.
 """
 from __future__ import annotations
 
@@ -73,8 +77,38 @@ def save_checkpoint(path, model: torch.nn.Module, flat, opt: torch.optim.Optimiz
     }
     if val_iou is not None:
         ckpt["val_iou"] = float(val_iou)
+    if _has_ema(flat):
+        ckpt["ema_state_dict"] = ema_state_dict(model, flat)
     torch.save(ckpt, path)
     return ckpt
+
+
+def _has_ema(flat) -> bool:
+    return all(getattr(g, "ema", None) is not None for g in _groups(flat))
+
+
+def ema_state_dict(model: torch.nn.Module, flat) -> dict:
+    """A full state dict with the EMA values for the trainable parameters and the live values for everything
+    else (frozen parameters, constants, batch-norm statistics): ``model.load_state_dict`` loads it as it is."""
+    sd = dict(model.state_dict())
+    for grp in _groups(flat):
+        for name, view in grp.views_of(grp.ema).items():
+            if name not in sd:
+                raise KeyError(f"checkpoint: {name} is not a key of the model's state dict")
+            sd[name] = view.detach().clone()
+    return sd
+
+
+def load_ema(sd: Optional[dict], flat) -> None:
+    """Copy an ``ema_state_dict`` into the EMA tensors in place; None (a file without one): the EMA starts from
+    the current weights."""
+    with torch.no_grad():
+        for grp in _groups(flat):
+            if sd is None:
+                grp.ema.copy_(grp.master.detach())
+                continue
+            for name, view in grp.views_of(grp.ema).items():
+                view.copy_(sd[name])
 
 
 def init_state(opt: torch.optim.Optimizer, master: torch.Tensor) -> dict:
@@ -126,6 +160,13 @@ def load_checkpoint(path, model: torch.nn.Module, flat, opt: torch.optim.Optimiz
     if isinstance(ckpt, dict) and "model_state_dict" in ckpt:
         model.load_state_dict(ckpt["model_state_dict"])  # copies into the parameters: the masters' memory
         load_optimizer_state(ckpt["optimizer_state_dict"], model, flat, opt)
+        if _has_ema(flat):
+            if "ema_state_dict" not in ckpt:
+                print(f"{path} has no ema_state_dict: the EMA starts from the loaded weights")
+            load_ema(ckpt.get("ema_state_dict"), flat)
         return int(ckpt.get("counter", 0)), int(ckpt.get("epoch", 0))
     model.load_state_dict(ckpt)
+    if _has_ema(flat):
+        print(f"{path} is a bare state dict: the EMA starts from the loaded weights")
+        load_ema(None, flat)
     return 0, 0

@@ -148,6 +148,7 @@ class FlatParams:
                 v.copy_(p)
                 p.data = v  # the module's Parameters now alias the master buffer
         self.master = nn.Parameter(master)
+        self.ema = None  # enable_ema()
         self.work16 = torch.empty(self.n16, device=dev, dtype=cast_dtype or torch.float32)
         self.work32 = torch.empty(self.numel - self.n16, device=dev, dtype=torch.float32)
         # the depthnet 1x1 conv (CamEncode.depthnet, src/models.py:47) of a fused-lift model: its bf16
@@ -170,14 +171,36 @@ class FlatParams:
             self.dn_packed = torch.empty(_lib.DN_PACKED_BYTES(K) // 2, device=dev, dtype=torch.bfloat16)
             dn.lss_packed_weight = (self.dn_packed, self.work16.data_ptr() + 2 * off)
 
-    def tensors(self) -> Dict[str, torch.Tensor]:
-        outs = _Materialize.apply(self.master, self)
+    def enable_ema(self) -> torch.Tensor:
+        """Allocate ``ema`` (flat fp32, laid out like ``master``) holding the master's current values; the
+        address is fixed from then on (call it before any capture). The optimizer's pass updates it
+        (optim.ClipAdam(ema=...)); ``tensors(source="ema")`` materialises the working copies from it."""
+        if self.ema is None:
+            self.ema = self.master.detach().clone()
+        return self.ema
+
+    def _source(self, source: str) -> torch.Tensor:
+        if source == "master":
+            return self.master
+        if source != "ema":
+            raise ValueError(f"FlatParams: source {source!r}: master or ema")
+        if self.ema is None:
+            raise RuntimeError("FlatParams: source='ema' needs enable_ema() first")
+        return self.ema
+
+    def tensors(self, source: str = "master") -> Dict[str, torch.Tensor]:
+        """The working parameters, materialised from the masters or (source="ema": no gradient flows back) from
+        the EMA by the same launch -- lss_flat_cast_bf16 and the packed depthnet weight included. Both sources
+        share the working buffers: the next materialisation overwrites them."""
+        outs = _Materialize.apply(self._source(source), self)
         return dict(zip(self.names16 + self.names32, outs))
 
-    def bind(self, model: nn.Module):
+    def bind(self, model: nn.Module, source: str = "master"):
         """A callable running `model` on the materialised working parameters."""
+        self._source(source)
+
         def run(*args, **kwargs):
-            return torch.func.functional_call(model, self.tensors(), args, kwargs, strict=False)
+            return torch.func.functional_call(model, self.tensors(source), args, kwargs, strict=False)
         return run
 
     def views_of(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
@@ -208,18 +231,33 @@ class FlatParamGroups:
     def masters(self) -> List[nn.Parameter]:
         return [g.master for g in self.groups]
 
-    def views(self, grads: bool = False) -> Dict[str, torch.Tensor]:
-        """name -> view of the masters (or of their gradients)."""
+    def enable_ema(self) -> List[torch.Tensor]:
+        """FlatParams.enable_ema for every group; the EMA tensors, in the masters' order."""
+        return [g.enable_ema() for g in self.groups]
+
+    @property
+    def emas(self):
+        """The groups' EMA tensors in the masters' order, or None before enable_ema()."""
+        return None if any(g.ema is None for g in self.groups) else [g.ema for g in self.groups]
+
+    def views(self, grads: bool = False, ema: bool = False) -> Dict[str, torch.Tensor]:
+        """name -> view of the masters (or of their gradients, or of the EMA tensors)."""
         out = {}
         for g in self.groups:
-            out.update(g.views_of(g.master.grad if grads else g.master.detach()))
+            if ema:
+                out.update(g.views_of(g._source("ema")))
+            else:
+                out.update(g.views_of(g.master.grad if grads else g.master.detach()))
         return out
 
-    def bind(self, model: nn.Module):
+    def bind(self, model: nn.Module, source: str = "master"):
+        for g in self.groups:
+            g._source(source)
+
         def run(*args, **kwargs):
             tensors = {}
             for g in self.groups:
-                tensors.update(g.tensors())
+                tensors.update(g.tensors(source))
             return torch.func.functional_call(model, tensors, args, kwargs, strict=False)
         return run
 

@@ -8,6 +8,7 @@ rebuild ``EvalStep`` by hand:
 
     p = L.Predictor(model, bsz, device, amp_dtype=torch.bfloat16, threshold=0.5, graph=True)
     p.load(path)                     # explore.py's plain state_dict, or train_simbev.py's {"model_state_dict": ...}
+                                     # (weights="auto": a trainer checkpoint's EMA weights when it carries them)
     logits = p(imgs, rots, trans, intrins, post_rots, post_trans)    # host or device tensors, b <= bsz samples
     p.probs(); p.masks()             # sigmoid as fp32; uint8 (b, K, X, Y) = logits > logit(threshold)
 
@@ -26,6 +27,7 @@ state_dict): build it on a model no training step is bound to. The hot path has 
     python -m lss_carla_amd.predict --modelf CKPT --dataroot ROOT --out DIR [--bsz N] [--label_groups "0;1,2,3"]
                                     [--dtype bf16|fp32] [--graph 0|1] [--threshold 0.5 | 0.45,0.5,0.35]
                                     [--loss bce|focal] [--focal_gamma G] [--focal_alpha A] [--iou_thresholds 0.35,...]
+                                    [--weights auto|ema|model]
 
 runs the val split through ``BatchStager`` and the Predictor and writes one uint8 mask array per sample
 (``DIR/<index>.npy``, (K, X, Y)) and ``DIR/metrics.json``: loss, IoU and per-class IoU from get_val_info's
@@ -57,11 +59,22 @@ def threshold_logit(threshold: float) -> float:
     return 0.0 if t == 0.5 else math.log(t / (1.0 - t))
 
 
-def model_state_dict(ckpt) -> dict:
+WEIGHTS = ("auto", "ema", "model")
+
+
+def model_state_dict(ckpt, weights: str = "model") -> dict:
     """The model's state dict out of either checkpoint format: train_simbev.py's dict with
-    ``"model_state_dict"`` (train_simbev.py:206-212), or explore.py's plain ``model.state_dict()``."""
+    ``"model_state_dict"`` (train_simbev.py:206-212), or explore.py's plain ``model.state_dict()``.
+    weights: "model"; "ema": the trainer checkpoint's ``ema_state_dict`` (ValueError when it has none);
+    "auto": the EMA when the file has one, else the model's."""
+    if weights not in WEIGHTS:
+        raise ValueError(f"weights {weights!r}: one of {', '.join(WEIGHTS)}")
     if isinstance(ckpt, dict) and "model_state_dict" in ckpt:
-        ckpt = ckpt["model_state_dict"]
+        if weights == "ema" and "ema_state_dict" not in ckpt:
+            raise ValueError("weights='ema': the checkpoint has no ema_state_dict")
+        ckpt = ckpt["ema_state_dict" if weights != "model" and "ema_state_dict" in ckpt else "model_state_dict"]
+    elif weights == "ema":
+        raise ValueError("weights='ema': a bare state dict has no ema_state_dict")
     if not isinstance(ckpt, dict) or not ckpt or not all(isinstance(k, str) and torch.is_tensor(v)
                                                          for k, v in ckpt.items()):
         raise ValueError("not a model checkpoint: neither a state_dict nor a dict holding 'model_state_dict'")
@@ -155,10 +168,12 @@ class Predictor:
         if self.params is None:
             self.params = {k: v.detach() for k, v in params.items()}  # views of the static working buffers
 
-    def load(self, path) -> None:
+    def load(self, path, weights: str = "auto") -> None:
         """Load a checkpoint of either format into the module in place and refresh the working parameters; the
-        head's width is checked first (nothing is loaded, materialised or captured when it differs)."""
-        sd = model_state_dict(torch.load(path, map_location="cpu"))
+        head's width is checked first (nothing is loaded, materialised or captured when it differs). weights:
+        "auto" takes a trainer checkpoint's ``ema_state_dict`` (the averaged weights validation chose the file by)
+        when it has one, "ema" insists on it, "model" takes ``model_state_dict``."""
+        sd = model_state_dict(torch.load(path, map_location="cpu"), weights)
         check_head(sd, self.n_out, f"checkpoint {path}")
         self.model.load_state_dict(sd)  # copies into the parameters (the master's memory) and the buffers
         self.refresh()
@@ -285,6 +300,8 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--graph", type=int, default=1, choices=[0, 1], help="0: the same forward, eager")
     p.add_argument("--threshold", type=threshold_arg, default=0.5,
                    help="the masks' probability threshold, or one per class: 0.5,0.4,0.35")
+    p.add_argument("--weights", default="auto", choices=list(WEIGHTS),
+                   help="which weights of a trainer checkpoint: its EMA (auto: when it has one) or the model's")
     p.add_argument("--gpuid", type=int, default=0)
     p.add_argument("--nworkers", type=int, default=4)
     p.add_argument("--H", type=int, default=224)
@@ -338,7 +355,7 @@ def predict(a, grid_conf=None, data_aug_conf=None, model: Optional[torch.nn.Modu
         raise ValueError(f"--threshold names {len(threshold)} classes, label_groups {K}")
     amp_dtype = torch.bfloat16 if a.dtype == "bf16" else None
     if model is None:
-        sd = model_state_dict(torch.load(a.modelf, map_location="cpu"))
+        sd = model_state_dict(torch.load(a.modelf, map_location="cpu"), getattr(a, "weights", "auto"))
         check_head(sd, K, f"checkpoint {a.modelf}")  # before anything is built
         model = L.compile_model(grid_conf, data_aug_conf, outC=K).to(dev)
         model.load_state_dict(sd)

@@ -42,7 +42,8 @@ class TrainStep:
                  all_reduce: bool = False, amp_dtype: Optional[torch.dtype] = torch.bfloat16,
                  max_grad_norm: float = 5.0, pre_step: Optional[Callable[[], None]] = None,
                  overlap_all_reduce: bool = False, force_collectives: bool = False,
-                 skip_nonfinite: bool = False, keep_preds: bool = False):
+                 skip_nonfinite: bool = False, keep_preds: bool = False, lr_schedule=None, ema=None,
+                 ema_decay: float = 0.999, ema_warmup: bool = True):
         """overlap_all_reduce: all-reduce each parameter's gradient (e.g. each FlatParamGroups
         master) from its post-accumulate hook, on a side stream, while the backward continues -- inside
         the captured graph too; the step waits for them before the update. force_collectives: issue
@@ -50,7 +51,11 @@ class TrainStep:
         step whose gradient norm is a NaN or an infinity leaves parameters and optimizer state untouched
         and is counted in ``self.skipped`` (one int32 on the device; needs the HIP update, optim.supported).
         keep_preds: keep the step's detached logits as ``self.static_preds`` (captured: a static tensor
-        every replay rewrites), for the caller's training IoU."""
+        every replay rewrites), for the caller's training IoU. lr_schedule (an optim.LRSchedule): the update
+        computes the learning rate on the device from Adam's step count, so replays follow it (``self.lr``: the
+        last applied rate, one fp32 on the device); ema: one fp32 tensor per entry of params (e.g.
+        FlatParamGroups.enable_ema()), averaged in the Adam pass with ema_decay / ema_warmup (optim.ClipAdam).
+        Either needs the HIP update, as skip_nonfinite does."""
         self.forward, self.inputs, self.labels = forward, tuple(inputs), labels
         # host work staged into the step's static device inputs before each step is launched
         # (e.g. ops.HostInverses.update: the reference's host torch.inverse of the rig)
@@ -71,6 +76,15 @@ class TrainStep:
         self.static_loss = None
         self.keep_preds, self.static_preds = bool(keep_preds), None
         self.skipped = torch.zeros(1, device=labels.device, dtype=torch.int32) if skip_nonfinite else None
+        self.lr_schedule, self.ema = lr_schedule, (None if ema is None else list(ema))
+        self.ema_decay, self.ema_warmup = ema_decay, ema_warmup
+        self._clip_adam = None
+
+    @property
+    def lr(self) -> Optional[torch.Tensor]:
+        """The device scalar holding the last applied learning rate (a schedule or EMA asked for, after the
+        first update); None otherwise."""
+        return None if self._clip_adam is None else self._clip_adam.lr
 
     @property
     def captured(self) -> bool:
@@ -125,10 +139,14 @@ class TrainStep:
                     p.grad.mul_(1.0 / self.world)
         from . import optim
         if optim.supported(self.opt, self.params):  # both in two launches on the GPU (lss_clip_adam)
-            if getattr(self, "_clip_adam", None) is None or self._clip_adam.opt is not self.opt:
-                self._clip_adam = optim.ClipAdam(self.opt)
+            if self._clip_adam is None or self._clip_adam.opt is not self.opt:
+                self._clip_adam = optim.ClipAdam(self.opt, schedule=self.lr_schedule, ema=self.ema,
+                                                 ema_decay=self.ema_decay, ema_warmup=self.ema_warmup)
             self._clip_adam.step(self.max_grad_norm, skipped=self.skipped)
             return
+        if self.lr_schedule is not None or self.ema is not None:
+            raise RuntimeError("TrainStep(lr_schedule=..., ema=...) needs the HIP update (a fused / capturable "
+                               "torch.optim.Adam over fp32 device tensors, optim.supported)")
         if self.skipped is not None:
             raise RuntimeError("TrainStep(skip_nonfinite=True) needs the HIP update (a fused / capturable "
                                "torch.optim.Adam over fp32 device tensors, optim.supported)")

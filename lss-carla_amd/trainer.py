@@ -159,6 +159,24 @@ def _loss_setup(loss, pos_weight, focal_gamma, focal_alpha):
                                                           "pos_weight": pos_weight}
 
 
+def _schedule_setup(lr, lr_schedule, warmup_steps, warmup_factor, lr_min, lr_total_steps, ema_decay):
+    """Check the schedule's and the EMA's arguments (ValueError, before anything is looked for or built); returns
+    whether a schedule is asked for -- anything but a constant rate without warm-up. lr_min is absolute: the
+    decay ends at lr_min / lr. lr_total_steps None (the run's length, known once the loader is): checked later."""
+    from .optim import LRSchedule
+    if not float(lr) > 0.0:
+        raise ValueError(f"lr {lr!r}: positive")
+    if not 0.0 <= float(lr_min) <= float(lr):
+        raise ValueError(f"lr_min {lr_min!r}: between 0 and lr ({lr})")
+    if lr_total_steps is not None and int(lr_total_steps) <= 0:
+        raise ValueError(f"lr_total_steps {lr_total_steps!r}: positive")
+    total = int(lr_total_steps) if lr_total_steps is not None else max(int(warmup_steps), 0) + 1
+    LRSchedule(lr_schedule, warmup_steps, warmup_factor, total, float(lr_min) / float(lr))
+    if not 0.0 <= float(ema_decay) < 1.0:
+        raise ValueError(f"ema_decay {ema_decay!r}: in [0, 1) (0: no EMA)")
+    return lr_schedule != "constant" or int(warmup_steps) > 0
+
+
 def _class_setup(label_groups, pos_weight):
     """(groups or None, K, the loss's pos_weight): a list of weights must name one per class; a single-class
     run keeps a float (the one-weight kernels), a list of one collapsing to it."""
@@ -178,14 +196,18 @@ def _class_setup(label_groups, pos_weight):
 
 def build_step(grid_conf, data_aug_conf, bsz, device, *, dtype="bf16", lr=1e-3, weight_decay=1e-7,
                max_grad_norm=5.0, pos_weight=2.13, skip_nonfinite=True, n_val=None, label_groups=None,
-               loss="bce", focal_gamma=2.0, focal_alpha=None, iou_thresholds=None) -> dict:
+               loss="bce", focal_gamma=2.0, focal_alpha=None, iou_thresholds=None, lr_schedule=None,
+               ema_decay=0.0, ema_warmup=True) -> dict:
     """The model and its steps as bench.py's train branch builds them -- unused parameters frozen, one flat
     fp32 master per backward group, fused capturable Adam, TrainStep without a pre_step (the stager's
     commit stages the inverses) -- plus the stager and the EvalStep over the same static tensors. Nothing is
     captured yet. label_groups: K lists of BEV channels -> a model with outC = K and (B, K, X, Y) labels
     (None: the reference's vehicle mask, outC = 1); pos_weight: a float, or one weight per class.
     loss: "bce" (SimpleLoss) or "focal" (tools.FocalLoss(outC, focal_gamma, focal_alpha), pos_weight its w_pos
-    when focal_alpha is None); iou_thresholds: a ladder of probabilities the EvalStep also counts the IoU at."""
+    when focal_alpha is None); iou_thresholds: a ladder of probabilities the EvalStep also counts the IoU at.
+    lr_schedule: an optim.LRSchedule the captured update follows (None: the constant ``lr``). ema_decay > 0: the
+    masters get EMA twins (FlatParamGroups.enable_ema) the update averages into, and the EvalStep runs on them
+    (``forward_ema``: the working copies materialised from the EMA by the same launch)."""
     import lss_carla_amd as L
     from . import parallel, simbev, tools
     from .flat_params import FlatParamGroups, lss_backward_groups
@@ -214,14 +236,18 @@ def build_step(grid_conf, data_aug_conf, bsz, device, *, dtype="bf16", lr=1e-3, 
         loss_fn = tools.SimpleLoss(pos_weight).to(device)
     iou_thresholds = parse_thresholds(iou_thresholds)
     forward = flat.bind(model)
+    emas = flat.enable_ema() if ema_decay else None
+    forward_eval = flat.bind(model, source="ema") if emas is not None else forward
     step = TrainStep(forward, stager.inputs, stager.binimgs, loss_fn, opt, masters, all_reduce=False,
                      amp_dtype=amp_dtype, max_grad_norm=max_grad_norm, pre_step=None,
-                     skip_nonfinite=bool(skip_nonfinite), keep_preds=True)
-    evaluate = EvalStep(model, forward, stager.inputs, stager.binimgs, n_valid=stager.n_valid,
+                     skip_nonfinite=bool(skip_nonfinite), keep_preds=True, lr_schedule=lr_schedule, ema=emas,
+                     ema_decay=float(ema_decay) if emas is not None else 0.999, ema_warmup=bool(ema_warmup))
+    evaluate = EvalStep(model, forward_eval, stager.inputs, stager.binimgs, n_valid=stager.n_valid,
                         pos_weight=pos_weight, amp_dtype=amp_dtype, n_samples=n_val,
                         loss=loss_fn if loss == "focal" else None, thresholds=iou_thresholds)
     return {"model": model, "flat": flat, "masters": masters, "opt": opt, "stager": stager, "step": step,
-            "evaluate": evaluate, "loss_fn": loss_fn, "forward": forward, "label_groups": label_groups}
+            "evaluate": evaluate, "loss_fn": loss_fn, "forward": forward, "label_groups": label_groups,
+            "emas": emas, "forward_eval": forward_eval}
 
 
 def train(
@@ -270,6 +296,13 @@ def train(
     focal_gamma=2.0,
     focal_alpha=None,
     iou_thresholds=None,
+    lr_schedule="constant",
+    warmup_steps=0,
+    warmup_factor=0.0,
+    lr_min=0.0,
+    lr_total_steps=None,
+    ema_decay=0.0,
+    ema_warmup=True,
 ):
     """Train LiftSplatShoot on a SimBEV tree; the reference's arguments (train_simbev.py:23-98) plus:
 
@@ -289,6 +322,15 @@ def train(
     probability thresholds; validation then also counts the IoU at each, and the ``val`` events carry ``iou_max``,
     ``iou_max_per_class`` and ``best_threshold_per_class``. ``model_best.pt`` is chosen by ``iou`` (at 0.5) all the
     same. With either option metrics.jsonl starts with a ``config`` event naming the loss and the ladder.
+    lr_schedule: "constant", "linear" or "cosine" (optim.LRSchedule): a linear warm-up over warmup_steps updates from
+    lr * warmup_factor, then the decay to lr_min (absolute) at update lr_total_steps (default: the run's length,
+    nepochs * batches per epoch), flat afterwards. The captured update computes the rate on the device from Adam's
+    own step count, so a skipped step does not advance the schedule and a resumed run continues it; the ``train``
+    events then carry ``lr``. ema_decay > 0: an exponential moving average of the weights, kept by the same
+    optimizer pass (ema_warmup: decay min(ema_decay, (1 + t) / (10 + t))); validation then runs on the averaged
+    weights (``val`` events carry ``"weights": "ema"``, ``model_best.pt`` is chosen by that IoU) and checkpoints gain
+    ``ema_state_dict``. With either, metrics.jsonl starts with the ``config`` event. Argument errors raise
+    ValueError before anything is looked for or built.
     Returns a summary dict (counter, epoch, best_val_iou, skipped, frames_per_s of the training steps)."""
     from . import checkpoint, simbev, tools
 
@@ -297,6 +339,8 @@ def train(
     label_groups, n_out, pos_weight = _class_setup(label_groups, pos_weight)
     if focal is not None:
         tools.focal_rows(n_out, **focal)  # (argument errors come before anything is looked for or built)
+    sched_on = _schedule_setup(lr, lr_schedule, warmup_steps, warmup_factor, lr_min, lr_total_steps, ema_decay)
+    ema_on = float(ema_decay) > 0.0
     if gpuid < 0 or not torch.cuda.is_available():
         raise RuntimeError("lss_carla_amd.trainer: needs an MI355X (the hot path has no CPU fallback)")
     if ncams != len(simbev.CAMERA_ORDER):
@@ -323,9 +367,14 @@ def train(
             config["focal_gamma"], config["focal_alpha"] = focal_gamma, focal_alpha
             if focal_alpha is not None:
                 config["pos_weight"] = None  # (alpha sets the class balance)
+    if sched_on:
+        config.update({"lr_schedule": lr_schedule, "warmup_steps": int(warmup_steps), "warmup_factor": float(warmup_factor),
+                       "lr_min": float(lr_min), "lr_total_steps": lr_total_steps})
+    if ema_on:
+        config.update({"ema_decay": float(ema_decay), "ema_warmup": bool(ema_warmup)})
     log = _Log(logdir, use_wandb, {"project": wandb_project, "name": wandb_name, "entity": wandb_entity}, config)
 
-    if "loss" in config:
+    if "loss" in config and not (sched_on or ema_on):
         log.event("config", 0, **config)
 
     device = torch.device(f"cuda:{gpuid}")
@@ -342,12 +391,22 @@ def train(
     if cycle_batches:
         train_raw = _Cycle(train_raw, int(cycle_batches))
     n_val = len(valloader.dataset)
+    schedule = None
+    if sched_on:
+        from .optim import LRSchedule
+        if lr_total_steps is None:
+            lr_total_steps = config["lr_total_steps"] = int(nepochs) * len(train_raw)
+        schedule = LRSchedule(lr_schedule, warmup_steps, warmup_factor, lr_total_steps, float(lr_min) / float(lr))
+    if sched_on or ema_on:
+        log.event("config", 0, **config)  # (the schedule's length is known only now)
     print(f"Train batches: {len(train_raw)}  Val batches: {len(val_raw)}  device {device}  graph {bool(graph)} {dtype}")
 
     ctx = build_step(grid_conf, data_aug_conf, bsz, device, dtype=dtype, lr=lr, weight_decay=weight_decay,
                      max_grad_norm=max_grad_norm, pos_weight=pos_weight, skip_nonfinite=skip_nonfinite,
                      n_val=n_val, label_groups=label_groups, loss=loss, focal_gamma=focal_gamma,
-                     focal_alpha=focal_alpha, iou_thresholds=iou_thresholds)
+                     focal_alpha=focal_alpha, iou_thresholds=iou_thresholds, lr_schedule=schedule,
+                     ema_decay=float(ema_decay), ema_warmup=ema_warmup)
+    emas = ctx["emas"]
     model, flat, masters, opt = ctx["model"], ctx["flat"], ctx["masters"], ctx["opt"]
     stager, step, evaluate = ctx["stager"], ctx["step"], ctx["evaluate"]
 
@@ -361,7 +420,8 @@ def train(
 
     def snapshot():
         return ([t.detach().clone() for t in model.state_dict().values()],
-                [{k: v.detach().clone() for k, v in opt.state[m].items()} for m in masters])
+                [{k: v.detach().clone() for k, v in opt.state[m].items()} for m in masters],
+                [e.clone() for e in emas or []])
 
     def restore(snap):
         with torch.no_grad():
@@ -370,6 +430,8 @@ def train(
             for m, st in zip(masters, snap[1]):
                 for k, v in st.items():
                     opt.state[m][k].copy_(v)
+            for e, s in zip(emas or [], snap[2]):
+                e.copy_(s)
             if step.skipped is not None:
                 step.skipped.zero_()
 
@@ -434,7 +496,8 @@ def train(
                     stager.stage(nxt)
             if counter % loss_step == 0:
                 last_loss = float(loss.item())
-                log.event("train", counter, epoch=epoch, loss=last_loss)
+                extra = {"lr": float(step.lr.item())} if schedule is not None else {}
+                log.event("train", counter, epoch=epoch, loss=last_loss, **extra)
             if counter % iou_step == 0:
                 extra = {}
                 if n_out > 1:
@@ -456,6 +519,8 @@ def train(
                 extra = {"iou_per_class": info["iou_per_class"]} if n_out > 1 else {}
                 if iou_thresholds is not None:
                     extra.update({k: info[k] for k in ("iou_max", "iou_max_per_class", "best_threshold_per_class")})
+                if ema_on:
+                    extra["weights"] = "ema"
                 log.event("val", counter, epoch=epoch, loss=info["loss"], iou=info["iou"], **extra)
                 if info["iou"] > best_val_iou:
                     best_val_iou = info["iou"]
@@ -540,6 +605,16 @@ def main(argv=None):
     p.add_argument("--iou_thresholds", type=str, default=None,
                    help="validation also reports the IoU at these probability thresholds and the best per class: "
                         "0.35,0.4,0.45,0.5,0.55,0.6,0.65")
+    p.add_argument("--lr_schedule", default="constant", choices=["constant", "linear", "cosine"],
+                   help="the decay after the warm-up, computed on the device from Adam's step count")
+    p.add_argument("--warmup_steps", type=int, default=0, help="linear warm-up over this many updates")
+    p.add_argument("--warmup_factor", type=float, default=0.0, help="the warm-up starts at lr * this")
+    p.add_argument("--lr_min", type=float, default=0.0, help="the learning rate the decay ends at (absolute)")
+    p.add_argument("--lr_total_steps", type=int, default=None,
+                   help="the update the decay ends at (default: nepochs * batches per epoch)")
+    p.add_argument("--ema_decay", type=float, default=0.0,
+                   help="> 0: keep an EMA of the weights; validation and model_best.pt use it")
+    p.add_argument("--ema_warmup", type=int, default=1, help="EMA decay min(ema_decay, (1 + t) / (10 + t))")
     a = p.parse_args(argv)
     return train(dataroot=a.dataroot, nepochs=a.nepochs, gpuid=a.gpuid, H=a.H, W=a.W, final_dim=(a.final_h, a.final_w),
                  ncams=a.ncams, bsz=a.bsz, nworkers=a.nworkers, lr=a.lr, weight_decay=a.weight_decay, logdir=a.logdir,
@@ -552,7 +627,9 @@ def main(argv=None):
                  else (None if a.loss == "focal" else 2.13), loss=a.loss,
                  focal_gamma=parse_per_class(a.focal_gamma, "--focal_gamma"),
                  focal_alpha=None if a.focal_alpha is None else parse_per_class(a.focal_alpha, "--focal_alpha"),
-                 iou_thresholds=parse_thresholds(a.iou_thresholds))
+                 iou_thresholds=parse_thresholds(a.iou_thresholds), lr_schedule=a.lr_schedule,
+                 warmup_steps=a.warmup_steps, warmup_factor=a.warmup_factor, lr_min=a.lr_min,
+                 lr_total_steps=a.lr_total_steps, ema_decay=a.ema_decay, ema_warmup=bool(a.ema_warmup))
 
 
 if __name__ == "__main__":

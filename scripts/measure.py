@@ -30,6 +30,9 @@ Steps:
                                       Predictor at c3 sizes, norm.USE_HIP_BN_EVAL on / off alternately, bsz 8 and 1); the
                                       default training line on each side; kernel traces of the Predictor, switch on and
                                       off, in runs of their own: infer.json, infer_kernels.txt
+  bench_ab:PARENT_DIR[:RUNS]          the default ``python bench.py`` line on a checkout of the parent commit (library built
+                                      there) and on this tree alternately, RUNS (3) each: bench_parent_<i>.json,
+                                      bench_this_<i>.json, bench_ab.txt
   lib:VARIANT                         later steps load lss-carla_amd/variants/VARIANT.so (product: the default)
 """
 from __future__ import annotations
@@ -339,6 +342,40 @@ def step_infer(out, spec):
     return 0
 
 
+def step_bench_ab(out, spec):
+    """bench_ab:PARENT_DIR[:RUNS] -- the default ``python bench.py`` line on a checkout of the parent commit (PARENT_DIR,
+    with its own build of the library) and on this tree alternately, RUNS (3) fresh processes each; every JSON line is
+    kept as bench_parent_<i>.json / bench_this_<i>.json, and bench_ab.txt says whether this tree's runs lie inside the
+    parent's run-to-run spread."""
+    import json
+    parent, _, runs = spec.partition(":")
+    parent, runs = os.path.abspath(parent), int(runs or 3)
+    vals = {"parent": [], "this": []}
+    for i in range(1, runs + 1):
+        for side, cwd in (("parent", parent), ("this", REPO)):
+            log = os.path.join(out, f"bench_{side}_{i}.log")
+            rc = run([PY, "-u", "bench.py"], log, 400, cwd=cwd)
+            last = tail(log, 1).strip()
+            if rc != 0 or not last.startswith("{"):
+                print(tail(log, 15), flush=True)
+                return rc or 1
+            with open(os.path.join(out, f"bench_{side}_{i}.json"), "w") as fh:
+                fh.write(last + "\n")
+            got = json.loads(last)
+            vals[side].append(got.get("value"))
+            print(f"  {side} {i}: {got.get('value')} {got.get('unit', '')} ({got.get('ms_per_step')} ms / step)", flush=True)
+    lo, hi = min(vals["parent"]), max(vals["parent"])
+    inside = [lo <= v <= hi for v in vals["this"]]
+    lines = [f"python bench.py, parent tree and this tree alternately, {runs} fresh processes each, one MI355X, one session",
+             "parent: " + " ".join(f"{v:.3f}" for v in vals["parent"]) + f"   (spread {lo:.3f} - {hi:.3f})",
+             "this:   " + " ".join(f"{v:.3f}" for v in vals["this"]),
+             f"runs of this tree inside the parent's spread: {sum(inside)} of {len(inside)}"]
+    with open(os.path.join(out, "bench_ab.txt"), "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    print("\n".join(lines), flush=True)
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tag", required=True)
@@ -348,7 +385,7 @@ def main():
     os.makedirs(out, exist_ok=True)
     os.chdir(REPO)
     fns = {"tests": step_tests, "smoke": step_smoke, "bench": step_bench, "trace": step_trace, "pmc": step_pmc,
-           "kbench": step_kbench, "py": step_py, "train_loop": step_train_loop, "infer": step_infer}
+           "kbench": step_kbench, "py": step_py, "train_loop": step_train_loop, "infer": step_infer, "bench_ab": step_bench_ab}
     for s in a.steps:
         kind, _, spec = s.partition(":")
         print(f"== {s}", flush=True)

@@ -63,6 +63,23 @@ int lss_simbev_vehicle_mask(const uint8_t* bev, int32_t n, int32_t n_classes, in
 int lss_simbev_class_masks(const uint8_t* bev, int32_t n, int32_t n_classes, int32_t X, int32_t Y,
                            const uint32_t* group_bits, int32_t K, float* out, void* stream);
 
+/* (ABI 31) lss_simbev_class_masks under a BEV-space augmentation of the ego frame -- one rotation about z, one
+ * isotropic scale, flips of x and y, p' = A p -- applied to the labels as a nearest-neighbour gather in the same
+ * pass. index_mats: n x 6 fp32 in DEVICE memory, sample b's row-major 2 x 3 affine map from the centre of an
+ * output cell in index units, (i + 0.5, j + 0.5), to the source position in index units (for a grid of cell
+ * D = diag(dx, dy) and lower corner lo: M = D^-1 A2^-1 D, b = D^-1 (A2^-1 lo - lo), A2 the xy block of A). Row i of
+ * a label is x cell i, column j is y cell j, as the model's logits. With ci = i + 0.5f, cj = j + 0.5f:
+ *   su = (m00*ci + m01*cj) + m02;  sv = (m10*ci + m11*cj) + m12       each product and sum rounded once, fp32
+ *   inside = su >= 0 && su < X && sv >= 0 && sv < Y                   tested on the floats; a NaN is outside
+ *   out[b, k, i, j] = inside && any over c of group k of (bev[b, c, X-1-floor(su), floor(sv)] > 0)
+ * -- the X-1-. is lss_simbev_class_masks' flipud. A cell whose source falls outside the grid is 0: no camera point
+ * lands there (the corners past the grid under rotation, the ring past s times its half width). Every output
+ * element is written exactly once. The identity {1, 0, 0, 0, 1, 0} gives lss_simbev_class_masks' output bit for bit.
+ * -1 for what lss_simbev_class_masks refuses, for a NULL index_mats and for X or Y above 2^23 (i + 0.5 exact). */
+int lss_simbev_class_masks_warp(const uint8_t* bev, int32_t n, int32_t n_classes, int32_t X, int32_t Y,
+                                const uint32_t* group_bits, int32_t K, const float* index_mats, float* out,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif

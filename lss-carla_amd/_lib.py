@@ -18,7 +18,7 @@ DEBUG_LIB_PATH = os.path.join(_HERE, "liblss_hip_debug.so")  # LSS_DEBUG=1: devi
 
 F32, BF16 = 0, 1
 NCHW, NHWC = 0, 1
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 
 class Dims(ctypes.Structure):
@@ -93,6 +93,7 @@ SIGNATURES = {
     "lss_simbev_images": (ctypes.c_int, [_p, _i32, _i32, _i32, _p, _p, _i32, _i32, _p, _p]),
     "lss_simbev_vehicle_mask": (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _p, _p]),
     "lss_simbev_class_masks": (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _p, _i32, _p, _p]),
+    "lss_simbev_class_masks_warp": (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _p, _i32, _p, _p, _p]),
     # include/lss_convs.h (conv-stack kernels, same library)
     "lss_dwconv_arm": (ctypes.c_int, [_i32] * 13 + [ctypes.POINTER(DwArm)]),
     "lss_dwconv_fwd": (ctypes.c_int, [_p, _i32, _p] + [_i32] * 10 + [_p, _p]),

@@ -160,6 +160,44 @@ __global__ __launch_bounds__(kThreads) void k_class_masks(const uint8_t* __restr
         if (k < K) o[(size_t)k * XY] = (set & groups.bits[k]) ? 1.0f : 0.0f;
 }
 
+// k_class_masks under a BEV-space augmentation of the ego frame (rotation about z, isotropic scale, flips): a
+// nearest-neighbour gather. Sample b's index matrix m (2 x 3, row-major) takes the centre of output cell (i, j), in
+// index units, to its source position; the label is the source cell's, 0 where the position is outside the grid:
+//   su = (m00*ci + m01*cj) + m02, sv = (m10*ci + m11*cj) + m12 with ci = i + 0.5, cj = j + 0.5,
+//   out[b, k, i, j] = inside && any(bev[b, c, X-1-floor(su), floor(sv)] > 0 for c in group k).
+// Every product and sum is one correctly rounded fp32 operation in that order (no FMA: the numpy restatement of the
+// tests does the same five roundings). The range test is on the floats, before any conversion, and a NaN fails it;
+// su < X then bounds floor(su) by X - 1 (X, Y <= 2^23, the entry's check: i + 0.5 and (float)X are exact).
+// Thread = output cell, consecutive threads along j: coalesced writes; the reads are a rotated line of the source,
+// bytes of a 40-KB plane that stays in L2.
+__global__ __launch_bounds__(kThreads) void k_class_masks_warp(const uint8_t* __restrict__ bev, int ncls, int X, int Y,
+                                                               long total, ClassGroups groups, uint32_t used, int K,
+                                                               const float* __restrict__ mats,
+                                                               float* __restrict__ out) {
+    const long i = (long)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= total) return;
+    const long XY = (long)X * Y;
+    const long b = i / XY;
+    const long r = i - b * XY;
+    const int row = (int)(r / Y), col = (int)(r - (long)row * Y);
+    const float* m = mats + 6 * b;
+    const float ci = __fadd_rn((float)row, 0.5f), cj = __fadd_rn((float)col, 0.5f);
+    const float su = __fadd_rn(__fadd_rn(__fmul_rn(m[0], ci), __fmul_rn(m[1], cj)), m[2]);
+    const float sv = __fadd_rn(__fadd_rn(__fmul_rn(m[3], ci), __fmul_rn(m[4], cj)), m[5]);
+    const bool inside = su >= 0.0f && su < (float)X && sv >= 0.0f && sv < (float)Y;
+    uint32_t set = 0;
+    if (inside) {
+        const int si = (int)floorf(su), sj = (int)floorf(sv);
+        const uint8_t* s = bev + (size_t)b * ncls * XY + (size_t)(X - 1 - si) * Y + sj;
+        for (int c = 0; c < ncls; ++c)
+            if ((used >> c) & 1u) set |= (s[(size_t)c * XY] > 0 ? 1u : 0u) << c;
+    }
+    float* o = out + (size_t)b * K * XY + r;
+#pragma unroll
+    for (int k = 0; k < LSS_SIMBEV_MAX_GROUPS; ++k)
+        if (k < K) o[(size_t)k * XY] = (set & groups.bits[k]) ? 1.0f : 0.0f;
+}
+
 // ---- host: Pillow's bicubic coefficient tables (Resample.c precompute_coeffs / normalize_coeffs_8bpc)
 double bicubic_filter(double x) {
     const double a = -0.5;
@@ -167,6 +205,21 @@ double bicubic_filter(double x) {
     if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
     if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
     return 0.0;
+}
+
+// What both class-mask entries refuse, and the groups as the kernels take them (g, used = the union of the groups).
+bool class_mask_args(const uint8_t* bev, int n, int n_classes, int X, int Y, const uint32_t* group_bits, int K,
+                     const float* out, ClassGroups* g, uint32_t* used) {
+    if (!bev || !out || !group_bits || n <= 0 || n_classes <= 0 || n_classes > 32 || X <= 0 || Y <= 0 || K <= 0 ||
+        K > LSS_SIMBEV_MAX_GROUPS)
+        return false;
+    const uint32_t valid = n_classes == 32 ? 0xFFFFFFFFu : ((1u << n_classes) - 1u);
+    for (int k = 0; k < K; ++k) {
+        if (group_bits[k] == 0 || (group_bits[k] & ~valid)) return false;  // an empty group, a channel out of range
+        g->bits[k] = group_bits[k];
+        *used |= group_bits[k];
+    }
+    return true;
 }
 
 int ksize_of(int in_size, int out_size) {
@@ -243,20 +296,25 @@ int lss_simbev_vehicle_mask(const uint8_t* bev, int32_t n, int32_t n_classes, in
 
 int lss_simbev_class_masks(const uint8_t* bev, int32_t n, int32_t n_classes, int32_t X, int32_t Y,
                            const uint32_t* group_bits, int32_t K, float* out, void* stream) {
-    if (!bev || !out || !group_bits || n <= 0 || n_classes <= 0 || n_classes > 32 || X <= 0 || Y <= 0 || K <= 0 ||
-        K > LSS_SIMBEV_MAX_GROUPS)
-        return -1;
-    const uint32_t valid = n_classes == 32 ? 0xFFFFFFFFu : ((1u << n_classes) - 1u);
     ClassGroups g{};
     uint32_t used = 0;
-    for (int k = 0; k < K; ++k) {
-        if (group_bits[k] == 0 || (group_bits[k] & ~valid)) return -1;  // an empty group, a channel out of range
-        g.bits[k] = group_bits[k];
-        used |= group_bits[k];
-    }
+    if (!class_mask_args(bev, n, n_classes, X, Y, group_bits, K, out, &g, &used)) return -1;
     const long total = (long)n * X * Y;
     hipLaunchKernelGGL(k_class_masks, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0,
                        (hipStream_t)stream, bev, n_classes, X, Y, total, g, used, K, out);
+    return launch_status();
+}
+
+int lss_simbev_class_masks_warp(const uint8_t* bev, int32_t n, int32_t n_classes, int32_t X, int32_t Y,
+                                const uint32_t* group_bits, int32_t K, const float* index_mats, float* out,
+                                void* stream) {
+    ClassGroups g{};
+    uint32_t used = 0;
+    if (!class_mask_args(bev, n, n_classes, X, Y, group_bits, K, out, &g, &used) || !index_mats) return -1;
+    if (X > (1 << 23) || Y > (1 << 23)) return -1;  // i + 0.5 and (float)X exact: the range test bounds the gather
+    const long total = (long)n * X * Y;
+    hipLaunchKernelGGL(k_class_masks_warp, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+                       (hipStream_t)stream, bev, n_classes, X, Y, total, g, used, K, index_mats, out);
     return launch_status();
 }
 

@@ -89,6 +89,92 @@ def post_homography(resize, crop, flip, rotate):
     return post_rot_3, post_tran_3
 
 
+# ----------------------------------------------------------------------------- BEV-space augmentation (host)
+# One transform of the ego frame per sample, A = s * Rz(theta) * diag(fx, fy, 1) with fx, fy in {+1, -1}, applied
+# to ego-frame points as p' = A p (z is scaled by s too). The rig takes it as rots' = A rots, trans' = A trans, so
+# the frustum points move with it; the labels take it as a nearest-neighbour gather (class_masks, index_mats=).
+BEV_AUG_IDENTITY = (0.0, 1.0, False, False)
+
+
+def _bev_aug_lims(conf: dict):
+    """(rot_lim, scale_lim, flip) of a data_aug_conf: the keys bev_rot_lim (degrees), bev_scale_lim, bev_flip, absent
+    ones neutral; ValueError for a pair that is not finite and ascending or a scale that is not positive."""
+    rot = tuple(float(v) for v in conf.get("bev_rot_lim", (0.0, 0.0)))
+    scale = tuple(float(v) for v in conf.get("bev_scale_lim", (1.0, 1.0)))
+    for name, lim in (("bev_rot_lim", rot), ("bev_scale_lim", scale)):
+        if len(lim) != 2 or not all(math.isfinite(v) for v in lim) or lim[0] > lim[1]:
+            raise ValueError(f"{name} {lim!r}: a finite (lo, hi) with lo <= hi")
+    if scale[0] <= 0.0:
+        raise ValueError(f"bev_scale_lim {scale!r}: positive scales")
+    return rot, scale, bool(conf.get("bev_flip", False))
+
+
+def bev_aug_enabled(conf: dict) -> bool:
+    """Whether a data_aug_conf asks for the BEV-space augmentation: any of bev_rot_lim / bev_scale_lim / bev_flip
+    present and not neutral ((0, 0), (1, 1), False). The training and the validation samples of such a conf carry
+    the label index matrix (SimBEVDataset.__getitem__), and this is the flag their consumers are given."""
+    rot, scale, flip = _bev_aug_lims(conf)
+    return rot != (0.0, 0.0) or scale != (1.0, 1.0) or flip
+
+
+def draw_bev_augmentation(conf: dict, train: bool):
+    """One sample's BEV-space augmentation (theta_deg, scale, flip_x, flip_y). Off -- validation, or a conf that does
+    not ask for it -- it is the identity and draws nothing. On, it draws from np.random, after the sample's other
+    draws: theta ~ U(bev_rot_lim), scale ~ U(bev_scale_lim), then the x coin and the y coin only when bev_flip is on."""
+    if not train or not bev_aug_enabled(conf):
+        return BEV_AUG_IDENTITY
+    rot, scale, flip = _bev_aug_lims(conf)
+    rnd = np.random
+    theta = float(rnd.uniform(*rot))
+    s = float(rnd.uniform(*scale))
+    flip_x = bool(flip and rnd.choice([0, 1]))
+    flip_y = bool(flip and rnd.choice([0, 1]))
+    return theta, s, flip_x, flip_y
+
+
+def bev_aug_matrix(theta_deg, scale, flip_x, flip_y) -> np.ndarray:
+    """A = scale * Rz(theta) * diag(fx, fy, 1) as (3, 3) fp32: built in float64, rounded once."""
+    t = math.radians(float(theta_deg))
+    c, s = math.cos(t), math.sin(t)
+    rz = np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]], dtype=np.float64)
+    f = np.diag([-1.0 if flip_x else 1.0, -1.0 if flip_y else 1.0, 1.0])
+    return (float(scale) * (rz @ f)).astype(np.float32)
+
+
+def compose_rig(A, rots: torch.Tensor, trans: torch.Tensor):
+    """The rig in the augmented ego frame: (A @ rots, A @ trans) for rots (..., 3, 3) and trans (..., 3), fp32 on the
+    host -- camera points then land at A (R x + t). intrins / post_rots / post_trans are not touched (nor are the
+    host inverses ops.HostInverses takes of them)."""
+    A = torch.as_tensor(np.asarray(A), dtype=torch.float32)
+    return A.matmul(rots), A.matmul(trans.unsqueeze(-1)).squeeze(-1)
+
+
+def label_index_matrix(A, grid_conf: dict) -> np.ndarray:
+    """The (2, 3) fp32 affine map of the label warp under A: from the centre of output cell (i, j) in index units,
+    (i + 0.5, j + 0.5), to the source position in index units -- row i of a label is x cell i, column j is y cell j,
+    the layout of the model's logits. With A2 the xy block of A, D = diag(dx, dy) and lo = bx - dx / 2 (ops.GridSpec):
+    M = D^-1 A2^-1 D and b = D^-1 (A2^-1 lo - lo), in float64, rounded once. ValueError for a non-finite or singular A."""
+    a = np.asarray(A, dtype=np.float64)
+    if a.shape != (3, 3) or not np.isfinite(a).all():
+        raise ValueError(f"label_index_matrix: a finite (3, 3) matrix, got {a!r}")
+    det = a[0, 0] * a[1, 1] - a[0, 1] * a[1, 0]
+    if det == 0.0 or not math.isfinite(1.0 / det):
+        raise ValueError(f"label_index_matrix: the xy block of {a!r} is singular")
+    inv = np.array([[a[1, 1], -a[0, 1]], [-a[1, 0], a[0, 0]]], dtype=np.float64) / det
+    from .ops import GridSpec
+    gs = GridSpec.from_conf(grid_conf)
+    d = np.array(gs.dx[:2], dtype=np.float64)
+    lo = np.array(gs.lo[:2], dtype=np.float64)
+    out = np.empty((2, 3), dtype=np.float64)
+    for r in range(2):
+        for c in range(2):
+            out[r, c] = inv[r, c] * d[c] / d[r]
+        out[r, 2] = ((inv[r, 0] * lo[0] + inv[r, 1] * lo[1]) - lo[r]) / d[r]
+    if not np.isfinite(out).all():
+        raise ValueError(f"label_index_matrix: {a!r} has no finite inverse map")
+    return out.astype(np.float32)
+
+
 def rotation_mode(angle: float, w: int, h: int) -> Tuple[int, Tuple[int, ...]]:
     """(rot_mode, 16.16 affine coefficients) for Image.rotate(angle) of a w x h image (NEAREST,
     expand=False): the fast paths of Image.rotate, else its inverse matrix (Python doubles, as
@@ -265,13 +351,23 @@ def group_bits(label_groups, n_classes: int = 32) -> List[int]:
     return bits
 
 
-def class_masks(bev_u8: torch.Tensor, label_groups=None, out=None) -> torch.Tensor:
+VEHICLE_GROUPS = [[1, 2, 3]]  # get_binimg's merge (src/data_simbev.py:236-244) as label groups
+
+
+def class_masks(bev_u8: torch.Tensor, label_groups=None, out=None, index_mats=None, keep=None) -> torch.Tensor:
     """(n, C, X, Y) uint8 device BEV maps -> (n, K, X, Y) fp32 labels, one channel per group of
     ``label_groups`` (K lists of npz channel indices): out[:, k] = flipud(any(bev[:, c] > 0 for c in group
     k)), ``lss_simbev_class_masks``. None: the reference's single vehicle mask [[1, 2, 3]] through
-    ``vehicle_masks``, as before. out: a contiguous fp32 device tensor of n * K * X * Y elements to write."""
+    ``vehicle_masks``, as before. out: a contiguous fp32 device tensor of n * K * X * Y elements to write.
+
+    index_mats: (n, 2, 3) fp32, host or device -- each sample's ``label_index_matrix``: the labels under the
+    BEV-space augmentation, gathered by ``lss_simbev_class_masks_warp`` (nearest neighbour, 0 outside the grid);
+    label_groups None is then [[1, 2, 3]] through that kernel. keep: a list that receives the device copy of host
+    matrices -- a caller on a side stream holds it until its event, as with ``augment_images``."""
     if label_groups is None:
-        return vehicle_masks(bev_u8, out=out)
+        if index_mats is None:
+            return vehicle_masks(bev_u8, out=out)
+        label_groups = VEHICLE_GROUPS
     if not bev_u8.is_cuda:
         raise RuntimeError("lss_carla_amd.simbev: BEV maps must be on the MI355X (no CPU fallback)")
     if bev_u8.dtype == torch.bool:
@@ -288,9 +384,24 @@ def class_masks(bev_u8: torch.Tensor, label_groups=None, out=None) -> torch.Tens
         raise RuntimeError(f"out= must be a contiguous fp32 device tensor of {(n, K, X, Y)}")
     b = bev_u8.contiguous()
     host = (ctypes.c_uint32 * K)(*bits)
-    _lib.check(_lib.load().lss_simbev_class_masks(_lib.ptr(b), n, C, X, Y, ctypes.cast(host, ctypes.c_void_p), K,
-                                                  _lib.ptr(out), _lib.stream_handle(b.device)),
-               "lss_simbev_class_masks")
+    if index_mats is None:
+        _lib.check(_lib.load().lss_simbev_class_masks(_lib.ptr(b), n, C, X, Y, ctypes.cast(host, ctypes.c_void_p), K,
+                                                      _lib.ptr(out), _lib.stream_handle(b.device)),
+                   "lss_simbev_class_masks")
+        return out
+    mats = torch.as_tensor(index_mats)
+    if mats.dtype != torch.float32 or tuple(mats.shape) != (n, 2, 3):
+        raise RuntimeError(f"index_mats= must be {(n, 2, 3)} fp32, got {mats.dtype} {tuple(mats.shape)}")
+    if not mats.is_cuda:
+        mats = mats.contiguous().pin_memory().to(b.device, non_blocking=True)
+    elif mats.device != b.device:
+        raise RuntimeError(f"index_mats= is on {mats.device}, the BEV maps on {b.device}")
+    mats = mats.contiguous()
+    if keep is not None:
+        keep.extend([mats, b])
+    _lib.check(_lib.load().lss_simbev_class_masks_warp(_lib.ptr(b), n, C, X, Y, ctypes.cast(host, ctypes.c_void_p), K,
+                                                       _lib.ptr(mats), _lib.ptr(out), _lib.stream_handle(b.device)),
+               "lss_simbev_class_masks_warp")
     return out
 
 
@@ -309,6 +420,9 @@ class SimBEVDataset(torch.utils.data.Dataset):
         from .tools import gen_dx_bx
         dx, bx, nx = gen_dx_bx(grid_conf["xbound"], grid_conf["ybound"], grid_conf["zbound"])
         self.dx, self.bx, self.nx = dx.numpy(), bx.numpy(), nx.numpy()
+        # the conf asks for the BEV-space augmentation: every sample (validation's too, with the identity) then
+        # carries its label index matrix directly before the BEV map
+        self.bev_aug = bev_aug_enabled(data_aug_conf)
         print(self)
 
     def _load_all_samples(self):
@@ -343,10 +457,21 @@ class SimBEVDataset(torch.utils.data.Dataset):
         fit-to-width scale, the mean bottom fraction and a centred window."""
         return draw_augmentation(self.data_aug_conf, self.is_train)
 
+    def sample_bev_augmentation(self):
+        """(theta_deg, scale, flip_x, flip_y) of one sample's BEV-space augmentation (draw_bev_augmentation): drawn
+        after sample_augmentation's values; the identity, and no draw, for validation or a conf without it."""
+        return draw_bev_augmentation(self.data_aug_conf, self.is_train)
+
     def get_image_data(self, sample, cam_indices):
-        """Decoded images and calibration (src/data_simbev.py:147-218 without the pixel work)."""
+        """Decoded images and calibration (src/data_simbev.py:147-218 without the pixel work); with the BEV-space
+        augmentation on, rots / trans are the composed ones (compose_rig)."""
+        return self._image_data(sample, cam_indices)[0]
+
+    def _image_data(self, sample, cam_indices):
+        """(get_image_data's tuple, the sample's label index matrix (2, 3) or None without the BEV augmentation)."""
         from PIL import Image
         resize, resize_dims, crop, flip, rotate = self.sample_augmentation()
+        bev_aug = self.sample_bev_augmentation() if self.bev_aug else None
         imgs, rots, trans, intrins, post_rots, post_trans = [], [], [], [], [], []
         for cam_idx in cam_indices:
             img = Image.open(self.dataroot / sample["images"][cam_idx]).convert("RGB")
@@ -360,13 +485,25 @@ class SimBEVDataset(torch.utils.data.Dataset):
             post_trans.append(pt)
         aug = torch.tensor([resize_dims[0], resize_dims[1], crop[0], crop[1], crop[2], crop[3], int(flip)],
                            dtype=torch.int64)
-        return (torch.stack(imgs), torch.stack(rots), torch.stack(trans), torch.stack(intrins),
-                torch.stack(post_rots), torch.stack(post_trans), aug, torch.tensor(float(rotate), dtype=torch.float64))
+        rots, trans, index_mat = torch.stack(rots), torch.stack(trans), None
+        if bev_aug is not None:
+            A = bev_aug_matrix(*bev_aug)
+            if tuple(bev_aug) != BEV_AUG_IDENTITY:  # (validation: the rig as it is, the identity for the labels)
+                rots, trans = compose_rig(A, rots, trans)
+            index_mat = torch.from_numpy(label_index_matrix(A, self.grid_conf))
+        return (torch.stack(imgs), rots, trans, torch.stack(intrins), torch.stack(post_rots), torch.stack(post_trans),
+                aug, torch.tensor(float(rotate), dtype=torch.float64)), index_mat
 
     def get_bev_raw(self, sample):
         """The BEV npz's (n_classes, X, Y) map as uint8 (value > 0 kept), src/data_simbev.py:227-232."""
         bev = np.load(sample["meta_dir"] / sample["bev"])["bev"]
         return torch.from_numpy((bev > 0).astype(np.uint8) if bev.dtype != np.uint8 else bev.copy())
+
+    def _labels(self, sample, index_mat):
+        """The sample's tail: the BEV map, last, and directly before it the label index matrix when the conf asks
+        for the BEV-space augmentation."""
+        bev = self.get_bev_raw(sample)
+        return (bev,) if index_mat is None else (index_mat, bev)
 
     def choose_cams(self):
         all_cams = list(range(len(CAMERA_ORDER)))
@@ -386,27 +523,32 @@ class SimBEVDataset(torch.utils.data.Dataset):
 class VizData(SimBEVDataset):
     def __getitem__(self, index):
         sample = self.samples[index]
-        raw = self.get_image_data(sample, self.choose_cams())
-        return raw + (torch.empty(3, 0), self.get_bev_raw(sample))
+        raw, index_mat = self._image_data(sample, self.choose_cams())
+        return raw + (torch.empty(3, 0),) + self._labels(sample, index_mat)
 
 
 class SegmentationData(SimBEVDataset):
     def __getitem__(self, index):
         sample = self.samples[index]
-        raw = self.get_image_data(sample, self.choose_cams())
-        return raw + (self.get_bev_raw(sample),)
+        raw, index_mat = self._image_data(sample, self.choose_cams())
+        return raw + self._labels(sample, index_mat)
 
 
 def worker_rnd_init(x):
     np.random.seed(13 + x)  # src/data_simbev.py:310-312
 
 
-def finish_batch(batch, final_dim, device, label_groups=None):
+def finish_batch(batch, final_dim, device, label_groups=None, bev_aug=False):
     """A collated raw batch -> the reference's (imgs, rots, trans, intrins, post_rots, post_trans,
     [lidar,] binimgs) on `device`, the pixel work done by the HIP kernels. label_groups: K lists of BEV
-    channels -> binimgs (B, K, X, Y) (class_masks); None: the reference's vehicle mask, (B, 1, X, Y)."""
+    channels -> binimgs (B, K, X, Y) (class_masks); None: the reference's vehicle mask, (B, 1, X, Y).
+    bev_aug: the batch comes from a conf with the BEV-space augmentation (bev_aug_enabled): the element before
+    the BEV maps is the (B, 2, 3) label index matrices, which warp the labels; the rig is already composed."""
     imgs_u8, rots, trans, intrins, post_rots, post_trans, aug, rot = batch[:8]
     rest = batch[8:]
+    index_mats = None
+    if bev_aug:
+        index_mats, rest = rest[-2], tuple(rest[:-2]) + tuple(rest[-1:])
     B, N = imgs_u8.shape[:2]
     src = imgs_u8.reshape(B * N, *imgs_u8.shape[2:]).to(device, non_blocking=True)
     augs = []
@@ -422,16 +564,16 @@ def finish_batch(batch, final_dim, device, label_groups=None):
     out[4]._lss_host, out[4]._lss_host_version = post_rots, out[4]._version
     for t in rest[:-1]:
         out.append(t)  # lidar placeholder (VizData)
-    out.append(class_masks(rest[-1].to(device, non_blocking=True), label_groups))
+    out.append(class_masks(rest[-1].to(device, non_blocking=True), label_groups, index_mats=index_mats))
     return tuple(out)
 
 
 class DeviceLoader:
     """Iterates a DataLoader of raw samples and yields finished device batches (finish_batch)."""
 
-    def __init__(self, loader, final_dim, device, label_groups=None):
+    def __init__(self, loader, final_dim, device, label_groups=None, bev_aug=False):
         self.loader, self.final_dim, self.device = loader, final_dim, torch.device(device)
-        self.label_groups = label_groups
+        self.label_groups, self.bev_aug = label_groups, bool(bev_aug)
         self.dataset = loader.dataset
         self.batch_size = loader.batch_size
 
@@ -440,13 +582,17 @@ class DeviceLoader:
 
     def __iter__(self):
         for batch in self.loader:
-            yield finish_batch(batch, self.final_dim, self.device, self.label_groups)
+            yield finish_batch(batch, self.final_dim, self.device, self.label_groups, self.bev_aug)
 
 
 def compile_data(version, dataroot, data_aug_conf, grid_conf, bsz, nworkers, parser_name, device="cuda",
                  label_groups=None):
     """src/data_simbev.py:315-354 with the same loaders' settings; returns DeviceLoaders. label_groups: the
-    BEV channel groups of a multi-class model's labels (finish_batch); None: the reference's vehicle mask."""
+    BEV channel groups of a multi-class model's labels (finish_batch); None: the reference's vehicle mask.
+    A data_aug_conf with bev_rot_lim / bev_scale_lim / bev_flip (bev_aug_enabled) adds the BEV-space augmentation to
+    the training loader -- the rig composed, the labels warped -- and never to the validation loader; both loaders
+    carry the flag (``bev_aug``) that says their raw batches hold the label index matrices."""
+    bev_aug = bev_aug_enabled(data_aug_conf)  # (a bad limit fails here)
     if label_groups is not None:
         group_bits(label_groups)  # a bad group list fails here, not in the first batch
     parser = {"vizdata": VizData, "segmentationdata": SegmentationData}[parser_name]
@@ -457,4 +603,5 @@ def compile_data(version, dataroot, data_aug_conf, grid_conf, bsz, nworkers, par
     valloader = torch.utils.data.DataLoader(valdata, batch_size=bsz, shuffle=False, num_workers=nworkers,
                                             pin_memory=True)
     fd = data_aug_conf["final_dim"]
-    return DeviceLoader(trainloader, fd, device, label_groups), DeviceLoader(valloader, fd, device, label_groups)
+    return (DeviceLoader(trainloader, fd, device, label_groups, bev_aug),
+            DeviceLoader(valloader, fd, device, label_groups, bev_aug))

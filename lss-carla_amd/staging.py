@@ -7,7 +7,8 @@ are valid. ``BatchStager`` owns those tensors and fills them from the raw batche
 
   stage(raw)   on the staging stream: H2D copies of the uint8 images / BEV and of the rig, then
                ``lss_simbev_images`` and ``lss_simbev_vehicle_mask`` (``lss_simbev_class_masks`` with
-               ``label_groups``) straight into the next of two slots;
+               ``label_groups``; ``lss_simbev_class_masks_warp`` with ``bev_aug``: the batch's label index
+               matrices, uploaded on the same stream) straight into the next of two slots;
                an event marks the slot ready. Batch k+1 is staged while step k runs.
   commit()     on the current stream: wait for the oldest staged slot's event, copy slot -> static tensors
                (device to device), ``HostInverses.update`` with the slot's host post_rots / intrins, set
@@ -55,9 +56,11 @@ class BatchStager:
     RIG = ("rots", "trans", "intrins", "post_rots", "post_trans")
 
     def __init__(self, final_dim: Sequence[int], B: int, N: int, src_hw: Sequence[int], grid: dict, device,
-                 label_groups=None):
+                 label_groups=None, bev_aug=False):
         """label_groups: K lists of BEV channels, one label channel each (simbev.class_masks): ``binimgs`` and
-        both slots are (B, K, X, Y); None: the reference's vehicle mask, K = 1."""
+        both slots are (B, K, X, Y); None: the reference's vehicle mask, K = 1. bev_aug: the raw batches come from a
+        conf with the BEV-space augmentation (simbev.bev_aug_enabled): the element before the BEV maps is the
+        (b, 2, 3) label index matrices, which warp the labels; the rig arrives composed."""
         dev = torch.device(device)
         if dev.type != "cuda":
             raise RuntimeError("BatchStager: the static tensors live on the MI355X (no CPU fallback)")
@@ -73,6 +76,7 @@ class BatchStager:
         if label_groups is not None:
             simbev.group_bits(label_groups)
         self.label_groups = None if label_groups is None else [list(g) for g in label_groups]
+        self.bev_aug = bool(bev_aug)
         K = 1 if label_groups is None else len(self.label_groups)
         self.binimgs = torch.zeros(B, K, X, Y, device=dev, dtype=torch.float32)
         self.n_valid = torch.full((1,), B, device=dev, dtype=torch.int32)
@@ -100,6 +104,7 @@ class BatchStager:
             raise RuntimeError("BatchStager.stage: both slots hold uncommitted batches (commit() first)")
         imgs_u8, rots, trans, intrins, post_rots, post_trans, aug, rot = raw_batch[:8]
         bev = raw_batch[-1]
+        index_mats = raw_batch[-2] if self.bev_aug else None
         b, N = int(imgs_u8.shape[0]), int(imgs_u8.shape[1])
         slot = self._slots[self._next]
         if not 0 < b <= self.B or N != self.N or tuple(imgs_u8.shape[2:]) != tuple(slot.u8.shape[1:]):
@@ -110,6 +115,10 @@ class BatchStager:
         if bev.dtype != torch.uint8 or bev.dim() != 4 or tuple(bev.shape[2:]) != tuple(slot.binimgs.shape[2:]):
             raise RuntimeError(f"BatchStager.stage: BEV maps {bev.dtype} {tuple(bev.shape)} against labels "
                                f"{tuple(slot.binimgs.shape)}")
+        if index_mats is not None and (index_mats.dtype != torch.float32 or tuple(index_mats.shape) != (b, 2, 3)):
+            raise RuntimeError(f"BatchStager.stage: label index matrices {index_mats.dtype} "
+                               f"{tuple(index_mats.shape)} for a batch of {b} (a raw batch without the BEV-space "
+                               "augmentation?)")
         self._next ^= 1
         self._retire(slot)
         augs = []
@@ -129,7 +138,8 @@ class BatchStager:
             for name, t in zip(self.RIG, (rots, trans, intrins, post_rots, post_trans)):
                 getattr(slot, name)[:b].copy_(t, non_blocking=True)
             simbev.augment_images(slot.u8[:b * N], augs, self.final_dim, out=slot.imgs[:b], keep=keep)
-            simbev.class_masks(slot.bev_u8[:b], self.label_groups, out=slot.binimgs[:b])
+            simbev.class_masks(slot.bev_u8[:b], self.label_groups, out=slot.binimgs[:b], index_mats=index_mats,
+                               keep=keep)
             slot.ready = torch.cuda.Event()
             slot.ready.record(st)
         slot.host_post_rots, slot.host_intrins, slot.b, slot.keep = post_rots, intrins, b, keep

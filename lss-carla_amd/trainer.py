@@ -127,6 +127,14 @@ def parse_per_class(text, name="value"):
     return vals[0] if len(vals) == 1 else vals
 
 
+def parse_pair(text, name="value"):
+    """``--bev_rot_lim -22.5,22.5`` -> (-22.5, 22.5): the two ends of a range, as the loader's *_lim keys."""
+    items = [v.strip() for v in str(text).split(",") if v.strip()]
+    if len(items) != 2:
+        raise ValueError(f"{name} {text!r}: two numbers, lo,hi")
+    return float(items[0]), float(items[1])
+
+
 def parse_thresholds(text):
     """``--iou_thresholds 0.35,0.4,0.45,0.5,0.55,0.6,0.65`` (or a sequence of numbers) -> the ladder as an ascending
     list of distinct probabilities, each strictly between 0 and 1, 15 at most (0.5 makes 16); None or empty: None."""
@@ -207,7 +215,9 @@ def build_step(grid_conf, data_aug_conf, bsz, device, *, dtype="bf16", lr=1e-3, 
     when focal_alpha is None); iou_thresholds: a ladder of probabilities the EvalStep also counts the IoU at.
     lr_schedule: an optim.LRSchedule the captured update follows (None: the constant ``lr``). ema_decay > 0: the
     masters get EMA twins (FlatParamGroups.enable_ema) the update averages into, and the EvalStep runs on them
-    (``forward_ema``: the working copies materialised from the EMA by the same launch)."""
+    (``forward_ema``: the working copies materialised from the EMA by the same launch).
+    A data_aug_conf that asks for the BEV-space augmentation (simbev.bev_aug_enabled) makes the stager expect the
+    label index matrices in its raw batches, as ``compile_data``'s loaders of the same conf provide them."""
     import lss_carla_amd as L
     from . import parallel, simbev, tools
     from .flat_params import FlatParamGroups, lss_backward_groups
@@ -225,7 +235,8 @@ def build_step(grid_conf, data_aug_conf, bsz, device, *, dtype="bf16", lr=1e-3, 
     masters = flat.masters
     opt = torch.optim.Adam(masters, lr=lr, weight_decay=weight_decay, fused=True, capturable=True)
     stager = BatchStager(data_aug_conf["final_dim"], bsz, len(simbev.CAMERA_ORDER),
-                         (data_aug_conf["H"], data_aug_conf["W"]), grid_conf, device, label_groups=label_groups)
+                         (data_aug_conf["H"], data_aug_conf["W"]), grid_conf, device, label_groups=label_groups,
+                         bev_aug=simbev.bev_aug_enabled(data_aug_conf))
     model.static_inverses = (stager.hinv.pinv, stager.hinv.kinv)  # staged by the stager's commit
     if loss not in ("bce", "focal"):
         raise ValueError(f"loss {loss!r}: bce or focal")
@@ -303,6 +314,9 @@ def train(
     lr_total_steps=None,
     ema_decay=0.0,
     ema_warmup=True,
+    bev_rot_lim=(0.0, 0.0),
+    bev_scale_lim=(1.0, 1.0),
+    bev_flip=False,
 ):
     """Train LiftSplatShoot on a SimBEV tree; the reference's arguments (train_simbev.py:23-98) plus:
 
@@ -329,8 +343,13 @@ def train(
     events then carry ``lr``. ema_decay > 0: an exponential moving average of the weights, kept by the same
     optimizer pass (ema_warmup: decay min(ema_decay, (1 + t) / (10 + t))); validation then runs on the averaged
     weights (``val`` events carry ``"weights": "ema"``, ``model_best.pt`` is chosen by that IoU) and checkpoints gain
-    ``ema_state_dict``. With either, metrics.jsonl starts with the ``config`` event. Argument errors raise
-    ValueError before anything is looked for or built.
+    ``ema_state_dict``. With either, metrics.jsonl starts with the ``config`` event.
+    bev_rot_lim (degrees), bev_scale_lim, bev_flip: the BEV-space augmentation of the training samples -- one rotation
+    about the ego z axis, one isotropic scale and, with bev_flip, a coin each for x and y, drawn per sample after the
+    image augmentation's values; the rig is composed with it on the host and the labels are warped by the staging
+    stream's label kernel (simbev.class_masks, index_mats=). Validation is never augmented, the captured step and the
+    checkpoints do not change, and the neutral defaults leave the loader exactly as it was. When on, the ``config``
+    event carries the three values. Argument errors raise ValueError before anything is looked for or built.
     Returns a summary dict (counter, epoch, best_val_iou, skipped, frames_per_s of the training steps)."""
     from . import checkpoint, simbev, tools
 
@@ -341,6 +360,9 @@ def train(
         tools.focal_rows(n_out, **focal)  # (argument errors come before anything is looked for or built)
     sched_on = _schedule_setup(lr, lr_schedule, warmup_steps, warmup_factor, lr_min, lr_total_steps, ema_decay)
     ema_on = float(ema_decay) > 0.0
+    bev_aug_conf = {"bev_rot_lim": tuple(float(v) for v in bev_rot_lim),
+                    "bev_scale_lim": tuple(float(v) for v in bev_scale_lim), "bev_flip": bool(bev_flip)}
+    bev_on = simbev.bev_aug_enabled(bev_aug_conf)
     if gpuid < 0 or not torch.cuda.is_available():
         raise RuntimeError("lss_carla_amd.trainer: needs an MI355X (the hot path has no CPU fallback)")
     if ncams != len(simbev.CAMERA_ORDER):
@@ -353,6 +375,8 @@ def train(
     grid_conf = {"xbound": xbound, "ybound": ybound, "zbound": zbound, "dbound": dbound}
     data_aug_conf = {"resize_lim": resize_lim, "final_dim": final_dim, "rot_lim": rot_lim, "H": H, "W": W,
                      "rand_flip": rand_flip, "bot_pct_lim": bot_pct_lim, "Ncams": ncams}
+    if bev_on:
+        data_aug_conf.update(bev_aug_conf)
     config = {"dataroot": str(dataroot), "nepochs": nepochs, "batch_size": bsz, "learning_rate": lr,
               "weight_decay": weight_decay, "num_workers": nworkers, "num_cameras": ncams, "image_H": H, "image_W": W,
               "final_dim": list(final_dim), "max_grad_norm": max_grad_norm, "pos_weight": pos_weight,
@@ -372,9 +396,11 @@ def train(
                        "lr_min": float(lr_min), "lr_total_steps": lr_total_steps})
     if ema_on:
         config.update({"ema_decay": float(ema_decay), "ema_warmup": bool(ema_warmup)})
+    if bev_on:
+        config.update({k: list(v) if isinstance(v, tuple) else v for k, v in bev_aug_conf.items()})
     log = _Log(logdir, use_wandb, {"project": wandb_project, "name": wandb_name, "entity": wandb_entity}, config)
 
-    if "loss" in config and not (sched_on or ema_on):
+    if ("loss" in config or bev_on) and not (sched_on or ema_on):
         log.event("config", 0, **config)
 
     device = torch.device(f"cuda:{gpuid}")
@@ -615,6 +641,12 @@ def main(argv=None):
     p.add_argument("--ema_decay", type=float, default=0.0,
                    help="> 0: keep an EMA of the weights; validation and model_best.pt use it")
     p.add_argument("--ema_warmup", type=int, default=1, help="EMA decay min(ema_decay, (1 + t) / (10 + t))")
+    p.add_argument("--bev_rot_lim", type=str, default="0,0",
+                   help="BEV-space augmentation: rotation about the ego z axis, degrees, lo,hi (e.g. -22.5,22.5)")
+    p.add_argument("--bev_scale_lim", type=str, default="1,1",
+                   help="BEV-space augmentation: isotropic scale of the ego frame, lo,hi (e.g. 0.9,1.1)")
+    p.add_argument("--bev_flip", type=int, default=0, choices=[0, 1],
+                   help="BEV-space augmentation: flip x and y of the ego frame, a coin each")
     a = p.parse_args(argv)
     return train(dataroot=a.dataroot, nepochs=a.nepochs, gpuid=a.gpuid, H=a.H, W=a.W, final_dim=(a.final_h, a.final_w),
                  ncams=a.ncams, bsz=a.bsz, nworkers=a.nworkers, lr=a.lr, weight_decay=a.weight_decay, logdir=a.logdir,
@@ -629,7 +661,9 @@ def main(argv=None):
                  focal_alpha=None if a.focal_alpha is None else parse_per_class(a.focal_alpha, "--focal_alpha"),
                  iou_thresholds=parse_thresholds(a.iou_thresholds), lr_schedule=a.lr_schedule,
                  warmup_steps=a.warmup_steps, warmup_factor=a.warmup_factor, lr_min=a.lr_min,
-                 lr_total_steps=a.lr_total_steps, ema_decay=a.ema_decay, ema_warmup=bool(a.ema_warmup))
+                 lr_total_steps=a.lr_total_steps, ema_decay=a.ema_decay, ema_warmup=bool(a.ema_warmup),
+                 bev_rot_lim=parse_pair(a.bev_rot_lim, "--bev_rot_lim"),
+                 bev_scale_lim=parse_pair(a.bev_scale_lim, "--bev_scale_lim"), bev_flip=bool(a.bev_flip))
 
 
 if __name__ == "__main__":

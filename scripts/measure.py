@@ -24,6 +24,9 @@ Steps:
                                       written to a temporary directory): frames/s of (a) the loop with 14 loader
                                       workers, (b) the loop cycling pre-decoded host batches, (c) bench.py's default,
                                       (d) bench.py --caller reference, in train_loop.json
+  train_loop_bev[:steps[:runs]]       the same tree and the same two loops with the BEV-space augmentation off and on
+                                      (--bev-rot-lim=-22.5,22.5 --bev-scale-lim 0.9,1.1 --bev-flip 1) alternately, RUNS (3)
+                                      fresh processes each: train_loop_bev.json
   infer[:PARENT_DIR]                  the eval-mode forward with and without the lss_bn_eval path: bench.py --config c2
                                       on a checkout of the parent commit (PARENT_DIR, library built there) and on this
                                       tree alternately, three runs each, and --hip-bn 0 here; scripts/infer_ab.py (the
@@ -249,6 +252,42 @@ def step_train_loop(out, spec):
     return 0
 
 
+def step_train_loop_bev(out, spec):
+    import json
+    import tempfile
+    steps, _, runs = spec.partition(":")
+    steps, runs = int(steps or 200), int(runs or 3)
+    script = os.path.join("scripts", "train_loop.py")
+    on = ["--bev-rot-lim=-22.5,22.5", "--bev-scale-lim", "0.9,1.1", "--bev-flip", "1"]
+    loops = (("loop_14_workers", ["--nworkers", "14"]), ("loop_predecoded", ["--nworkers", "0", "--cycle-batches", "4"]))
+    result = {"steps": steps, "bsz": 8, "runs": runs, **{k: {"off": [], "on": []} for k, _ in loops}}
+    with tempfile.TemporaryDirectory(prefix="lss_simbev_") as root:
+        samples = int(steps * 8 / 0.8) + 40
+        rc = run([PY, "-u", script, "--make", root, "--samples", str(samples)], os.path.join(out, "tree.log"), 900)
+        if rc != 0:
+            return rc
+        for key, extra in loops:
+            for i in range(1, runs + 1):
+                for side, aug in (("off", []), ("on", on)):
+                    log = os.path.join(out, f"train_loop_bev_{key}_{side}_{i}.log")
+                    rc = run([PY, "-u", script, "--dataroot", root, "--steps", str(steps)] + extra + aug, log, 600)
+                    last = tail(log, 1).strip()
+                    if rc != 0 or not last.startswith("{"):
+                        print(tail(log, 15), flush=True)
+                        return rc or 1
+                    got = json.loads(last)
+                    if got["skipped"]:
+                        print(f"  {key} {side} {i}: {got['skipped']} skipped steps", flush=True)
+                        return 1
+                    result[key][side].append(got["frames_per_s"])
+                    print(f"  {key} {side} {i}: {got['frames_per_s']:.1f} frames/s", flush=True)
+    with open(os.path.join(out, "train_loop_bev.json"), "w") as fh:
+        json.dump(result, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(result), flush=True)
+    return 0
+
+
 def _bench_value(cmd, log, cwd, limit=600):
     import json
     rc = run(cmd, log, limit, cwd=cwd)
@@ -385,7 +424,7 @@ def main():
     os.makedirs(out, exist_ok=True)
     os.chdir(REPO)
     fns = {"tests": step_tests, "smoke": step_smoke, "bench": step_bench, "trace": step_trace, "pmc": step_pmc,
-           "kbench": step_kbench, "py": step_py, "train_loop": step_train_loop, "infer": step_infer, "bench_ab": step_bench_ab}
+           "kbench": step_kbench, "py": step_py, "train_loop": step_train_loop, "train_loop_bev": step_train_loop_bev, "infer": step_infer, "bench_ab": step_bench_ab}
     for s in a.steps:
         kind, _, spec = s.partition(":")
         print(f"== {s}", flush=True)

@@ -8,6 +8,8 @@ train_loop step): one JSON line {"frames_per_s", "steps", "nworkers", "cycle_bat
   python scripts/train_loop.py --dataroot DIR --label-groups "0;1,2;3"             a multi-class run (on a tree made
                                                                                     with --box-classes 0,1,2,3)
   python scripts/train_loop.py --dataroot DIR --loss focal [--focal-gamma 2.0]     the focal loss (--pos-weight its w_pos)
+  python scripts/train_loop.py --dataroot DIR --bev-rot-lim=-22.5,22.5 --bev-scale-lim 0.9,1.1 --bev-flip 1
+                                                                                    the BEV-space augmentation
 """
 from __future__ import annotations
 
@@ -37,6 +39,9 @@ def main():
     ap.add_argument("--loss", default="bce", choices=["bce", "focal"], help="trainer --loss")
     ap.add_argument("--focal-gamma", default="2.0", help="trainer --focal_gamma")
     ap.add_argument("--box-classes", default="1,2,3", help="--make: the BEV channels the boxes are drawn in")
+    ap.add_argument("--bev-rot-lim", default="0,0", help="trainer --bev_rot_lim")
+    ap.add_argument("--bev-scale-lim", default="1,1", help="trainer --bev_scale_lim")
+    ap.add_argument("--bev-flip", type=int, default=0, help="trainer --bev_flip")
     a = ap.parse_args()
     from lss_carla_amd import miopen_db
     miopen_db.use_committed()  # before torch starts
@@ -54,11 +59,15 @@ def main():
                             miopen_find=bool(a.miopen_find), seed=0, max_steps=a.steps,
                             cycle_batches=a.cycle_batches, label_groups=trainer.parse_label_groups(a.label_groups),
                             pos_weight=trainer.parse_pos_weight(a.pos_weight), loss=a.loss,
-                            focal_gamma=trainer.parse_per_class(a.focal_gamma, "--focal-gamma"))
+                            focal_gamma=trainer.parse_per_class(a.focal_gamma, "--focal-gamma"),
+                            bev_rot_lim=trainer.parse_pair(a.bev_rot_lim, "--bev-rot-lim"),
+                            bev_scale_lim=trainer.parse_pair(a.bev_scale_lim, "--bev-scale-lim"),
+                            bev_flip=bool(a.bev_flip))
     print(json.dumps({"frames_per_s": out["frames_per_s"], "steps": out["counter"], "bsz": a.bsz,
                       "nworkers": a.nworkers, "cycle_batches": a.cycle_batches, "graph": a.graph,
                       "skipped": out["skipped"], "loss": out["loss"], "label_groups": a.label_groups or None,
-                      "loss_kind": a.loss}))
+                      "loss_kind": a.loss, "bev_rot_lim": a.bev_rot_lim, "bev_scale_lim": a.bev_scale_lim,
+                      "bev_flip": a.bev_flip}))
 
 
 if __name__ == "__main__":

@@ -252,6 +252,41 @@ int lss_seg_metrics_accum(const void* x, int32_t dtype, const float* target, int
                           int32_t T, double* totals, void* partial, void* stream);
 int64_t lss_seg_metrics_partial_bytes(int64_t n, int32_t K, int32_t T);
 
+/* (ABI 32) The masked forms: losses and metrics over the cells a uint8 mask marks valid (e.g. lss_simbev_valid_mask's,
+ * include/lss_simbev.h). valid: (batch, plane) bytes in device memory, any value != 0 = valid, one plane shared by the K
+ * classes of a sample: element i of the (batch, K, plane) logits reads valid[(i / (K plane)) plane + i % plane]
+ * (n = batch K plane). The existing entries and their kernels are untouched.
+ *
+ * lss_seg_loss_masked: lss_focal_logits_pc's per-element term (rows (w_pos, w_neg, gamma); (pw, 1, 0) is SimpleLoss)
+ * over the valid elements only. An element whose mask byte is 0 is selected out, not multiplied out: it adds nothing
+ * and its gradient is exactly 0, whatever its logit (NaN, +-Inf). With M the number of valid elements (K per valid
+ * cell), counted as integers in the same pass:
+ *   loss[0] = sum of l / max(M, 1),   scale[0] = n / max(M, 1),   grad = dl/dx / n in the logits' type
+ * -- M is not known while the gradient is written, so grad is what lss_focal_logits_pc stores and the backward applies
+ * the rest; scale is exactly 1 when every element is valid, and an all-ones mask then gives lss_focal_logits_pc's loss
+ * gradient bit for bit (a bf16 gradient takes the same two roundings). M = 0 gives loss 0 and a zero gradient. partial:
+ * 2 * lss_bce_partials(n) 4-byte words (the block sums, then the block counts). Partition, loads, fixed-order folds and
+ * alignment rules are lss_focal_logits_pc's; two launches, capturable; the mask is read on the device, so a replay
+ * follows an in-place change of it. -1 also for n not a multiple of K * plane.
+ * lss_seg_loss_masked_bwd: dx = grad * (grad_loss[0] * scale[0]), both scalars read on the device, rounded once. */
+int lss_seg_loss_masked(const void* x, int32_t dtype, const float* target, const uint8_t* valid, int64_t n,
+                        int64_t plane, int32_t K, const float* params, float* partial, float* loss, float* scale,
+                        void* grad, void* stream);
+int lss_seg_loss_masked_bwd(const void* grad, int32_t dtype, int64_t n, const float* grad_loss, const float* scale,
+                            void* dx, void* stream);
+/* lss_seg_metrics_accum with the mask: only valid elements of the first n_valid[0] samples enter the counts and the
+ * fp64 loss sum. With M the number of those elements and nv the clamped n_valid:
+ *   totals[0] += nv * (sum of l) / max(M, 1)     (the masked batch mean times the batch size, as get_val_info
+ *                                                 weights it);  totals[1..]: as lss_seg_metrics_accum, same layout
+ *   valid_cells[0] += M / K                      (one double in device memory, 8-B aligned; may be NULL)
+ * partial: lss_seg_metrics_masked_partial_bytes(batch * per_sample, K, T) bytes (0 for sizes out of range), 8-B
+ * aligned. Two launches, no host read, capturable. */
+int lss_seg_metrics_accum_masked(const void* x, int32_t dtype, const float* target, const uint8_t* valid,
+                                 int64_t per_sample, int32_t batch, const int32_t* n_valid, int64_t plane, int32_t K,
+                                 const float* params, const float* thetas, int32_t T, double* totals,
+                                 double* valid_cells, void* partial, void* stream);
+int64_t lss_seg_metrics_masked_partial_bytes(int64_t n, int32_t K, int32_t T);
+
 /* out[c] = sum over (n, pixel) of x[n][c][pixel] (fp32, fixed order), x (N, C, HW) NCHW fp32 or bf16: the
  * bias gradient of the fused lift's depthnet conv (src/models.py:47) from d(logits). One launch. */
 int lss_channel_sums(const void* x, int32_t dtype, int32_t N, int32_t C, int32_t HW, float* out, void* stream);

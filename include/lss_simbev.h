@@ -80,6 +80,36 @@ int lss_simbev_class_masks_warp(const uint8_t* bev, int32_t n, int32_t n_classes
                                 const uint32_t* group_bits, int32_t K, const float* index_mats, float* out,
                                 void* stream);
 
+/* (ABI 32) Valid-cell mask for the losses and metrics: out (n, X, Y) uint8, row i = x cell i, column j = y cell j
+ * (one class plane of the logits); out[b, i, j] = 1 iff cell (i, j) of sample b is in the grid and, in FOV mode,
+ * seen by at least one of the sample's N cameras.
+ *   in the grid  index_mats NULL: always. Otherwise (n x 6 fp32, DEVICE memory) lss_simbev_class_masks_warp's own
+ *                su, sv and test 0 <= su < X, 0 <= sv < Y: the mask is 0 exactly where that entry writes its
+ *                out-of-grid 0.
+ *   seen         the cell centre x = x0 + i dx, y = y0 + j dy (x0, y0: the first cell's centre) at a height z of
+ *                `heights` (n_heights <= LSS_SIMBEV_MAX_HEIGHTS floats in HOST memory, passed by value), through
+ *                camera n's block of `cams` (n x N x 16 fp32, DEVICE: M = intrins rots^-1 row-major (9), o = -M trans
+ *                (3), P = post_rots[:2, :2] row-major (4)) and of `post_trans` (n x N x 2 fp32, DEVICE: q):
+ *                  c_r = ((m_r0 x + m_r1 y) + m_r2 z) + o_r,  d = c_2,  u' = c_0 / d,  v' = c_1 / d,
+ *                  u = (p00 u' + p01 v') + q0,  v = (p10 u' + p11 v') + q1
+ *                every product, sum and quotient rounded once to fp32 in that order; seen iff, on the floats (a NaN
+ *                fails), d_lo <= d < d_hi, 0 <= u <= fW - 1, 0 <= v <= fH - 1 for some height and camera -- the
+ *                frustum of create_frustum (dbound, final_dim), get_geometry inverted, so it holds for a rig
+ *                composed with the BEV-space augmentation as it is.
+ * mode: LSS_SIMBEV_VALID_GRID (the first test only; cams, post_trans, heights may be NULL) or LSS_SIMBEV_VALID_FOV.
+ * One launch, one thread per cell, a block inside one sample, the camera blocks in LDS; every byte written exactly
+ * once, no atomics, no workspace. -1 without launching for: NULL out, n outside 1..65535, X or Y outside 1..2^23,
+ * another mode, n_heights > 8, d_lo <= 0 or d_hi <= d_lo; in FOV mode also NULL cams / post_trans / heights,
+ * N outside 1..LSS_SIMBEV_MAX_CAMERAS, n_heights < 1, fH or fW < 1. */
+#define LSS_SIMBEV_MAX_HEIGHTS 8
+#define LSS_SIMBEV_MAX_CAMERAS 256
+#define LSS_SIMBEV_VALID_GRID 0
+#define LSS_SIMBEV_VALID_FOV 1
+int lss_simbev_valid_mask(const float* cams, const float* post_trans, int32_t n, int32_t N, int32_t X, int32_t Y,
+                          float x0, float dx, float y0, float dy, const float* heights, int32_t n_heights, float d_lo,
+                          float d_hi, int32_t fH, int32_t fW, const float* index_mats, int32_t mode, uint8_t* out,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

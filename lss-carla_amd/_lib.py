@@ -18,7 +18,7 @@ DEBUG_LIB_PATH = os.path.join(_HERE, "liblss_hip_debug.so")  # LSS_DEBUG=1: devi
 
 F32, BF16 = 0, 1
 NCHW, NHWC = 0, 1
-ABI_VERSION = 31
+ABI_VERSION = 32
 
 
 class Dims(ctypes.Structure):
@@ -94,6 +94,8 @@ SIGNATURES = {
     "lss_simbev_vehicle_mask": (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _p, _p]),
     "lss_simbev_class_masks": (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _p, _i32, _p, _p]),
     "lss_simbev_class_masks_warp": (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _p, _i32, _p, _p, _p]),
+    "lss_simbev_valid_mask": (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _i32] + [ctypes.c_float] * 4 +
+                              [_p, _i32, ctypes.c_float, ctypes.c_float, _i32, _i32, _p, _i32, _p, _p]),
     # include/lss_convs.h (conv-stack kernels, same library)
     "lss_dwconv_arm": (ctypes.c_int, [_i32] * 13 + [ctypes.POINTER(DwArm)]),
     "lss_dwconv_fwd": (ctypes.c_int, [_p, _i32, _p] + [_i32] * 10 + [_p, _p]),
@@ -115,6 +117,12 @@ SIGNATURES = {
     "lss_seg_metrics_accum": (ctypes.c_int, [_p, _i32, _p, ctypes.c_int64, _i32, _p, ctypes.c_int64, _i32, _p, _p,
                                              _i32, _p, _p, _p]),
     "lss_seg_metrics_partial_bytes": (ctypes.c_int64, [ctypes.c_int64, _i32, _i32]),
+    "lss_seg_loss_masked": (ctypes.c_int, [_p, _i32, _p, _p, ctypes.c_int64, ctypes.c_int64, _i32, _p, _p, _p, _p, _p,
+                                           _p]),
+    "lss_seg_loss_masked_bwd": (ctypes.c_int, [_p, _i32, ctypes.c_int64, _p, _p, _p, _p]),
+    "lss_seg_metrics_accum_masked": (ctypes.c_int, [_p, _i32, _p, _p, ctypes.c_int64, _i32, _p, ctypes.c_int64, _i32,
+                                                    _p, _p, _i32, _p, _p, _p, _p]),
+    "lss_seg_metrics_masked_partial_bytes": (ctypes.c_int64, [ctypes.c_int64, _i32, _i32]),
     "lss_bn_bwd_rank1": (ctypes.c_int, [_p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _i32, _i32, _p, _p, _p, _p, _p,
                                         _p]),
     "lss_scale_add": (ctypes.c_int, [_p, _p, ctypes.c_float, _p, ctypes.c_int64, ctypes.c_int64, _p, _p]),

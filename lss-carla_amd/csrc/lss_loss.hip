@@ -557,6 +557,289 @@ __global__ __launch_bounds__(kBlock) void k_seg_metrics_fold(const double* __res
     }
 }
 
+// ---- The masked forms (ABI 32): a uint8 mask `valid` (batch, plane), one plane shared by the K classes of a
+// sample, says which cells count: element i of the (batch, K, plane) logits reads valid[(i / (K plane)) plane +
+// i % plane]. ClassWalk with that index walked beside it: inside a plane both advance by one, at the end of a class
+// plane the mask index goes back to the plane's start, at the end of a sample it runs on into the next plane.
+struct MaskWalk {
+    long long rem, plane, vi;  // position inside the plane; index into valid
+    int k, K;
+    __device__ MaskWalk(long long i0, long long plane_, int K_) : plane(plane_), K(K_) {
+        const long long p = i0 / plane_;
+        rem = i0 - p * plane_;
+        k = (int)(p % K_);
+        vi = (p / K_) * plane_ + rem;
+    }
+    __device__ __forceinline__ void next() {
+        ++vi;
+        if (++rem == plane) {
+            rem = 0;
+            k = k + 1 == K ? 0 : k + 1;
+            if (k != 0) vi -= plane;
+        }
+    }
+};
+
+// A thread's 8 mask bytes into bit j of the result: one 8-byte load when the 8 elements lie in one plane at an
+// 8-byte aligned address (plane % 8 == 0: always), else a byte each, walked as the classes are.
+__device__ __forceinline__ unsigned mask_bits(const uint8_t* __restrict__ valid, long long i0, long long n,
+                                               long long plane, int K) {
+    MaskWalk mw(i0, plane, K);
+    unsigned bits = 0;
+    if (i0 + kBceVpt <= n && mw.rem + kBceVpt <= plane && ((reinterpret_cast<uintptr_t>(valid) + mw.vi) & 7) == 0) {
+        const uint2 w = *reinterpret_cast<const uint2*>(valid + mw.vi);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            bits |= ((w.x >> (8 * j)) & 0xFFu) ? 1u << j : 0u;
+            bits |= ((w.y >> (8 * j)) & 0xFFu) ? 1u << (4 + j) : 0u;
+        }
+        return bits;
+    }
+#pragma unroll
+    for (int j = 0; j < kBceVpt; ++j) {
+        if (i0 + j < n && valid[mw.vi]) bits |= 1u << j;
+        mw.next();
+    }
+    return bits;
+}
+
+// k_focal_fwd_pc with the mask: an element whose mask byte is 0 is selected out -- it adds nothing to the sum
+// and its gradient is written as 0 whatever its logit is (a NaN or an infinity too). The number of valid elements M
+// is counted in the same pass, so the gradient cannot be divided by it here: it is stored as k_focal_fwd_pc stores it,
+// times 1 / n, and the fold writes n / max(M, 1) for the backward -- exactly 1 when every element is valid, so an
+// all-ones mask gives k_focal_fwd_pc's gradient bit for bit (a bf16 gradient takes the same two roundings).
+// Block record: partial[block] the sum, counts[block] the block's valid elements.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_seg_loss_masked(const T* __restrict__ x, const float* __restrict__ t,
+                                                            const uint8_t* __restrict__ valid, long long n,
+                                                            long long plane, int K, const float* __restrict__ params,
+                                                            float inv_n, float* __restrict__ partial,
+                                                            int* __restrict__ counts, T* __restrict__ grad) {
+    __shared__ float s_w[kBlock / kWave];
+    __shared__ int s_m[kBlock / kWave];
+    const long long i0 = ((long long)blockIdx.x * kBlock + threadIdx.x) * kBceVpt;
+    float xv[kBceVpt], tv[kBceVpt], gv[kBceVpt];
+    const bool full = i0 + kBceVpt <= n;
+    unsigned bits = 0;
+    if (full) {
+        ldv<8>(x + i0, xv);
+        const float4 a = *reinterpret_cast<const float4*>(t + i0), b = *reinterpret_cast<const float4*>(t + i0 + 4);
+        tv[0] = a.x; tv[1] = a.y; tv[2] = a.z; tv[3] = a.w; tv[4] = b.x; tv[5] = b.y; tv[6] = b.z; tv[7] = b.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < kBceVpt; ++j) {
+            xv[j] = i0 + j < n ? ld(x + i0 + j) : 0.f;
+            tv[j] = i0 + j < n ? t[i0 + j] : 0.f;
+        }
+    }
+    if (i0 < n) bits = mask_bits(valid, i0, n, plane, K);
+    ClassWalk cw(i0, plane, K);
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < kBceVpt; ++j) {
+        const float* pr = params + 3 * cw.k;
+        const float wp = pr[0], wn = pr[1], gamma = pr[2];
+        cw.next();
+        const FocalTerm f = focal_term(xv[j], tv[j], wp, wn, gamma);
+        const bool on = (bits >> j) & 1u;  // (never set past n)
+        gv[j] = on ? f.g * inv_n : 0.f;
+        s += on ? f.l : 0.f;
+    }
+    if (full) stv<8>(grad + i0, gv);
+    else {
+#pragma unroll
+        for (int j = 0; j < kBceVpt; ++j)
+            if (i0 + j < n) st(grad + i0 + j, gv[j]);
+    }
+    int m = __popc(bits);
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+        s += __shfl_xor(s, o, kWave);
+        m += __shfl_xor(m, o, kWave);
+    }
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+        s_w[threadIdx.x / kWave] = s;
+        s_m[threadIdx.x / kWave] = m;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float b = 0.f;
+        int c = 0;
+#pragma unroll
+        for (int w = 0; w < kBlock / kWave; ++w) {
+            b += s_w[w];
+            c += s_m[w];
+        }
+        partial[blockIdx.x] = b;
+        counts[blockIdx.x] = c;
+    }
+}
+
+// k_bce_total's fold of the sums, the counts beside it (integers): loss = sum / max(M, 1), scale = n / max(M, 1)
+__global__ __launch_bounds__(kWave) void k_seg_loss_masked_total(const float* __restrict__ partial,
+                                                                 const int* __restrict__ counts, int nb, float nf,
+                                                                 float* __restrict__ loss, float* __restrict__ scale) {
+    float s = 0.f;
+    long long m = 0;
+    for (int b = threadIdx.x; b < nb; b += kWave) {
+        s += partial[b];
+        m += counts[b];
+    }
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+        s += __shfl_xor(s, o, kWave);
+        m += __shfl_xor(m, o, kWave);
+    }
+    if (threadIdx.x == 0) {
+        const float d = (float)(m > 0 ? m : 1);
+        loss[0] = s / d;
+        scale[0] = nf / d;
+    }
+}
+
+// dx = grad * (gout[0] * scale[0]): k_bce_bwd with the normalisation the forward could not apply
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_seg_loss_masked_bwd(const T* __restrict__ grad, long long n,
+                                                                const float* __restrict__ gout,
+                                                                const float* __restrict__ scale, T* __restrict__ dx) {
+    const long long i0 = ((long long)blockIdx.x * kBlock + threadIdx.x) * kBceVpt;
+    const float gs = gout[0] * scale[0];
+    float v[kBceVpt];
+    if (i0 + kBceVpt <= n) {
+        ldv<8>(grad + i0, v);
+#pragma unroll
+        for (int j = 0; j < kBceVpt; ++j) v[j] *= gs;
+        stv<8>(dx + i0, v);
+    } else {
+        for (long long i = i0; i < n; ++i) st(dx + i, ld(grad + i) * gs);
+    }
+}
+
+// k_seg_metrics with the mask: only valid elements of the first n_valid samples enter the histograms and the loss
+// sum; the block's count of them is one more int behind its histograms (block record: nh + 1 int32).
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_seg_metrics_masked(const T* __restrict__ x, const float* __restrict__ t,
+                                                               const uint8_t* __restrict__ valid, long long per_sample,
+                                                               int batch, const int* __restrict__ n_valid,
+                                                               long long plane, int K, const float* __restrict__ params,
+                                                               const float* __restrict__ thetas, int nt, int vec,
+                                                               double* __restrict__ ploss, int* __restrict__ pcount) {
+    __shared__ double s_l[kBlock / kWave];
+    __shared__ int s_h[kIouMaxClasses * (kSegMaxThresholds + 1) * 2 + 1];
+    __shared__ float s_th[kSegMaxThresholds];
+    const int nh = K * (nt + 1) * 2;
+    for (int c = threadIdx.x; c <= nh; c += kBlock) s_h[c] = 0;
+    if (threadIdx.x < nt) s_th[threadIdx.x] = thetas[threadIdx.x];
+    __syncthreads();
+    int nv = n_valid ? n_valid[0] : batch;
+    nv = nv < 0 ? 0 : (nv > batch ? batch : nv);
+    const long long limit = (long long)nv * per_sample;
+    const long long i0 = ((long long)blockIdx.x * kBlock + threadIdx.x) * kBceVpt;
+    double s = 0.0;
+    if (i0 < limit) {
+        float xv[kBceVpt], tv[kBceVpt];
+        if (vec && i0 + kBceVpt <= limit) {
+            ldv<8>(x + i0, xv);
+            const float4 a = *reinterpret_cast<const float4*>(t + i0), b = *reinterpret_cast<const float4*>(t + i0 + 4);
+            tv[0] = a.x; tv[1] = a.y; tv[2] = a.z; tv[3] = a.w; tv[4] = b.x; tv[5] = b.y; tv[6] = b.z; tv[7] = b.w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < kBceVpt; ++j) {
+                xv[j] = i0 + j < limit ? ld(x + i0 + j) : 0.f;
+                tv[j] = i0 + j < limit ? t[i0 + j] : 0.f;
+            }
+        }
+        const unsigned bits = mask_bits(valid, i0, limit, plane, K);
+        ClassWalk cw(i0, plane, K);
+#pragma unroll
+        for (int j = 0; j < kBceVpt; ++j) {
+            const float xx = xv[j], tt = tv[j];
+            const int k = cw.k;
+            const float* pr = params + 3 * k;
+            const float wp = pr[0], wn = pr[1], gamma = pr[2];
+            cw.next();
+            const FocalTerm f = focal_term(xx, tt, wp, wn, gamma);
+            if ((bits >> j) & 1u) {  // (never set past limit)
+                s += (double)f.l;
+                int bin = 0;
+                for (int m = 0; m < nt; ++m) bin += xx > s_th[m] ? 1 : 0;
+                atomicAdd(&s_h[(k * (nt + 1) + bin) * 2 + (tt != 0.f ? 1 : 0)], 1);
+            }
+        }
+        if (bits) atomicAdd(&s_h[nh], __popc(bits));
+    }
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, kWave);
+    if ((threadIdx.x & (kWave - 1)) == 0) s_l[threadIdx.x / kWave] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double l = 0.0;
+#pragma unroll
+        for (int w = 0; w < kBlock / kWave; ++w) l += s_l[w];
+        ploss[blockIdx.x] = l;
+    }
+    for (int c = threadIdx.x; c <= nh; c += kBlock) pcount[(size_t)blockIdx.x * (nh + 1) + c] = s_h[c];
+}
+
+// k_seg_metrics_fold over the masked records: with M the valid elements of the batch (K per valid cell) and nv the
+// clamped n_valid, totals[0] += nv * (sum of the loss terms) / max(M, 1) -- the masked batch mean times the batch
+// size -- and valid_cells[0] += M / K (when not NULL); the counts as before.
+__global__ __launch_bounds__(kBlock) void k_seg_metrics_fold_masked(const double* __restrict__ ploss,
+                                                                    const int* __restrict__ pcount, int nb, int K, int nt,
+                                                                    int batch, const int* __restrict__ n_valid,
+                                                                    double* __restrict__ totals,
+                                                                    double* __restrict__ valid_cells) {
+    __shared__ double s_l[kBlock / kWave];
+    __shared__ long long s_m[kBlock / kWave];
+    __shared__ long long s_h[kIouMaxClasses * (kSegMaxThresholds + 1) * 2];
+    const int nh = K * (nt + 1) * 2;
+    double s = 0.0;
+    long long m = 0;
+    for (int b = threadIdx.x; b < nb; b += kBlock) {
+        s += ploss[b];
+        m += pcount[(size_t)b * (nh + 1) + nh];
+    }
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+        s += __shfl_xor(s, o, kWave);
+        m += __shfl_xor(m, o, kWave);
+    }
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+        s_l[threadIdx.x / kWave] = s;
+        s_m[threadIdx.x / kWave] = m;
+    }
+    for (int c = threadIdx.x; c < nh; c += kBlock) {
+        long long a = 0;
+        for (int b = 0; b < nb; ++b) a += pcount[(size_t)b * (nh + 1) + c];
+        s_h[c] = a;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double l = 0.0;
+        long long M = 0;
+#pragma unroll
+        for (int w = 0; w < kBlock / kWave; ++w) {
+            l += s_l[w];
+            M += s_m[w];
+        }
+        int nv = n_valid ? n_valid[0] : batch;
+        nv = nv < 0 ? 0 : (nv > batch ? batch : nv);
+        totals[0] += (double)nv * l / (double)(M > 0 ? M : 1);
+        if (valid_cells) valid_cells[0] += (double)(M / K);
+    }
+    for (int c = threadIdx.x; c < K + 2 * K * nt; c += kBlock) {
+        long long a = 0;
+        if (c < K) {
+            for (int b = 0; b <= nt; ++b) a += s_h[(c * (nt + 1) + b) * 2 + 1];
+        } else {
+            const int r = c - K, pp = r >= K * nt, kj = pp ? r - K * nt : r, k = kj / nt, j = kj - k * nt;
+            for (int b = j + 1; b <= nt; ++b)
+                a += s_h[(k * (nt + 1) + b) * 2 + 1] + (pp ? s_h[(k * (nt + 1) + b) * 2] : 0);
+        }
+        totals[1 + c] += (double)a;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -737,6 +1020,89 @@ int lss_seg_metrics_accum(const void* x, int32_t dtype, const float* target, int
                            thetas, (int)T, vec, pl, pc);
     hipLaunchKernelGGL(k_seg_metrics_fold, dim3(1), dim3(kBlock), 0, s, (const double*)pl, (const int*)pc, (int)nb,
                        (int)K, (int)T, (double)per_sample, totals);
+    return launch_status();
+}
+
+int lss_seg_loss_masked(const void* x, int32_t dtype, const float* target, const uint8_t* valid, int64_t n,
+                        int64_t plane, int32_t K, const float* params, float* partial, float* loss, float* scale,
+                        void* grad, void* stream) {
+    const int esz = dtype == LSS_CONV_BF16 ? 2 : dtype == LSS_CONV_F32 ? 4 : 0;
+    if (!x || !target || !valid || !params || !partial || !loss || !scale || !grad || !esz || n <= 0 || plane <= 0 ||
+        K <= 0 || plane > LLONG_MAX / K || n % (plane * K) != 0 ||
+        ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(grad)) & 15) ||
+        (reinterpret_cast<uintptr_t>(target) & 15) ||
+        ((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(partial) |
+          reinterpret_cast<uintptr_t>(scale)) & 3))
+        return LSS_CONV_EINVAL;
+    const long long nb = (n + (long long)kBlock * kBceVpt - 1) / ((long long)kBlock * kBceVpt);
+    if (nb > INT_MAX) return LSS_CONV_EINVAL;
+    const float inv_n = 1.0f / (float)n;
+    hipStream_t s = (hipStream_t)stream;
+    int* counts = reinterpret_cast<int*>(partial + nb);
+    if (esz == 2)
+        hipLaunchKernelGGL(k_seg_loss_masked<bf16>, dim3((unsigned)nb), dim3(kBlock), 0, s, (const bf16*)x, target,
+                           valid, (long long)n, (long long)plane, (int)K, params, inv_n, partial, counts, (bf16*)grad);
+    else
+        hipLaunchKernelGGL(k_seg_loss_masked<float>, dim3((unsigned)nb), dim3(kBlock), 0, s, (const float*)x, target,
+                           valid, (long long)n, (long long)plane, (int)K, params, inv_n, partial, counts, (float*)grad);
+    hipLaunchKernelGGL(k_seg_loss_masked_total, dim3(1), dim3(kWave), 0, s, partial, (const int*)counts, (int)nb, (float)n,
+                       loss, scale);
+    return launch_status();
+}
+
+int lss_seg_loss_masked_bwd(const void* grad, int32_t dtype, int64_t n, const float* grad_loss, const float* scale,
+                            void* dx, void* stream) {
+    const int esz = dtype == LSS_CONV_BF16 ? 2 : dtype == LSS_CONV_F32 ? 4 : 0;
+    if (!grad || !grad_loss || !scale || !dx || !esz || n <= 0 ||
+        ((reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(dx)) & 15) ||
+        ((reinterpret_cast<uintptr_t>(grad_loss) | reinterpret_cast<uintptr_t>(scale)) & 3))
+        return LSS_CONV_EINVAL;
+    const long long nb = (n + (long long)kBlock * kBceVpt - 1) / ((long long)kBlock * kBceVpt);
+    if (nb > INT_MAX) return LSS_CONV_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    if (esz == 2)
+        hipLaunchKernelGGL(k_seg_loss_masked_bwd<bf16>, dim3((unsigned)nb), dim3(kBlock), 0, s, (const bf16*)grad,
+                           (long long)n, grad_loss, scale, (bf16*)dx);
+    else
+        hipLaunchKernelGGL(k_seg_loss_masked_bwd<float>, dim3((unsigned)nb), dim3(kBlock), 0, s, (const float*)grad,
+                           (long long)n, grad_loss, scale, (float*)dx);
+    return launch_status();
+}
+
+int64_t lss_seg_metrics_masked_partial_bytes(int64_t n, int32_t K, int32_t T) {
+    return n <= 0 || K <= 0 || K > kIouMaxClasses || T <= 0 || T > kSegMaxThresholds
+               ? 0
+               : lss_bce_partials(n) * (int64_t)(sizeof(double) + 2 * ((size_t)K * (size_t)(T + 1) + 1) * sizeof(int));
+}
+
+int lss_seg_metrics_accum_masked(const void* x, int32_t dtype, const float* target, const uint8_t* valid,
+                                 int64_t per_sample, int32_t batch, const int32_t* n_valid, int64_t plane, int32_t K,
+                                 const float* params, const float* thetas, int32_t T, double* totals,
+                                 double* valid_cells, void* partial, void* stream) {
+    const int esz = dtype == LSS_CONV_BF16 ? 2 : dtype == LSS_CONV_F32 ? 4 : 0;
+    if (!x || !target || !valid || !params || !thetas || !totals || !partial || !esz || per_sample <= 0 || batch <= 0 ||
+        plane <= 0 || K <= 0 || K > kIouMaxClasses || T <= 0 || T > kSegMaxThresholds || per_sample != plane * K ||
+        per_sample > LLONG_MAX / batch || (reinterpret_cast<uintptr_t>(partial) & 7) ||
+        ((reinterpret_cast<uintptr_t>(totals) | reinterpret_cast<uintptr_t>(valid_cells)) & 7) ||
+        ((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(thetas)) & 3))
+        return LSS_CONV_EINVAL;
+    const long long n = (long long)per_sample * batch;
+    const long long nb = (n + (long long)kBlock * kBceVpt - 1) / ((long long)kBlock * kBceVpt);
+    if (nb > INT_MAX) return LSS_CONV_EINVAL;
+    const int vec = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(target)) & 15) == 0;
+    hipStream_t s = (hipStream_t)stream;
+    double* pl = (double*)partial;
+    int* pc = (int*)(pl + nb);
+    if (esz == 2)
+        hipLaunchKernelGGL(k_seg_metrics_masked<bf16>, dim3((unsigned)nb), dim3(kBlock), 0, s, (const bf16*)x, target,
+                           valid, (long long)per_sample, (int)batch, (const int*)n_valid, (long long)plane, (int)K,
+                           params, thetas, (int)T, vec, pl, pc);
+    else
+        hipLaunchKernelGGL(k_seg_metrics_masked<float>, dim3((unsigned)nb), dim3(kBlock), 0, s, (const float*)x, target,
+                           valid, (long long)per_sample, (int)batch, (const int*)n_valid, (long long)plane, (int)K,
+                           params, thetas, (int)T, vec, pl, pc);
+    hipLaunchKernelGGL(k_seg_metrics_fold_masked, dim3(1), dim3(kBlock), 0, s, (const double*)pl, (const int*)pc, (int)nb,
+                       (int)K, (int)T, (int)batch, (const int*)n_valid, totals, valid_cells);
     return launch_status();
 }
 

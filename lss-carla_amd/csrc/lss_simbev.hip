@@ -198,6 +198,73 @@ __global__ __launch_bounds__(kThreads) void k_class_masks_warp(const uint8_t* __
         if (k < K) o[(size_t)k * XY] = (set & groups.bits[k]) ? 1.0f : 0.0f;
 }
 
+// ---- Valid-cell mask: valid[b, i, j] = in the grid && seen by a camera, the layout of one class plane of the logits.
+// In the grid: k_class_masks_warp's own su / sv and range test on sample b's index matrix (NULL: every cell is).
+// Seen: the cell centre (x, y) = (x0 + i dx, y0 + j dy) at one of the heights z, taken back through the rig --
+// get_geometry inverted: c = M p + o with M = intrins rots^-1, o = -M trans (the host's fov_cameras), depth d = c_2,
+// (u', v') = (c_0, c_1) / d, (u, v) = P (u', v') + q with P, q the image augmentation's post_rots / post_trans --
+// lands inside some camera's frustum: d_lo <= d < d_hi, 0 <= u <= u_max, 0 <= v <= v_max. Every product, sum and
+// quotient is one correctly rounded fp32 operation in the order written (the numpy restatement of the tests does
+// the same roundings); the tests are on the floats, so a NaN is unseen.
+// Block = 256 cells of one sample (blockIdx.y), consecutive threads along j; the sample's N camera blocks
+// (16 + 2 floats each) are copied to LDS once per block and every lane reads the same word (a broadcast). One byte
+// store per cell, each byte written once.
+struct FovHeights {
+    float z[LSS_SIMBEV_MAX_HEIGHTS];
+};
+constexpr int kCamFloats = 18;  // M (9), o (3), P (4), q (2)
+__global__ __launch_bounds__(kThreads) void k_valid_mask(const float* __restrict__ cams,
+                                                         const float* __restrict__ post_trans, int N, int X, int Y,
+                                                         float x0, float dx, float y0, float dy, FovHeights hs, int nh,
+                                                         float d_lo, float d_hi, float u_max, float v_max,
+                                                         const float* __restrict__ mats, int fov,
+                                                         uint8_t* __restrict__ out) {
+    extern __shared__ float s_cam[];
+    const int b = blockIdx.y;
+    if (fov) {
+        const float* c = cams + (size_t)b * N * 16;
+        const float* q = post_trans + (size_t)b * N * 2;
+        for (int t = threadIdx.x; t < N * 16; t += kThreads) s_cam[(t >> 4) * kCamFloats + (t & 15)] = c[t];
+        for (int t = threadIdx.x; t < N * 2; t += kThreads) s_cam[(t >> 1) * kCamFloats + 16 + (t & 1)] = q[t];
+        __syncthreads();
+    }
+    const long XY = (long)X * Y;
+    const long r = (long)blockIdx.x * kThreads + threadIdx.x;
+    if (r >= XY) return;
+    const int row = (int)(r / Y), col = (int)(r - (long)row * Y);
+    bool ok = true;
+    if (mats) {
+        const float* m = mats + 6 * b;
+        const float ci = __fadd_rn((float)row, 0.5f), cj = __fadd_rn((float)col, 0.5f);
+        const float su = __fadd_rn(__fadd_rn(__fmul_rn(m[0], ci), __fmul_rn(m[1], cj)), m[2]);
+        const float sv = __fadd_rn(__fadd_rn(__fmul_rn(m[3], ci), __fmul_rn(m[4], cj)), m[5]);
+        ok = su >= 0.0f && su < (float)X && sv >= 0.0f && sv < (float)Y;
+    }
+    if (fov && ok) {
+        const float x = __fadd_rn(x0, __fmul_rn((float)row, dx)), y = __fadd_rn(y0, __fmul_rn((float)col, dy));
+        bool seen = false;
+        for (int h = 0; h < nh && !seen; ++h) {
+            const float z = hs.z[h];
+            for (int n = 0; n < N && !seen; ++n) {
+                const float* p = s_cam + n * kCamFloats;
+                float c[3];
+#pragma unroll
+                for (int k = 0; k < 3; ++k)
+                    c[k] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(p[3 * k], x), __fmul_rn(p[3 * k + 1], y)),
+                                               __fmul_rn(p[3 * k + 2], z)),
+                                     p[9 + k]);
+                const float d = c[2];
+                const float up = __fdiv_rn(c[0], d), vp = __fdiv_rn(c[1], d);
+                const float u = __fadd_rn(__fadd_rn(__fmul_rn(p[12], up), __fmul_rn(p[13], vp)), p[16]);
+                const float v = __fadd_rn(__fadd_rn(__fmul_rn(p[14], up), __fmul_rn(p[15], vp)), p[17]);
+                seen = d >= d_lo && d < d_hi && u >= 0.0f && u <= u_max && v >= 0.0f && v <= v_max;
+            }
+        }
+        ok = seen;
+    }
+    out[(size_t)b * XY + r] = ok ? 1 : 0;
+}
+
 // ---- host: Pillow's bicubic coefficient tables (Resample.c precompute_coeffs / normalize_coeffs_8bpc)
 double bicubic_filter(double x) {
     const double a = -0.5;
@@ -315,6 +382,31 @@ int lss_simbev_class_masks_warp(const uint8_t* bev, int32_t n, int32_t n_classes
     const long total = (long)n * X * Y;
     hipLaunchKernelGGL(k_class_masks_warp, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0,
                        (hipStream_t)stream, bev, n_classes, X, Y, total, g, used, K, index_mats, out);
+    return launch_status();
+}
+
+int lss_simbev_valid_mask(const float* cams, const float* post_trans, int32_t n, int32_t N, int32_t X, int32_t Y,
+                          float x0, float dx, float y0, float dy, const float* heights, int32_t n_heights, float d_lo,
+                          float d_hi, int32_t fH, int32_t fW, const float* index_mats, int32_t mode, uint8_t* out,
+                          void* stream) {
+    if (!out || n <= 0 || n > 65535 || X <= 0 || Y <= 0 || X > (1 << 23) || Y > (1 << 23)) return -1;
+    if (mode != LSS_SIMBEV_VALID_GRID && mode != LSS_SIMBEV_VALID_FOV) return -1;
+    if (n_heights > LSS_SIMBEV_MAX_HEIGHTS || !(d_lo > 0.0f) || !(d_hi > d_lo)) return -1;  // (a NaN bound too)
+    const int fov = mode == LSS_SIMBEV_VALID_FOV;
+    FovHeights hs{};
+    if (fov) {
+        if (!cams || !post_trans || !heights || N < 1 || N > LSS_SIMBEV_MAX_CAMERAS || n_heights < 1 || fH < 1 ||
+            fW < 1)
+            return -1;
+        for (int h = 0; h < n_heights; ++h) hs.z[h] = heights[h];
+    }
+    const long XY = (long)X * Y;
+    const long bps = (XY + kThreads - 1) / kThreads;
+    if (bps > 0x7FFFFFFFL) return -1;
+    const size_t lds = fov ? (size_t)N * kCamFloats * sizeof(float) : 0;
+    hipLaunchKernelGGL(k_valid_mask, dim3((unsigned)bps, (unsigned)n), dim3(kThreads), lds, (hipStream_t)stream, cams,
+                       post_trans, fov ? N : 0, X, Y, x0, dx, y0, dy, hs, fov ? n_heights : 0, d_lo, d_hi,
+                       (float)(fW - 1), (float)(fH - 1), index_mats, fov, out);
     return launch_status();
 }
 

@@ -27,14 +27,17 @@ state_dict): build it on a model no training step is bound to. The hot path has 
     python -m lss_carla_amd.predict --modelf CKPT --dataroot ROOT --out DIR [--bsz N] [--label_groups "0;1,2,3"]
                                     [--dtype bf16|fp32] [--graph 0|1] [--threshold 0.5 | 0.45,0.5,0.35]
                                     [--loss bce|focal] [--focal_gamma G] [--focal_alpha A] [--iou_thresholds 0.35,...]
-                                    [--weights auto|ema|model]
+                                    [--weights auto|ema|model] [--valid_mask none|grid|fov] [--fov_z 0.0[,1.5,...]]
 
 runs the val split through ``BatchStager`` and the Predictor and writes one uint8 mask array per sample
 (``DIR/<index>.npy``, (K, X, Y)) and ``DIR/metrics.json``: loss, IoU and per-class IoU from get_val_info's
 accumulators (``tools.val_accumulate``), and frames/s. ``--threshold`` takes one probability or one per class.
 With ``--loss focal`` or ``--iou_thresholds`` the totals come from ``tools.seg_metrics_accumulate`` instead: the loss
 is the chosen one (``loss_kind``), the IoU keys are the 0.5 column's, and a ladder adds ``iou_at``,
-``iou_max_per_class``, ``best_threshold_per_class`` and ``iou_max``. The matplotlib figures of explore.py are not drawn.
+``iou_max_per_class``, ``best_threshold_per_class`` and ``iou_max``. With ``--valid_mask grid|fov`` the totals come from
+the masked form of that accumulate (``lss_seg_metrics_accum_masked``): loss and IoU are over valid cells (simbev.valid_mask),
+``metrics.json`` gains ``valid_mask`` and ``valid_fraction``, and each sample's mask is written to ``DIR/valid/<index>.npy``
+((X, Y) uint8); the written prediction masks are unchanged. The matplotlib figures of explore.py are not drawn.
 """
 from __future__ import annotations
 
@@ -302,6 +305,10 @@ def parser() -> argparse.ArgumentParser:
                    help="the masks' probability threshold, or one per class: 0.5,0.4,0.35")
     p.add_argument("--weights", default="auto", choices=list(WEIGHTS),
                    help="which weights of a trainer checkpoint: its EMA (auto: when it has one) or the model's")
+    p.add_argument("--valid_mask", default="none", choices=["none", "grid", "fov"],
+                   help="count only valid cells in loss and IoU (fov: cells some camera sees); also writes DIR/valid/")
+    p.add_argument("--fov_z", type=str, default="0.0",
+                   help="--valid_mask fov: the heights (metres) a cell is tested at, 1 to 8: 0.0[,1.5,...]")
     p.add_argument("--gpuid", type=int, default=0)
     p.add_argument("--nworkers", type=int, default=4)
     p.add_argument("--H", type=int, default=224)
@@ -334,7 +341,8 @@ def predict(a, grid_conf=None, data_aug_conf=None, model: Optional[torch.nn.Modu
     import lss_carla_amd as L
     from . import simbev, tools
     from .staging import BatchStager
-    from .trainer import _class_setup, _loss_setup, parse_label_groups, parse_per_class, parse_thresholds
+    from .trainer import (_class_setup, _loss_setup, parse_heights, parse_label_groups, parse_per_class,
+                          parse_thresholds)
 
     torch.cuda.set_device(dev)
     torch.backends.cudnn.benchmark = bool(a.miopen_find)
@@ -353,6 +361,9 @@ def predict(a, grid_conf=None, data_aug_conf=None, model: Optional[torch.nn.Modu
         focal = tools.focal_rows(K, **focal)  # (argument errors before anything is built)
     if not tools.is_scalar_weight(threshold) and len(threshold) != K:
         raise ValueError(f"--threshold names {len(threshold)} classes, label_groups {K}")
+    mask_mode = simbev.valid_mask_mode({"valid_mask": getattr(a, "valid_mask", None),
+                                        "fov_z": parse_heights(getattr(a, "fov_z", "0.0"))})
+    fov_z = parse_heights(getattr(a, "fov_z", "0.0"))
     amp_dtype = torch.bfloat16 if a.dtype == "bf16" else None
     if model is None:
         sd = model_state_dict(torch.load(a.modelf, map_location="cpu"), getattr(a, "weights", "auto"))
@@ -365,12 +376,14 @@ def predict(a, grid_conf=None, data_aug_conf=None, model: Optional[torch.nn.Modu
                                        "segmentationdata", device=dev, label_groups=groups)
     val_raw, n_val = valloader.loader, len(valloader.dataset)
     stager = BatchStager(data_aug_conf["final_dim"], a.bsz, len(simbev.CAMERA_ORDER),
-                         (data_aug_conf["H"], data_aug_conf["W"]), grid_conf, dev, label_groups=groups)
+                         (data_aug_conf["H"], data_aug_conf["W"]), grid_conf, dev, label_groups=groups,
+                         **({} if mask_mode is None else {"valid_mask": mask_mode, "fov_z": fov_z}))
     p = Predictor(model, a.bsz, dev, amp_dtype=amp_dtype, threshold=threshold, graph=bool(a.graph), stager=stager)
     if K > 1 or not tools.is_scalar_weight(pos_weight):
         pos_weight = tools.class_weights(pos_weight, K, dev)
     totals = torch.zeros(1 + 2 * K, device=dev, dtype=torch.float64)
-    ladder_mode = focal is not None or ladder is not None
+    ladder_mode = focal is not None or ladder is not None or mask_mode is not None  # (masked: always this path)
+    valid_cells = torch.zeros(1, device=dev, dtype=torch.float64) if mask_mode is not None else None
     if ladder_mode:  # lss_seg_metrics_accum at the ladder and 0.5: either loss term, every threshold, one pass
         columns = sorted(set((ladder or []) + [0.5]))
         if len(columns) > 16:
@@ -383,7 +396,7 @@ def predict(a, grid_conf=None, data_aug_conf=None, model: Optional[torch.nn.Modu
             params = torch.stack([w, torch.ones_like(w), torch.zeros_like(w)], dim=1).contiguous()
         totals = torch.zeros(1 + K + 2 * K * len(columns), device=dev, dtype=torch.float64)
     os.makedirs(a.out, exist_ok=True)
-    masks, frames = [], 0
+    masks, valids, frames = [], [], 0
     it = iter(val_raw)
     nxt = next(it, None)
     if nxt is not None:
@@ -394,10 +407,13 @@ def predict(a, grid_conf=None, data_aug_conf=None, model: Optional[torch.nn.Modu
         b = stager.commit()
         logits = p.run(b)  # (the first call captures the graph: timed from the second batch on)
         if ladder_mode:
-            tools.seg_metrics_accumulate(p._out, stager.binimgs, totals, stager.n_valid, params, thetas)
+            tools.seg_metrics_accumulate(p._out, stager.binimgs, totals, stager.n_valid, params, thetas,
+                                         valid=stager.valid, valid_cells=valid_cells)
         else:
             tools.val_accumulate(p._out, stager.binimgs, totals, n_valid=stager.n_valid, pos_weight=pos_weight)
         masks.append(p.masks())  # a fresh tensor per batch; the logits are static
+        if mask_mode is not None:
+            valids.append(stager.valid[:b].clone())
         nxt = next(it, None)
         if nxt is not None:
             stager.stage(nxt)
@@ -413,6 +429,13 @@ def predict(a, grid_conf=None, data_aug_conf=None, model: Optional[torch.nn.Modu
         for s in m.cpu().numpy():
             np.save(os.path.join(a.out, f"{index}.npy"), s)
             index += 1
+    if mask_mode is not None:
+        os.makedirs(os.path.join(a.out, "valid"), exist_ok=True)
+        vi = 0
+        for m in valids:
+            for s in m.cpu().numpy():
+                np.save(os.path.join(a.out, "valid", f"{vi}.npy"), s)
+                vi += 1
     t = totals.tolist()
     extra = {}
     if ladder_mode:
@@ -430,6 +453,10 @@ def predict(a, grid_conf=None, data_aug_conf=None, model: Optional[torch.nn.Modu
             "threshold": threshold, "intersection": inter, "union": union, "samples": index, "classes": K,
             "dtype": a.dtype, "graph": bool(a.graph), "bsz": a.bsz,
             "frames_per_s": frames / elapsed if frames and elapsed > 0 else None}
+    if mask_mode is not None:
+        cells = stager.valid.numel() // stager.valid.shape[0]
+        info.update({"valid_mask": mask_mode, "fov_z": list(fov_z),
+                     "valid_fraction": float(valid_cells.item()) / (n_val * cells) if n_val else None})
     with open(os.path.join(a.out, "metrics.json"), "w") as f:
         json.dump(info, f, indent=1)
     return info

@@ -405,6 +405,128 @@ def class_masks(bev_u8: torch.Tensor, label_groups=None, out=None, index_mats=No
     return out
 
 
+# ----------------------------------------------------------------------------- valid-cell mask
+VALID_MASK_MODES = ("grid", "fov")   # LSS_SIMBEV_VALID_GRID / LSS_SIMBEV_VALID_FOV of include/lss_simbev.h
+MAX_FOV_HEIGHTS = 8                  # LSS_SIMBEV_MAX_HEIGHTS
+
+
+def valid_mask_mode(conf: dict):
+    """The valid-cell mask a data_aug_conf asks for: None (the key ``valid_mask`` absent, None or "none"), "grid"
+    (cells whose label source lies inside the labelled grid under the BEV-space augmentation) or "fov" (those that
+    some camera also sees, at one of the heights ``fov_z``). ValueError for another value or bad heights. The batches
+    of such a conf carry the mask after the labels, and this is the flag their consumers are given."""
+    mode = conf.get("valid_mask")
+    if mode is None or mode == "none":
+        return None
+    if mode not in VALID_MASK_MODES:
+        raise ValueError(f"valid_mask {mode!r}: none, grid or fov")
+    fov_heights(conf)
+    return mode
+
+
+def fov_heights(conf: dict) -> Tuple[float, ...]:
+    """The heights (metres, ego frame) a cell is tested at: ``fov_z`` of a data_aug_conf, default (0.0,); 1 to 8
+    finite numbers, else ValueError."""
+    z = conf.get("fov_z", (0.0,))
+    z = (float(z),) if isinstance(z, (int, float)) else tuple(float(v) for v in z)
+    if not 1 <= len(z) <= MAX_FOV_HEIGHTS or not all(math.isfinite(v) for v in z):
+        raise ValueError(f"fov_z {z!r}: 1 to {MAX_FOV_HEIGHTS} finite heights")
+    return z
+
+
+def fov_cameras(rots, trans, intrins, post_rots, post_trans=None) -> torch.Tensor:
+    """The (..., N, 16) fp32 camera blocks ``lss_simbev_valid_mask`` projects cell centres with, from the host rig
+    (rots (..., N, 3, 3), trans (..., N, 3), intrins, post_rots): per camera M = intrins rots^-1 (9, row-major),
+    o = -M trans (3) and P = post_rots[:2, :2] (4) -- get_geometry (src/models.py:170-192) inverted: an ego point p
+    is the camera point M p + o = (u' d, v' d, d), and its pixel is P (u', v') + post_trans[:2]. Computed in
+    float64, rounded once. A rig composed with the BEV-space augmentation needs nothing more:
+    (A rots)^-1 (A p - A t) is the original camera point. post_trans is not used (valid_mask takes it beside the
+    blocks); it is accepted so that a batch's five rig tensors can be passed as they come."""
+    r, t = torch.as_tensor(rots).detach().cpu().double(), torch.as_tensor(trans).detach().cpu().double()
+    k, p = torch.as_tensor(intrins).detach().cpu().double(), torch.as_tensor(post_rots).detach().cpu().double()
+    M = k.matmul(torch.linalg.inv(r))
+    o = -M.matmul(t.unsqueeze(-1)).squeeze(-1)
+    P = p[..., :2, :2]
+    lead = M.shape[:-2]
+    return torch.cat([M.reshape(*lead, 9), o, P.reshape(*lead, 4)], dim=-1).to(torch.float32).contiguous()
+
+
+def valid_mask(cams, post_trans, grid_conf, final_dim, heights=(0.0,), index_mats=None, mode="fov", out=None,
+               keep=None) -> torch.Tensor:
+    """The (n, X, Y) uint8 valid-cell mask of a batch, ``lss_simbev_valid_mask``: 1 where a cell is in the grid --
+    index_mats (n, 2, 3) fp32, the batch's ``label_index_matrix`` rows; None: every cell is -- and, with mode "fov",
+    some camera sees its centre at one of `heights`: cams (n, N, 16) from ``fov_cameras``, post_trans (n, N, 3) or
+    (n, N, 2), the frustum dbound of grid_conf and final_dim (fH, fW). mode "grid": cams and post_trans may be None
+    (n then comes from index_mats or out). Host tensors are uploaded pinned, without blocking; keep: a list that
+    receives what was allocated here -- a caller on a side stream holds it until its event. out: a contiguous uint8
+    device tensor of n * X * Y elements to write. Row i is x cell i, column j is y cell j, as the logits."""
+    if mode not in VALID_MASK_MODES:
+        raise ValueError(f"valid_mask: mode {mode!r}: grid or fov")
+    from .ops import GridSpec
+    from .tools import gen_dx_bx
+    z = fov_heights({"fov_z": heights})
+    X, Y, _ = GridSpec.from_conf(grid_conf).nx
+    dx, bx, _ = gen_dx_bx(grid_conf["xbound"], grid_conf["ybound"], grid_conf["zbound"])
+    d_lo, d_hi = float(grid_conf["dbound"][0]), float(grid_conf["dbound"][1])
+    fH, fW = int(final_dim[0]), int(final_dim[1])
+    fov = mode == "fov"
+    dev = next((t.device for t in (out, cams, index_mats, post_trans) if torch.is_tensor(t) and t.is_cuda), None)
+    if dev is None:
+        raise RuntimeError("lss_carla_amd.simbev: valid_mask runs on the MI355X (pass out= or a device tensor)")
+
+    def device(t, shape_tail, what):
+        t = torch.as_tensor(t)
+        if t.dtype != torch.float32 or tuple(t.shape[1:]) != shape_tail:
+            raise RuntimeError(f"valid_mask: {what} must be (n, {', '.join(map(str, shape_tail))}) fp32, got "
+                               f"{t.dtype} {tuple(t.shape)}")
+        if not t.is_cuda:
+            t = t.contiguous().pin_memory().to(dev, non_blocking=True)
+        elif t.device != dev:
+            raise RuntimeError(f"valid_mask: {what} is on {t.device}, not {dev}")
+        t = t.contiguous()
+        if keep is not None:
+            keep.append(t)
+        return t
+
+    n = N = None
+    cams_d = q_d = mats_d = None
+    if fov:
+        if cams is None or post_trans is None:
+            raise RuntimeError("valid_mask: mode 'fov' needs the camera blocks and post_trans")
+        cams = torch.as_tensor(cams)
+        if cams.dim() != 3 or cams.shape[1] < 1:
+            raise RuntimeError(f"valid_mask: cams must be (n, N, 16) with N >= 1, got {tuple(cams.shape)}")
+        n, N = int(cams.shape[0]), int(cams.shape[1])
+        cams_d = device(cams, (N, 16), "cams")
+        q = torch.as_tensor(post_trans)
+        if q.dim() == 3 and q.shape[-1] == 3:
+            q = q[..., :2]
+        q_d = device(q, (N, 2), "post_trans")
+        if q_d.shape[0] != n:
+            raise RuntimeError(f"valid_mask: post_trans of {q_d.shape[0]} samples for cams of {n}")
+    if index_mats is not None:
+        mats_d = device(index_mats, (2, 3), "index_mats")
+        if n is not None and mats_d.shape[0] != n:
+            raise RuntimeError(f"valid_mask: index_mats of {mats_d.shape[0]} samples for cams of {n}")
+        n = int(mats_d.shape[0])
+    if n is None:
+        if out is None:
+            raise RuntimeError("valid_mask: mode 'grid' without index_mats needs out= (it gives the batch size)")
+        n = out.numel() // (X * Y)
+    if out is None:
+        out = torch.empty(n, X, Y, device=dev, dtype=torch.uint8)
+    elif not (out.is_cuda and out.device == dev and out.dtype == torch.uint8 and out.is_contiguous()
+              and out.numel() == n * X * Y and n > 0):
+        raise RuntimeError(f"out= must be a contiguous uint8 device tensor of {(n, X, Y)}")
+    hz = (ctypes.c_float * len(z))(*z)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().lss_simbev_valid_mask(
+            _lib.ptr(cams_d), _lib.ptr(q_d), n, N or 0, X, Y, float(bx[0]), float(dx[0]), float(bx[1]), float(dx[1]),
+            ctypes.cast(hz, ctypes.c_void_p), len(z), d_lo, d_hi, fH, fW, _lib.ptr(mats_d),
+            VALID_MASK_MODES.index(mode), _lib.ptr(out), _lib.stream_handle(dev)), "lss_simbev_valid_mask")
+    return out
+
+
 # ----------------------------------------------------------------------------- dataset (host side)
 class SimBEVDataset(torch.utils.data.Dataset):
     """src/data_simbev.py:23-265: same layout (SimBEV_cvt_label/scene_*/yaw0pitch0/meta.json, 80/20
@@ -538,12 +660,14 @@ def worker_rnd_init(x):
     np.random.seed(13 + x)  # src/data_simbev.py:310-312
 
 
-def finish_batch(batch, final_dim, device, label_groups=None, bev_aug=False):
+def finish_batch(batch, final_dim, device, label_groups=None, bev_aug=False, valid_mask_conf=None):
     """A collated raw batch -> the reference's (imgs, rots, trans, intrins, post_rots, post_trans,
     [lidar,] binimgs) on `device`, the pixel work done by the HIP kernels. label_groups: K lists of BEV
     channels -> binimgs (B, K, X, Y) (class_masks); None: the reference's vehicle mask, (B, 1, X, Y).
     bev_aug: the batch comes from a conf with the BEV-space augmentation (bev_aug_enabled): the element before
-    the BEV maps is the (B, 2, 3) label index matrices, which warp the labels; the rig is already composed."""
+    the BEV maps is the (B, 2, 3) label index matrices, which warp the labels; the rig is already composed.
+    valid_mask_conf: None (the tuple is as above), or (mode, grid_conf, heights) -- the finished batch then carries,
+    after the labels, the (B, X, Y) uint8 valid-cell mask of ``valid_mask`` on the batch's host rig."""
     imgs_u8, rots, trans, intrins, post_rots, post_trans, aug, rot = batch[:8]
     rest = batch[8:]
     index_mats = None
@@ -565,15 +689,23 @@ def finish_batch(batch, final_dim, device, label_groups=None, bev_aug=False):
     for t in rest[:-1]:
         out.append(t)  # lidar placeholder (VizData)
     out.append(class_masks(rest[-1].to(device, non_blocking=True), label_groups, index_mats=index_mats))
+    if valid_mask_conf is not None:
+        mode, grid_conf, heights = valid_mask_conf
+        X, Y = out[-1].shape[-2:]
+        mask = torch.empty(B, X, Y, device=device, dtype=torch.uint8)
+        cams = fov_cameras(rots, trans, intrins, post_rots) if mode == "fov" else None
+        out.append(valid_mask(cams, post_trans if mode == "fov" else None, grid_conf, final_dim, heights,
+                              index_mats=index_mats, mode=mode, out=mask))
     return tuple(out)
 
 
 class DeviceLoader:
     """Iterates a DataLoader of raw samples and yields finished device batches (finish_batch)."""
 
-    def __init__(self, loader, final_dim, device, label_groups=None, bev_aug=False):
+    def __init__(self, loader, final_dim, device, label_groups=None, bev_aug=False, valid_mask_conf=None):
         self.loader, self.final_dim, self.device = loader, final_dim, torch.device(device)
         self.label_groups, self.bev_aug = label_groups, bool(bev_aug)
+        self.valid_mask_conf = valid_mask_conf  # None, or (mode, grid_conf, heights): finish_batch appends the mask
         self.dataset = loader.dataset
         self.batch_size = loader.batch_size
 
@@ -582,7 +714,11 @@ class DeviceLoader:
 
     def __iter__(self):
         for batch in self.loader:
-            yield finish_batch(batch, self.final_dim, self.device, self.label_groups, self.bev_aug)
+            if self.valid_mask_conf is None:
+                yield finish_batch(batch, self.final_dim, self.device, self.label_groups, self.bev_aug)
+            else:
+                yield finish_batch(batch, self.final_dim, self.device, self.label_groups, self.bev_aug,
+                                   self.valid_mask_conf)
 
 
 def compile_data(version, dataroot, data_aug_conf, grid_conf, bsz, nworkers, parser_name, device="cuda",
@@ -591,8 +727,12 @@ def compile_data(version, dataroot, data_aug_conf, grid_conf, bsz, nworkers, par
     BEV channel groups of a multi-class model's labels (finish_batch); None: the reference's vehicle mask.
     A data_aug_conf with bev_rot_lim / bev_scale_lim / bev_flip (bev_aug_enabled) adds the BEV-space augmentation to
     the training loader -- the rig composed, the labels warped -- and never to the validation loader; both loaders
-    carry the flag (``bev_aug``) that says their raw batches hold the label index matrices."""
+    carry the flag (``bev_aug``) that says their raw batches hold the label index matrices. A data_aug_conf with
+    ``valid_mask`` "grid" or "fov" (valid_mask_mode; heights ``fov_z``) makes both loaders' finished batches carry the
+    valid-cell mask after the labels -- validation's too: that is the point of a masked metric."""
     bev_aug = bev_aug_enabled(data_aug_conf)  # (a bad limit fails here)
+    mask_mode = valid_mask_mode(data_aug_conf)
+    mask_conf = None if mask_mode is None else (mask_mode, grid_conf, fov_heights(data_aug_conf))
     if label_groups is not None:
         group_bits(label_groups)  # a bad group list fails here, not in the first batch
     parser = {"vizdata": VizData, "segmentationdata": SegmentationData}[parser_name]
@@ -603,5 +743,5 @@ def compile_data(version, dataroot, data_aug_conf, grid_conf, bsz, nworkers, par
     valloader = torch.utils.data.DataLoader(valdata, batch_size=bsz, shuffle=False, num_workers=nworkers,
                                             pin_memory=True)
     fd = data_aug_conf["final_dim"]
-    return (DeviceLoader(trainloader, fd, device, label_groups, bev_aug),
-            DeviceLoader(valloader, fd, device, label_groups, bev_aug))
+    return (DeviceLoader(trainloader, fd, device, label_groups, bev_aug, mask_conf),
+            DeviceLoader(valloader, fd, device, label_groups, bev_aug, mask_conf))

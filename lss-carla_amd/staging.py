@@ -8,7 +8,8 @@ are valid. ``BatchStager`` owns those tensors and fills them from the raw batche
   stage(raw)   on the staging stream: H2D copies of the uint8 images / BEV and of the rig, then
                ``lss_simbev_images`` and ``lss_simbev_vehicle_mask`` (``lss_simbev_class_masks`` with
                ``label_groups``; ``lss_simbev_class_masks_warp`` with ``bev_aug``: the batch's label index
-               matrices, uploaded on the same stream) straight into the next of two slots;
+               matrices, uploaded on the same stream; with ``valid_mask``, ``lss_simbev_valid_mask`` into
+               the slot's mask) straight into the next of two slots;
                an event marks the slot ready. Batch k+1 is staged while step k runs.
   commit()     on the current stream: wait for the oldest staged slot's event, copy slot -> static tensors
                (device to device), ``HostInverses.update`` with the slot's host post_rots / intrins, set
@@ -44,6 +45,7 @@ class _Slot:
         self.post_rots = torch.zeros(B, N, 3, 3, device=dev)
         self.post_trans = torch.zeros(B, N, 3, device=dev)
         self.binimgs = torch.zeros(B, K, X, Y, device=dev, dtype=torch.float32)
+        self.valid = None  # (B, X, Y) uint8, all ones, when the stager keeps a valid-cell mask
         self.host_post_rots = None
         self.host_intrins = None
         self.b = 0
@@ -56,11 +58,16 @@ class BatchStager:
     RIG = ("rots", "trans", "intrins", "post_rots", "post_trans")
 
     def __init__(self, final_dim: Sequence[int], B: int, N: int, src_hw: Sequence[int], grid: dict, device,
-                 label_groups=None, bev_aug=False):
+                 label_groups=None, bev_aug=False, valid_mask=None, fov_z=(0.0,), dbound=None):
         """label_groups: K lists of BEV channels, one label channel each (simbev.class_masks): ``binimgs`` and
         both slots are (B, K, X, Y); None: the reference's vehicle mask, K = 1. bev_aug: the raw batches come from a
         conf with the BEV-space augmentation (simbev.bev_aug_enabled): the element before the BEV maps is the
-        (b, 2, 3) label index matrices, which warp the labels; the rig arrives composed."""
+        (b, 2, 3) label index matrices, which warp the labels; the rig arrives composed.
+        valid_mask: None, "grid" or "fov" (simbev.valid_mask_mode): the stager then keeps ``valid``, the (B, X, Y) uint8
+        valid-cell mask of the committed batch (all ones before the first), filled on the staging stream by
+        ``lss_simbev_valid_mask`` from the batch's host rig (camera blocks built in float64, uploaded pinned on that
+        stream and held until the slot's event) at the heights fov_z; dbound overrides the grid's frustum bounds.
+        Training and validation batches are masked alike; without index matrices every cell is in the grid."""
         dev = torch.device(device)
         if dev.type != "cuda":
             raise RuntimeError("BatchStager: the static tensors live on the MI355X (no CPU fallback)")
@@ -79,6 +86,12 @@ class BatchStager:
         self.bev_aug = bool(bev_aug)
         K = 1 if label_groups is None else len(self.label_groups)
         self.binimgs = torch.zeros(B, K, X, Y, device=dev, dtype=torch.float32)
+        if valid_mask is not None and valid_mask not in simbev.VALID_MASK_MODES:
+            raise ValueError(f"BatchStager: valid_mask {valid_mask!r}: None, grid or fov")
+        self.valid_mask = valid_mask
+        self.fov_z = simbev.fov_heights({"fov_z": fov_z})
+        self.grid = dict(grid) if dbound is None else {**grid, "dbound": list(dbound)}
+        self.valid = None if valid_mask is None else torch.ones(B, X, Y, device=dev, dtype=torch.uint8)
         self.n_valid = torch.full((1,), B, device=dev, dtype=torch.int32)
         self.hinv = ops.HostInverses(B * N, dev)
         # the host rig HostInverses inverts: samples past a partial batch keep their previous matrices
@@ -86,6 +99,9 @@ class BatchStager:
         self._host_intrins = torch.eye(3).repeat(B, N, 1, 1)
         self.stream = torch.cuda.Stream(dev)
         self._slots = [_Slot(B, N, fH, fW, src_hw, K, X, Y, dev) for _ in range(2)]
+        if valid_mask is not None:
+            for slot in self._slots:
+                slot.valid = torch.ones(B, X, Y, device=dev, dtype=torch.uint8)
         self._next = 0
         self._staged: deque = deque()   # slots staged and not yet committed, oldest first
         self._retired: List[tuple] = []  # (event, tensors) of reused slots whose event had not completed
@@ -127,6 +143,9 @@ class BatchStager:
             rec = {"resize_dims": (a[0], a[1]), "crop": tuple(a[2:6]), "flip": bool(a[6]), "rotate": float(rot[i])}
             augs.extend([rec] * N)
         keep = [raw_batch]  # the copies below read the batch's host memory
+        cams = None
+        if self.valid_mask == "fov":  # the camera blocks of the batch's (composed) rig: host float64, rounded once
+            cams = simbev.fov_cameras(rots, trans, intrins, post_rots)
         st = self.stream
         if slot.consumed is not None:
             st.wait_event(slot.consumed)  # commit's copies out of this slot come first
@@ -140,6 +159,10 @@ class BatchStager:
             simbev.augment_images(slot.u8[:b * N], augs, self.final_dim, out=slot.imgs[:b], keep=keep)
             simbev.class_masks(slot.bev_u8[:b], self.label_groups, out=slot.binimgs[:b], index_mats=index_mats,
                                keep=keep)
+            if self.valid_mask is not None:
+                simbev.valid_mask(cams, post_trans if cams is not None else None, self.grid, self.final_dim,
+                                  self.fov_z, index_mats=index_mats, mode=self.valid_mask, out=slot.valid[:b],
+                                  keep=keep)
             slot.ready = torch.cuda.Event()
             slot.ready.record(st)
         slot.host_post_rots, slot.host_intrins, slot.b, slot.keep = post_rots, intrins, b, keep
@@ -155,6 +178,8 @@ class BatchStager:
         cur.wait_event(slot.ready)
         for name in ("imgs", "binimgs") + self.RIG:
             getattr(self, name)[:b].copy_(getattr(slot, name)[:b], non_blocking=True)
+        if self.valid is not None:
+            self.valid[:b].copy_(slot.valid[:b], non_blocking=True)
         self._host_post_rots[:b].copy_(slot.host_post_rots)
         self._host_intrins[:b].copy_(slot.host_intrins)
         self.hinv.update(self._host_post_rots, self._host_intrins)

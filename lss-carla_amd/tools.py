@@ -131,6 +131,95 @@ class _BceLogitsPerClass(torch.autograd.Function):
         return _BceLogits.backward(ctx, g)
 
 
+def masked_mean_loss(x: torch.Tensor, target: torch.Tensor, valid: torch.Tensor, params: torch.Tensor):
+    """(loss, d loss / dx) of the masked loss in torch, fp32: focal_terms per element with the rows (w_pos, w_neg,
+    gamma) of params (K, 3), elements whose cell has valid == 0 selected out by torch.where -- a NaN or an infinity
+    there reaches neither the loss nor another element's gradient -- and the sum divided by max(M, 1), M the number
+    of valid elements. valid: (batch, X, Y) (or (batch, 1, X, Y)), one plane for the K classes of a sample."""
+    p = params.to(device=x.device, dtype=torch.float32)
+    if p.shape[0] > 1:
+        p = p.view(p.shape[0], 1, 1, 3)
+    on = _broadcast_valid(valid, x)
+    l, g = focal_terms(x.detach().float(), target != 0, p[..., 0], p[..., 1], p[..., 2])
+    zero = torch.zeros((), device=x.device, dtype=torch.float32)
+    m = on.sum().clamp(min=1).to(torch.float32)
+    return torch.where(on, l, zero).sum() / m, torch.where(on, g, zero) / m
+
+
+def _broadcast_valid(valid: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    """The (batch, plane) mask as booleans of x's shape (batch, K, ...)."""
+    if x.dim() < 2 or valid.numel() * x.shape[1] != x.numel() or valid.shape[0] != x.shape[0]:
+        raise RuntimeError(f"valid {tuple(valid.shape)} is not one plane per sample of logits {tuple(x.shape)}")
+    v = (valid != 0).to(x.device).reshape(x.shape[0], 1, *x.shape[2:])
+    return v.expand_as(x)
+
+
+class _SegLossMaskedTorch(torch.autograd.Function):
+    """The masked loss where the kernel does not apply (CPU, strided or misaligned tensors): masked_mean_loss."""
+
+    @staticmethod
+    def forward(ctx, x, target, valid, params: torch.Tensor):
+        loss, g = masked_mean_loss(x, target, valid, params)
+        ctx.save_for_backward(g.to(x.dtype))
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return (grad.float() * g.float()).to(grad.dtype), None, None, None
+
+
+class _SegLossMasked(torch.autograd.Function):
+    """``lss_seg_loss_masked``: the loss over the valid cells and its gradient over n in one pass (the count of valid
+    elements M is not known yet), the fold writing n / max(M, 1) to a device scalar; the backward
+    (``lss_seg_loss_masked_bwd``) multiplies by it and by the incoming gradient. params: the (K, 3) device rows; valid: (batch, plane) uint8 on the device, read there."""
+
+    @staticmethod
+    def forward(ctx, x, target, valid, params: torch.Tensor):
+        from . import _lib
+        lib = _lib.load()
+        n = x.numel()
+        K = params.shape[0]
+        partial = torch.empty(2 * int(lib.lss_bce_partials(n)), device=x.device, dtype=torch.float32)
+        loss = torch.empty((), device=x.device, dtype=torch.float32)
+        scale = torch.empty((), device=x.device, dtype=torch.float32)
+        grad = torch.empty_like(x)
+        _lib.check(lib.lss_seg_loss_masked(_lib.ptr(x), _lib.dtype_code(x.dtype), _lib.ptr(target), _lib.ptr(valid), n,
+                                           n // (x.shape[0] * K), K, _lib.ptr(params), _lib.ptr(partial),
+                                           _lib.ptr(loss), _lib.ptr(scale), _lib.ptr(grad),
+                                           _lib.stream_handle(x.device)), "lss_seg_loss_masked")
+        ctx.save_for_backward(grad, scale)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import _lib
+        grad, scale = ctx.saved_tensors
+        g = g.float().contiguous()
+        dx = torch.empty_like(grad)
+        _lib.check(_lib.load().lss_seg_loss_masked_bwd(_lib.ptr(grad), _lib.dtype_code(grad.dtype), grad.numel(),
+                                                       _lib.ptr(g), _lib.ptr(scale), _lib.ptr(dx),
+                                                       _lib.stream_handle(grad.device)), "lss_seg_loss_masked_bwd")
+        return dx, None, None, None
+
+
+def _masked_loss(ypred, ytgt, valid, params: torch.Tensor):
+    """The masked loss of SimpleLoss / FocalLoss: the kernel under their conditions (and a contiguous uint8 device
+    mask), else the same formula in torch."""
+    if ytgt.shape != ypred.shape:
+        raise RuntimeError(f"labels {tuple(ytgt.shape)} for logits {tuple(ypred.shape)}")
+    _broadcast_valid(valid, ypred)  # (the shape check)
+    K = params.shape[0]
+    if (ypred.is_cuda and ypred.dtype in (torch.float32, torch.bfloat16) and ytgt.dtype == torch.float32
+            and ytgt.device == ypred.device and ypred.is_contiguous() and ytgt.is_contiguous()
+            and ypred.data_ptr() % 16 == 0 and ytgt.data_ptr() % 16 == 0 and ypred.numel() > 0 and ypred.dim() >= 2
+            and ypred.shape[1] == K and valid.dtype == torch.uint8 and valid.device == ypred.device
+            and valid.is_contiguous() and params.device == ypred.device and params.dtype == torch.float32
+            and params.is_contiguous()):
+        return _SegLossMasked.apply(ypred, ytgt, valid, params)
+    return _SegLossMaskedTorch.apply(ypred, ytgt, valid, params)
+
+
 class SimpleLoss(torch.nn.Module):
     """BCE-with-logits with a positive-class weight (src/tools.py:222-230).
 
@@ -159,10 +248,28 @@ class SimpleLoss(torch.nn.Module):
             self.pos_weight_value = None
             self.register_buffer("pos_weight_classes", w.clone(), persistent=False)
 
-    def forward(self, ypred, ytgt):
+    def masked_params(self, K: int, device) -> torch.Tensor:
+        """The (K, 3) rows (pw_k, 1, 0) of the masked loss on `device`, rebuilt only when the class weights' buffer
+        changed (its version) -- so a captured step builds them once, before the capture."""
+        pc = self.pos_weight_classes
+        key = (K, torch.device(device), None if pc is None else (pc.data_ptr(), pc._version))
+        if getattr(self, "_masked_key", None) != key:
+            w = class_weights(self.pos_weight_value if pc is None else pc, K, device)
+            self._masked_rows = torch.stack([w, torch.ones_like(w), torch.zeros_like(w)], dim=1).contiguous()
+            self._masked_key = key
+        return self._masked_rows
+
+    def forward(self, ypred, ytgt, valid=None):
+        """valid: None, or the (batch, X, Y) uint8 valid-cell mask (simbev.valid_mask): the loss is then the mean
+        over the valid cells' elements only -- ``lss_seg_loss_masked`` with the rows (pw, 1, 0) on the GPU, the same
+        formula in torch elsewhere; labels are read as hard (t != 0)."""
         pc = self.pos_weight_classes
         if pc is not None and not (ypred.dim() == 4 and ypred.shape[1] == pc.numel()):
             raise RuntimeError(f"SimpleLoss: {pc.numel()} class weights for logits {tuple(ypred.shape)}")
+        if valid is not None:
+            if ypred.dim() < 2:
+                raise RuntimeError(f"SimpleLoss: a mask needs (batch, K, ...) logits, got {tuple(ypred.shape)}")
+            return _masked_loss(ypred, ytgt, valid, self.masked_params(int(ypred.shape[1]), ypred.device))
         if (ypred.is_cuda and ypred.dtype in (torch.float32, torch.bfloat16) and ytgt.dtype == torch.float32
                 and ytgt.device == ypred.device and ytgt.shape == ypred.shape and ypred.is_contiguous()
                 and ytgt.is_contiguous() and ypred.data_ptr() % 16 == 0 and ytgt.data_ptr() % 16 == 0
@@ -282,12 +389,18 @@ class FocalLoss(torch.nn.Module):
         self.classes = len(rows)
         self.register_buffer("focal_params", torch.tensor(rows, dtype=torch.float32), persistent=False)
 
-    def forward(self, ypred, ytgt):
+    def forward(self, ypred, ytgt, valid=None):
+        """valid: None, or the (batch, X, Y) uint8 valid-cell mask (simbev.valid_mask): the mean is then over the
+        valid cells' elements only (``lss_seg_loss_masked`` on the GPU, the same formula in torch elsewhere)."""
         K, p = self.classes, self.focal_params
         if K > 1 and not (ypred.dim() == 4 and ypred.shape[1] == K):
             raise RuntimeError(f"FocalLoss: {K} classes for logits {tuple(ypred.shape)}")
         if ytgt.shape != ypred.shape:
             raise RuntimeError(f"FocalLoss: labels {tuple(ytgt.shape)} for logits {tuple(ypred.shape)}")
+        if valid is not None:
+            if ypred.dim() < 2 or ypred.shape[1] != K:
+                raise RuntimeError(f"FocalLoss: a mask needs (batch, {K}, ...) logits, got {tuple(ypred.shape)}")
+            return _masked_loss(ypred, ytgt, valid, p)
         if (ypred.is_cuda and ypred.dtype in (torch.float32, torch.bfloat16) and ytgt.dtype == torch.float32
                 and ytgt.device == ypred.device and ypred.is_contiguous() and ytgt.is_contiguous()
                 and ypred.data_ptr() % 16 == 0 and ytgt.data_ptr() % 16 == 0 and ypred.numel() > 0 and ypred.dim() >= 1
@@ -395,13 +508,17 @@ def val_accumulate(preds: torch.Tensor, binimgs: torch.Tensor, totals: torch.Ten
 
 
 def seg_metrics_accumulate(preds: torch.Tensor, binimgs: torch.Tensor, totals: torch.Tensor, n_valid, params: torch.Tensor,
-                           thetas: torch.Tensor) -> torch.Tensor:
+                           thetas: torch.Tensor, valid=None, valid_cells=None) -> torch.Tensor:
     """One validation batch into the accumulators of a threshold ladder, ``lss_seg_metrics_accum``
     (include/lss_convs.h): params the (K, 3) fp32 device rows (w_pos, w_neg, gamma) of the loss term
     (FocalLoss.focal_params; (pw, 1, 0) is SimpleLoss), thetas T ascending fp32 logit thresholds on the device.
     totals (1 + K + 2 K T float64 on the device) += the loss term, P_k, TP_kj, PP_kj over the first ``n_valid``
     samples (one int32 on the device; None: all). Device tensors only; two launches, no host synchronisation,
-    capturable (the scratch is kept per device and size, as val_accumulate's)."""
+    capturable (the scratch is kept per device and size, as val_accumulate's).
+
+    valid: the (batch, X, Y) uint8 device valid-cell mask (simbev.valid_mask) -- ``lss_seg_metrics_accum_masked``: only
+    valid cells of the first n_valid samples are counted, and totals[0] += n_valid x the mean loss over their
+    elements; valid_cells (one float64 on the device, optional) += the number of valid cells counted."""
     from . import _lib
     if not (preds.is_cuda and all(v.device == preds.device for v in (binimgs, totals, params, thetas))):
         raise RuntimeError("seg_metrics_accumulate: device tensors only (no CPU fallback)")
@@ -418,15 +535,33 @@ def seg_metrics_accumulate(preds: torch.Tensor, binimgs: torch.Tensor, totals: t
     if n_valid is not None and not (n_valid.device == preds.device and n_valid.dtype == torch.int32
                                     and n_valid.numel() == 1):
         raise RuntimeError("seg_metrics_accumulate: n_valid must be one int32 on the logits' device")
+    if valid is None and valid_cells is not None:
+        raise RuntimeError("seg_metrics_accumulate: valid_cells counts the cells of valid=")
+    if valid is not None:
+        if not (valid.device == preds.device and valid.dtype == torch.uint8 and valid.is_contiguous() and preds.dim() >= 2
+                and valid.shape[0] == preds.shape[0] and valid.numel() * K == preds.numel()):
+            raise RuntimeError(f"seg_metrics_accumulate: valid {tuple(valid.shape)} {valid.dtype} is not one contiguous "
+                               f"uint8 plane per sample of logits {tuple(preds.shape)} on their device")
+        if valid_cells is not None and not (valid_cells.device == preds.device and valid_cells.dtype == torch.float64
+                                            and valid_cells.numel() == 1):
+            raise RuntimeError("seg_metrics_accumulate: valid_cells must be one float64 on the logits' device")
     lib = _lib.load()
     x, t = preds.detach().contiguous(), binimgs.contiguous()
     batch = x.shape[0]
     per_sample = x.numel() // batch
-    nbytes = int(lib.lss_seg_metrics_partial_bytes(x.numel(), K, T))
+    nbytes = int((lib.lss_seg_metrics_partial_bytes if valid is None else lib.lss_seg_metrics_masked_partial_bytes)(
+        x.numel(), K, T))
     key = (x.device, nbytes)
     partial = _VAL_PARTIAL.get(key)
     if partial is None:
         partial = _VAL_PARTIAL[key] = torch.empty(nbytes // 8, device=x.device, dtype=torch.float64)
+    if valid is not None:
+        _lib.check(lib.lss_seg_metrics_accum_masked(_lib.ptr(x), _lib.dtype_code(x.dtype), _lib.ptr(t), _lib.ptr(valid),
+                                                    per_sample, batch, _lib.ptr(n_valid), per_sample // K, K,
+                                                    _lib.ptr(params), _lib.ptr(thetas), T, _lib.ptr(totals),
+                                                    _lib.ptr(valid_cells), _lib.ptr(partial),
+                                                    _lib.stream_handle(x.device)), "lss_seg_metrics_accum_masked")
+        return totals
     _lib.check(lib.lss_seg_metrics_accum(_lib.ptr(x), _lib.dtype_code(x.dtype), _lib.ptr(t), per_sample, batch,
                                          _lib.ptr(n_valid), per_sample // K, K, _lib.ptr(params), _lib.ptr(thetas), T,
                                          _lib.ptr(totals), _lib.ptr(partial), _lib.stream_handle(x.device)),

@@ -43,7 +43,7 @@ class TrainStep:
                  max_grad_norm: float = 5.0, pre_step: Optional[Callable[[], None]] = None,
                  overlap_all_reduce: bool = False, force_collectives: bool = False,
                  skip_nonfinite: bool = False, keep_preds: bool = False, lr_schedule=None, ema=None,
-                 ema_decay: float = 0.999, ema_warmup: bool = True):
+                 ema_decay: float = 0.999, ema_warmup: bool = True, valid: Optional[torch.Tensor] = None):
         """overlap_all_reduce: all-reduce each parameter's gradient (e.g. each FlatParamGroups
         master) from its post-accumulate hook, on a side stream, while the backward continues -- inside
         the captured graph too; the step waits for them before the update. force_collectives: issue
@@ -55,8 +55,12 @@ class TrainStep:
         computes the learning rate on the device from Adam's step count, so replays follow it (``self.lr``: the
         last applied rate, one fp32 on the device); ema: one fp32 tensor per entry of params (e.g.
         FlatParamGroups.enable_ema()), averaged in the Adam pass with ema_decay / ema_warmup (optim.ClipAdam).
-        Either needs the HIP update, as skip_nonfinite does."""
+        Either needs the HIP update, as skip_nonfinite does. valid: the static (B, X, Y) uint8 valid-cell mask (e.g.
+        ``BatchStager.valid``): the step then calls ``loss_fn(preds, labels, valid)`` -- tools.SimpleLoss / FocalLoss
+        average over the valid cells only. The step stays captured: the mask is read on the device and so is the count
+        of valid elements."""
         self.forward, self.inputs, self.labels = forward, tuple(inputs), labels
+        self.valid = valid
         # host work staged into the step's static device inputs before each step is launched
         # (e.g. ops.HostInverses.update: the reference's host torch.inverse of the rig)
         self.pre_step = pre_step
@@ -101,7 +105,8 @@ class TrainStep:
         if self.keep_preds:
             self.static_preds = preds.detach()
         # (a loss that computes in fp32 itself, tools.SimpleLoss, takes the bf16 logits: no cast kernels)
-        loss = self.loss_fn(preds if getattr(self.loss_fn, "computes_in_fp32", False) else preds.float(), self.labels)
+        logits = preds if getattr(self.loss_fn, "computes_in_fp32", False) else preds.float()
+        loss = self.loss_fn(logits, self.labels) if self.valid is None else self.loss_fn(logits, self.labels, self.valid)
         loss.backward()
         if self.overlap:  # the collectives the hooks started: the update waits for them
             for w in self._works:
@@ -224,12 +229,16 @@ class EvalStep:
     def __init__(self, model: torch.nn.Module, forward: Callable[..., torch.Tensor], inputs: Sequence[torch.Tensor],
                  labels: torch.Tensor, n_valid: Optional[torch.Tensor] = None, pos_weight=2.13,
                  amp_dtype: Optional[torch.dtype] = torch.bfloat16, n_samples: Optional[int] = None,
-                 loss=None, thresholds=None):
+                 loss=None, thresholds=None, valid: Optional[torch.Tensor] = None):
         """loss: a tools.FocalLoss whose term the loss total sums (its ``focal_params`` buffer is read on the device;
         None: SimpleLoss(pos_weight)). thresholds: a ladder of probability thresholds to count the IoU at. With
         either, the step accumulates through ``tools.seg_metrics_accumulate`` (``lss_seg_metrics_accum``) at the
         ladder and 0.5, sorted, into 1 + K + 2 K T totals; ``read()`` keeps its keys -- the IoU from the 0.5 column --
-        and, for a ladder, adds ``tools.seg_metrics_summary``'s. With neither, nothing differs from before."""
+        and, for a ladder, adds ``tools.seg_metrics_summary``'s. With neither, nothing differs from before.
+        valid: the static (B, X, Y) uint8 valid-cell mask (e.g. ``BatchStager.valid``): the step always accumulates
+        through the seg-metrics path (the 0.5 column present), masked -- ``lss_seg_metrics_accum_masked`` -- so the loss
+        and every IoU are over valid cells, and ``read()`` adds ``valid_fraction``: valid cells / cells, over the
+        samples counted."""
         self.model, self.forward, self.inputs, self.labels = model, forward, tuple(inputs), labels
         self.n_samples = n_samples  # len(valloader.dataset): what read() divides the loss total by
         self.n_valid, self.amp_dtype = n_valid, amp_dtype
@@ -244,7 +253,9 @@ class EvalStep:
         self.totals = torch.zeros(1 + 2 * self.classes, device=labels.device, dtype=torch.float64)
         self.ladder = None if thresholds is None else [float(v) for v in thresholds]
         self.columns = self.params = self.thetas = None
-        if loss is not None or thresholds is not None:
+        self.valid = valid
+        self.valid_cells = None if valid is None else torch.zeros(1, device=labels.device, dtype=torch.float64)
+        if loss is not None or thresholds is not None or valid is not None:
             from .predict import threshold_logit
             K, dev = self.classes, labels.device
             self.columns = sorted(set((self.ladder or []) + [0.5]))
@@ -284,7 +295,7 @@ class EvalStep:
                                          pos_weight=self.pos_weight)
                 else:
                     tools.seg_metrics_accumulate(preds, self.labels, self.totals, self.n_valid, self.params,
-                                                 self.thetas)
+                                                 self.thetas, valid=self.valid, valid_cells=self.valid_cells)
         finally:
             self.model.train(was_training)
 
@@ -313,6 +324,8 @@ class EvalStep:
 
     def reset(self) -> None:
         self.totals.zero_()
+        if self.valid_cells is not None:
+            self.valid_cells.zero_()
 
     def read(self, n_samples: Optional[int] = None) -> dict:
         """get_val_info's dict {"loss", "iou", "iou_per_class"}: the loss total over ``n_samples``
@@ -336,4 +349,6 @@ class EvalStep:
             sub = t[:1 + K] + [TP[k][j] for k in range(K) for j in cols] + [PP[k][j] for k in range(K) for j in cols]
             extra = tools.seg_metrics_summary(sub, K, self.ladder, n)
             info.update({k: v for k, v in extra.items() if k != "loss"})
+        if self.valid is not None:  # valid cells over the cells of the samples counted
+            info["valid_fraction"] = float(self.valid_cells.item()) / (n * (self.valid.numel() // self.valid.shape[0]))
         return info

@@ -151,6 +151,17 @@ def parse_thresholds(text):
     return vals
 
 
+def parse_heights(text, name="--fov_z"):
+    """``--fov_z 0.0`` -> (0.0,); ``--fov_z 0.0,1.5`` -> (0.0, 1.5): the heights a cell is tested at (1 to 8); a
+    sequence of numbers passes through the same check."""
+    from . import simbev
+    items = [v for v in str(text).split(",") if v.strip()] if isinstance(text, str) else text
+    try:
+        return simbev.fov_heights({"fov_z": [float(v) for v in items] if not isinstance(items, (int, float)) else items})
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} {text!r}: 1 to 8 finite heights in metres, comma separated") from None
+
+
 def _loss_setup(loss, pos_weight, focal_gamma, focal_alpha):
     """(pos_weight, focal): the weight SimpleLoss / validation take (None: the reference's 2.13) and, for
     loss == "focal", tools.FocalLoss's keyword arguments -- pos_weight becomes w_pos unless focal_alpha is given;
@@ -217,7 +228,9 @@ def build_step(grid_conf, data_aug_conf, bsz, device, *, dtype="bf16", lr=1e-3, 
     masters get EMA twins (FlatParamGroups.enable_ema) the update averages into, and the EvalStep runs on them
     (``forward_ema``: the working copies materialised from the EMA by the same launch).
     A data_aug_conf that asks for the BEV-space augmentation (simbev.bev_aug_enabled) makes the stager expect the
-    label index matrices in its raw batches, as ``compile_data``'s loaders of the same conf provide them."""
+    label index matrices in its raw batches, as ``compile_data``'s loaders of the same conf provide them. One that
+    asks for a valid-cell mask (simbev.valid_mask_mode: ``valid_mask`` "grid" / "fov", heights ``fov_z``) makes the
+    stager keep the mask, the TrainStep average its loss over valid cells and the EvalStep count valid cells only."""
     import lss_carla_amd as L
     from . import parallel, simbev, tools
     from .flat_params import FlatParamGroups, lss_backward_groups
@@ -234,9 +247,12 @@ def build_step(grid_conf, data_aug_conf, bsz, device, *, dtype="bf16", lr=1e-3, 
     flat = FlatParamGroups(model, lss_backward_groups(), cast_dtype=amp_dtype)
     masters = flat.masters
     opt = torch.optim.Adam(masters, lr=lr, weight_decay=weight_decay, fused=True, capturable=True)
+    mask_mode = simbev.valid_mask_mode(data_aug_conf)
+    mask_args = {} if mask_mode is None else {"valid_mask": mask_mode, "fov_z": simbev.fov_heights(data_aug_conf)}
     stager = BatchStager(data_aug_conf["final_dim"], bsz, len(simbev.CAMERA_ORDER),
                          (data_aug_conf["H"], data_aug_conf["W"]), grid_conf, device, label_groups=label_groups,
-                         bev_aug=simbev.bev_aug_enabled(data_aug_conf))
+                         bev_aug=simbev.bev_aug_enabled(data_aug_conf), **mask_args)
+    step_mask = {} if mask_mode is None else {"valid": stager.valid}
     model.static_inverses = (stager.hinv.pinv, stager.hinv.kinv)  # staged by the stager's commit
     if loss not in ("bce", "focal"):
         raise ValueError(f"loss {loss!r}: bce or focal")
@@ -252,10 +268,11 @@ def build_step(grid_conf, data_aug_conf, bsz, device, *, dtype="bf16", lr=1e-3, 
     step = TrainStep(forward, stager.inputs, stager.binimgs, loss_fn, opt, masters, all_reduce=False,
                      amp_dtype=amp_dtype, max_grad_norm=max_grad_norm, pre_step=None,
                      skip_nonfinite=bool(skip_nonfinite), keep_preds=True, lr_schedule=lr_schedule, ema=emas,
-                     ema_decay=float(ema_decay) if emas is not None else 0.999, ema_warmup=bool(ema_warmup))
+                     ema_decay=float(ema_decay) if emas is not None else 0.999, ema_warmup=bool(ema_warmup),
+                     **step_mask)
     evaluate = EvalStep(model, forward_eval, stager.inputs, stager.binimgs, n_valid=stager.n_valid,
                         pos_weight=pos_weight, amp_dtype=amp_dtype, n_samples=n_val,
-                        loss=loss_fn if loss == "focal" else None, thresholds=iou_thresholds)
+                        loss=loss_fn if loss == "focal" else None, thresholds=iou_thresholds, **step_mask)
     return {"model": model, "flat": flat, "masters": masters, "opt": opt, "stager": stager, "step": step,
             "evaluate": evaluate, "loss_fn": loss_fn, "forward": forward, "label_groups": label_groups,
             "emas": emas, "forward_eval": forward_eval}
@@ -317,6 +334,8 @@ def train(
     bev_rot_lim=(0.0, 0.0),
     bev_scale_lim=(1.0, 1.0),
     bev_flip=False,
+    valid_mask=None,
+    fov_z=(0.0,),
 ):
     """Train LiftSplatShoot on a SimBEV tree; the reference's arguments (train_simbev.py:23-98) plus:
 
@@ -349,7 +368,13 @@ def train(
     image augmentation's values; the rig is composed with it on the host and the labels are warped by the staging
     stream's label kernel (simbev.class_masks, index_mats=). Validation is never augmented, the captured step and the
     checkpoints do not change, and the neutral defaults leave the loader exactly as it was. When on, the ``config``
-    event carries the three values. Argument errors raise ValueError before anything is looked for or built.
+    event carries the three values.
+    valid_mask: None / "none", "grid" or "fov" -- the loss and every metric then count valid cells only: cells whose
+    label source lies inside the labelled grid under the BEV-space augmentation ("grid") and that some camera sees at
+    one of the heights fov_z, metres ("fov": inside the frustum of dbound and final_dim). The mask is made per batch on
+    the staging stream (simbev.valid_mask), for validation batches too; the step stays captured. The ``config`` event
+    then carries ``valid_mask`` and ``fov_z``, ``val`` events gain ``valid_fraction``, and the training IoU counts
+    valid cells. Off, nothing differs. Argument errors raise ValueError before anything is looked for or built.
     Returns a summary dict (counter, epoch, best_val_iou, skipped, frames_per_s of the training steps)."""
     from . import checkpoint, simbev, tools
 
@@ -363,6 +388,8 @@ def train(
     bev_aug_conf = {"bev_rot_lim": tuple(float(v) for v in bev_rot_lim),
                     "bev_scale_lim": tuple(float(v) for v in bev_scale_lim), "bev_flip": bool(bev_flip)}
     bev_on = simbev.bev_aug_enabled(bev_aug_conf)
+    mask_conf = {"valid_mask": valid_mask, "fov_z": parse_heights(fov_z, "fov_z")}
+    mask_mode = simbev.valid_mask_mode(mask_conf)
     if gpuid < 0 or not torch.cuda.is_available():
         raise RuntimeError("lss_carla_amd.trainer: needs an MI355X (the hot path has no CPU fallback)")
     if ncams != len(simbev.CAMERA_ORDER):
@@ -377,6 +404,8 @@ def train(
                      "rand_flip": rand_flip, "bot_pct_lim": bot_pct_lim, "Ncams": ncams}
     if bev_on:
         data_aug_conf.update(bev_aug_conf)
+    if mask_mode is not None:
+        data_aug_conf.update({"valid_mask": mask_mode, "fov_z": mask_conf["fov_z"]})
     config = {"dataroot": str(dataroot), "nepochs": nepochs, "batch_size": bsz, "learning_rate": lr,
               "weight_decay": weight_decay, "num_workers": nworkers, "num_cameras": ncams, "image_H": H, "image_W": W,
               "final_dim": list(final_dim), "max_grad_norm": max_grad_norm, "pos_weight": pos_weight,
@@ -398,9 +427,11 @@ def train(
         config.update({"ema_decay": float(ema_decay), "ema_warmup": bool(ema_warmup)})
     if bev_on:
         config.update({k: list(v) if isinstance(v, tuple) else v for k, v in bev_aug_conf.items()})
+    if mask_mode is not None:
+        config.update({"valid_mask": mask_mode, "fov_z": list(mask_conf["fov_z"])})
     log = _Log(logdir, use_wandb, {"project": wandb_project, "name": wandb_name, "entity": wandb_entity}, config)
 
-    if ("loss" in config or bev_on) and not (sched_on or ema_on):
+    if ("loss" in config or bev_on or mask_mode is not None) and not (sched_on or ema_on):
         log.event("config", 0, **config)
 
     device = torch.device(f"cuda:{gpuid}")
@@ -526,14 +557,19 @@ def train(
                 log.event("train", counter, epoch=epoch, loss=last_loss, **extra)
             if counter % iou_step == 0:
                 extra = {}
+                iou_pred, iou_tgt = step.static_preds, stager.binimgs
+                if mask_mode is not None:  # valid cells only: masked-out cells are neither predicted nor labelled
+                    on = (stager.valid != 0).unsqueeze(1)
+                    iou_pred = torch.where(on, iou_pred.float(), torch.full((), -1.0, device=device))
+                    iou_tgt = torch.where(on, iou_tgt, torch.zeros((), device=device))
                 if n_out > 1:
-                    ci, cu = tools.get_batch_iou_per_class(step.static_preds, stager.binimgs)
+                    ci, cu = tools.get_batch_iou_per_class(iou_pred, iou_tgt)
                     ci, cu = ci.tolist(), cu.tolist()
                     extra["iou_per_class"] = [i / u if u > 0 else None for i, u in zip(ci, cu)]
                     seen = [v for v in extra["iou_per_class"] if v is not None]
                     iou = sum(seen) / len(seen) if seen else 1.0  # (get_batch_iou's value for an empty union)
                 else:
-                    _, _, iou = tools.get_batch_iou(step.static_preds, stager.binimgs)
+                    _, _, iou = tools.get_batch_iou(iou_pred, iou_tgt)
                 skipped = int(step.skipped.item()) if step.skipped is not None else 0
                 log.event("train_iou", counter, epoch=epoch, iou=iou, skipped=skipped, **extra)
             if will_val or counter % save_step == 0:
@@ -547,6 +583,8 @@ def train(
                     extra.update({k: info[k] for k in ("iou_max", "iou_max_per_class", "best_threshold_per_class")})
                 if ema_on:
                     extra["weights"] = "ema"
+                if mask_mode is not None:
+                    extra["valid_fraction"] = info["valid_fraction"]
                 log.event("val", counter, epoch=epoch, loss=info["loss"], iou=info["iou"], **extra)
                 if info["iou"] > best_val_iou:
                     best_val_iou = info["iou"]
@@ -647,6 +685,11 @@ def main(argv=None):
                    help="BEV-space augmentation: isotropic scale of the ego frame, lo,hi (e.g. 0.9,1.1)")
     p.add_argument("--bev_flip", type=int, default=0, choices=[0, 1],
                    help="BEV-space augmentation: flip x and y of the ego frame, a coin each")
+    p.add_argument("--valid_mask", default="none", choices=["none", "grid", "fov"],
+                   help="count only valid cells in the loss and the metrics: inside the labelled grid under the BEV-space "
+                        "augmentation (grid), and seen by a camera (fov)")
+    p.add_argument("--fov_z", type=str, default="0.0",
+                   help="--valid_mask fov: the heights (metres) a cell is tested at, 1 to 8: 0.0[,1.5,...]")
     a = p.parse_args(argv)
     return train(dataroot=a.dataroot, nepochs=a.nepochs, gpuid=a.gpuid, H=a.H, W=a.W, final_dim=(a.final_h, a.final_w),
                  ncams=a.ncams, bsz=a.bsz, nworkers=a.nworkers, lr=a.lr, weight_decay=a.weight_decay, logdir=a.logdir,
@@ -663,7 +706,8 @@ def main(argv=None):
                  warmup_steps=a.warmup_steps, warmup_factor=a.warmup_factor, lr_min=a.lr_min,
                  lr_total_steps=a.lr_total_steps, ema_decay=a.ema_decay, ema_warmup=bool(a.ema_warmup),
                  bev_rot_lim=parse_pair(a.bev_rot_lim, "--bev_rot_lim"),
-                 bev_scale_lim=parse_pair(a.bev_scale_lim, "--bev_scale_lim"), bev_flip=bool(a.bev_flip))
+                 bev_scale_lim=parse_pair(a.bev_scale_lim, "--bev_scale_lim"), bev_flip=bool(a.bev_flip),
+                 valid_mask=a.valid_mask, fov_z=parse_heights(a.fov_z))
 
 
 if __name__ == "__main__":

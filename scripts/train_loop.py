@@ -10,6 +10,7 @@ train_loop step): one JSON line {"frames_per_s", "steps", "nworkers", "cycle_bat
   python scripts/train_loop.py --dataroot DIR --loss focal [--focal-gamma 2.0]     the focal loss (--pos-weight its w_pos)
   python scripts/train_loop.py --dataroot DIR --bev-rot-lim=-22.5,22.5 --bev-scale-lim 0.9,1.1 --bev-flip 1
                                                                                     the BEV-space augmentation
+  python scripts/train_loop.py --dataroot DIR --valid-mask fov [--fov-z 0.0,1.5]   the valid-cell mask (none | grid | fov)
 """
 from __future__ import annotations
 
@@ -42,6 +43,8 @@ def main():
     ap.add_argument("--bev-rot-lim", default="0,0", help="trainer --bev_rot_lim")
     ap.add_argument("--bev-scale-lim", default="1,1", help="trainer --bev_scale_lim")
     ap.add_argument("--bev-flip", type=int, default=0, help="trainer --bev_flip")
+    ap.add_argument("--valid-mask", default="none", choices=["none", "grid", "fov"], help="trainer --valid_mask")
+    ap.add_argument("--fov-z", default="0.0", help="trainer --fov_z")
     a = ap.parse_args()
     from lss_carla_amd import miopen_db
     miopen_db.use_committed()  # before torch starts
@@ -62,12 +65,13 @@ def main():
                             focal_gamma=trainer.parse_per_class(a.focal_gamma, "--focal-gamma"),
                             bev_rot_lim=trainer.parse_pair(a.bev_rot_lim, "--bev-rot-lim"),
                             bev_scale_lim=trainer.parse_pair(a.bev_scale_lim, "--bev-scale-lim"),
-                            bev_flip=bool(a.bev_flip))
+                            bev_flip=bool(a.bev_flip), valid_mask=a.valid_mask,
+                            fov_z=trainer.parse_heights(a.fov_z))
     print(json.dumps({"frames_per_s": out["frames_per_s"], "steps": out["counter"], "bsz": a.bsz,
                       "nworkers": a.nworkers, "cycle_batches": a.cycle_batches, "graph": a.graph,
                       "skipped": out["skipped"], "loss": out["loss"], "label_groups": a.label_groups or None,
                       "loss_kind": a.loss, "bev_rot_lim": a.bev_rot_lim, "bev_scale_lim": a.bev_scale_lim,
-                      "bev_flip": a.bev_flip}))
+                      "bev_flip": a.bev_flip, "valid_mask": a.valid_mask, "fov_z": a.fov_z}))
 
 
 if __name__ == "__main__":

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define LSS_ABI_VERSION 32
+#define LSS_ABI_VERSION 33
 
 typedef struct lss_dims {
     int32_t B, N, D, H, W, C;
@@ -92,6 +92,18 @@ int lss_geometry_cells(const float* frustum, const float* rots, const float* tra
                        float* out_geom, int32_t* cell_of, int32_t* cell_count, int32_t* slot_of,
                        lss_stream_t stream);
 
+/* lss_geometry_cells with a camera-alive mask (ABI 33): cam_alive holds B*N bytes on the device,
+ * index b*N + n. Every point of a camera whose byte is 0 is a dropped point, exactly as an
+ * out-of-grid one: cell_of = -1, slot_of = -1, not counted. out_geom, when given, is written for
+ * every point as by lss_geometry_cells. The bytes are read by the kernel, so a captured launch
+ * follows whatever they hold at replay. With every byte non-zero the outputs are
+ * lss_geometry_cells', bit for bit. cam_alive NULL returns LSS_EINVAL. */
+int lss_geometry_cells_masked(const float* frustum, const float* rots, const float* trans,
+                              const float* kinv, const float* pinv, const float* post_trans,
+                              const lss_dims_t* dims, const lss_grid_t* grid,
+                              float* out_geom, int32_t* cell_of, int32_t* cell_count, int32_t* slot_of,
+                              lss_stream_t stream, const uint8_t* cam_alive);
+
 /* Quantise a given (Nprime, 3) fp32 geometry (voxel_pooling(geom_feats, x) boundary,
  * src/models.py:204-223). Same outputs as lss_geometry_cells; points_per_batch =
  * Nprime / B (src/models.py:214). */
@@ -151,6 +163,15 @@ int lss_geometry_cells_ordered(const float* frustum, const float* rots, const fl
                                const lss_dims_t* dims, const lss_grid_t* grid,
                                float* out_geom, int32_t* cell_of, int32_t* cell_word, int32_t* rank_of,
                                void* lists, void* workspace, lss_stream_t stream);
+/* lss_geometry_cells_ordered with a camera-alive mask (ABI 33; cam_alive as lss_geometry_cells_masked):
+ * a dead camera's points get cell_of = rank_of = -1, add nothing to cell_word and append no block
+ * record. lss_csr_build_ordered follows unchanged. */
+int lss_geometry_cells_ordered_masked(const float* frustum, const float* rots, const float* trans,
+                                      const float* kinv, const float* pinv, const float* post_trans,
+                                      const lss_dims_t* dims, const lss_grid_t* grid,
+                                      float* out_geom, int32_t* cell_of, int32_t* cell_word, int32_t* rank_of,
+                                      void* lists, void* workspace, lss_stream_t stream,
+                                      const uint8_t* cam_alive);
 int lss_cells_from_geom_ordered(const float* geom, int32_t nprime, int32_t points_per_batch,
                                 const lss_grid_t* grid, int32_t* cell_of, int32_t* cell_word,
                                 int32_t* rank_of, void* lists, void* workspace, lss_stream_t stream);

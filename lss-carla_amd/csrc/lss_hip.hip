@@ -277,6 +277,34 @@ __device__ __forceinline__ void geometry_point(const float* __restrict__ frustum
     }
 }
 
+// Camera-alive mask (ABI 33): kMasked reads cam_alive[cam] (B*N bytes) and sends the points of a camera
+// whose byte is 0 down the out-of-grid path (cell -1: no count, no record, slot / rank -1). Such a lane
+// skips the geometry unless out_geom wants it; blocks straddle cameras, so the skip is per lane and every
+// thread still reaches the block's barriers. kMasked = false is the unmasked kernel, unchanged.
+template <bool kMasked>
+__device__ __forceinline__ int geometry_cell(const float* __restrict__ frustum, const float* __restrict__ rots,
+                                             const float* __restrict__ trans, const float* __restrict__ kinv,
+                                             const float* __restrict__ pinv, const float* __restrict__ post_trans,
+                                             const uint8_t* __restrict__ cam_alive, int N, int DHW, int p, bool live,
+                                             const lss_grid_t& g, float* __restrict__ out_geom) {
+    const int cam = p / DHW;
+    const int f = p - cam * DHW;
+    const int b = cam / N;
+    bool alive = true;
+    if constexpr (kMasked) {
+        alive = cam_alive[cam] != 0;
+        if (!alive && out_geom == nullptr) return -1;
+    }
+    float e[3];
+    geometry_point(frustum, rots, trans, kinv, pinv, post_trans, cam, f, e);
+    if (out_geom != nullptr && live) {
+        out_geom[3 * (size_t)p + 0] = e[0];
+        out_geom[3 * (size_t)p + 1] = e[1];
+        out_geom[3 * (size_t)p + 2] = e[2];
+    }
+    return live && alive ? quantize_cell(e[0], e[1], e[2], g, b) : -1;
+}
+
 __global__ __launch_bounds__(kGeoBlock) void k_geometry_cells(
     const float* __restrict__ frustum, const float* __restrict__ rots, const float* __restrict__ trans,
     const float* __restrict__ kinv, const float* __restrict__ pinv, const float* __restrict__ post_trans,
@@ -285,17 +313,22 @@ __global__ __launch_bounds__(kGeoBlock) void k_geometry_cells(
     const int p0 = blockIdx.x * kGeoBlock + threadIdx.x;
     const bool live = p0 < nprime;
     const int p = live ? p0 : nprime - 1;  // dead lanes recompute the last point, then write nothing
-    const int cam = p / DHW;
-    const int f = p - cam * DHW;
-    const int b = cam / N;
-    float e[3];
-    geometry_point(frustum, rots, trans, kinv, pinv, post_trans, cam, f, e);
-    if (out_geom != nullptr && live) {
-        out_geom[3 * (size_t)p + 0] = e[0];
-        out_geom[3 * (size_t)p + 1] = e[1];
-        out_geom[3 * (size_t)p + 2] = e[2];
-    }
-    const int cell = live ? quantize_cell(e[0], e[1], e[2], g, b) : -1;
+    const int cell =
+        geometry_cell<false>(frustum, rots, trans, kinv, pinv, post_trans, nullptr, N, DHW, p, live, g, out_geom);
+    __shared__ GeoHash hash;
+    emit_cell_block(p, cell, cell_of, cell_count, slot_of, live, hash);
+}
+
+__global__ __launch_bounds__(kGeoBlock) void k_geometry_cells_masked(
+    const float* __restrict__ frustum, const float* __restrict__ rots, const float* __restrict__ trans,
+    const float* __restrict__ kinv, const float* __restrict__ pinv, const float* __restrict__ post_trans,
+    const uint8_t* __restrict__ cam_alive, int N, int DHW, int nprime, lss_grid_t g, float* __restrict__ out_geom,
+    int32_t* __restrict__ cell_of, int32_t* __restrict__ cell_count, int32_t* __restrict__ slot_of) {
+    const int p0 = blockIdx.x * kGeoBlock + threadIdx.x;
+    const bool live = p0 < nprime;
+    const int p = live ? p0 : nprime - 1;
+    const int cell =
+        geometry_cell<true>(frustum, rots, trans, kinv, pinv, post_trans, cam_alive, N, DHW, p, live, g, out_geom);
     __shared__ GeoHash hash;
     emit_cell_block(p, cell, cell_of, cell_count, slot_of, live, hash);
 }
@@ -399,17 +432,25 @@ __global__ __launch_bounds__(kGeoBlock) void k_geometry_cells_ord(
     const int p0 = lb * kGeoBlock + threadIdx.x;
     const bool live = p0 < nprime;
     const int p = live ? p0 : nprime - 1;  // dead lanes recompute the last point, then write nothing
-    const int cam = p / DHW;
-    const int f = p - cam * DHW;
-    const int b = cam / N;
-    float e[3];
-    geometry_point(frustum, rots, trans, kinv, pinv, post_trans, cam, f, e);
-    if (out_geom != nullptr && live) {
-        out_geom[3 * (size_t)p + 0] = e[0];
-        out_geom[3 * (size_t)p + 1] = e[1];
-        out_geom[3 * (size_t)p + 2] = e[2];
-    }
-    const int cell = live ? quantize_cell(e[0], e[1], e[2], g, b) : -1;
+    const int cell =
+        geometry_cell<false>(frustum, rots, trans, kinv, pinv, post_trans, nullptr, N, DHW, p, live, g, out_geom);
+    __shared__ GeoHashOrd hash;
+    emit_cell_block_ordered(lb, p, cell, cell_of, cell_word, rank_of, list, ovf, ovf_count, live, hash);
+}
+
+__global__ __launch_bounds__(kGeoBlock) void k_geometry_cells_ord_masked(
+    const float* __restrict__ frustum, const float* __restrict__ rots, const float* __restrict__ trans,
+    const float* __restrict__ kinv, const float* __restrict__ pinv, const float* __restrict__ post_trans,
+    const uint8_t* __restrict__ cam_alive, int N, int DHW, int nprime, lss_grid_t g, float* __restrict__ out_geom,
+    int32_t* __restrict__ cell_of, int32_t* __restrict__ cell_word, int32_t* __restrict__ rank_of,
+    int32_t* __restrict__ list, int2* __restrict__ ovf, unsigned* __restrict__ ovf_count) {
+    const int lb = xcd_block();
+    if (lb * kGeoBlock >= nprime) return;  // block-uniform
+    const int p0 = lb * kGeoBlock + threadIdx.x;
+    const bool live = p0 < nprime;
+    const int p = live ? p0 : nprime - 1;
+    const int cell =
+        geometry_cell<true>(frustum, rots, trans, kinv, pinv, post_trans, cam_alive, N, DHW, p, live, g, out_geom);
     __shared__ GeoHashOrd hash;
     emit_cell_block_ordered(lb, p, cell, cell_of, cell_word, rank_of, list, ovf, ovf_count, live, hash);
 }
@@ -2657,20 +2698,42 @@ const char* lss_error_string(int code) {
     return "lss: unknown error";
 }
 
-int lss_geometry_cells(const float* frustum, const float* rots, const float* trans, const float* kinv,
-                       const float* pinv, const float* post_trans, const lss_dims_t* dims, const lss_grid_t* grid,
-                       float* out_geom, int32_t* cell_of, int32_t* cell_count, int32_t* slot_of,
-                       lss_stream_t stream) {
+static int geometry_cells_launch(const float* frustum, const float* rots, const float* trans, const float* kinv,
+                                 const float* pinv, const float* post_trans, const uint8_t* cam_alive,
+                                 const lss_dims_t* dims, const lss_grid_t* grid, float* out_geom, int32_t* cell_of,
+                                 int32_t* cell_count, int32_t* slot_of, lss_stream_t stream) {
     if (!dims_ok(dims) || !grid_ok(grid) || !frustum || !rots || !trans || !kinv || !pinv || !post_trans || !cell_of)
         return LSS_EINVAL;
     if (cell_count && !slot_of) return LSS_EINVAL;
     const long DHW = (long)dims->D * dims->H * dims->W;
     const long nprime = (long)dims->B * dims->N * DHW;
     if (nprime >= INT_MAX) return LSS_EUNSUPPORTED;
-    hipLaunchKernelGGL(k_geometry_cells, dim3(grid_blocks(nprime, kGeoBlock)), dim3(kGeoBlock), 0,
-                       (hipStream_t)stream, frustum, rots, trans, kinv, pinv, post_trans, dims->N, (int)DHW,
-                       (int)nprime, *grid, out_geom, cell_of, cell_count, slot_of);
+    if (cam_alive != nullptr)
+        hipLaunchKernelGGL(k_geometry_cells_masked, dim3(grid_blocks(nprime, kGeoBlock)), dim3(kGeoBlock), 0,
+                           (hipStream_t)stream, frustum, rots, trans, kinv, pinv, post_trans, cam_alive, dims->N,
+                           (int)DHW, (int)nprime, *grid, out_geom, cell_of, cell_count, slot_of);
+    else
+        hipLaunchKernelGGL(k_geometry_cells, dim3(grid_blocks(nprime, kGeoBlock)), dim3(kGeoBlock), 0,
+                           (hipStream_t)stream, frustum, rots, trans, kinv, pinv, post_trans, dims->N, (int)DHW,
+                           (int)nprime, *grid, out_geom, cell_of, cell_count, slot_of);
     return launch_status();
+}
+
+int lss_geometry_cells(const float* frustum, const float* rots, const float* trans, const float* kinv,
+                       const float* pinv, const float* post_trans, const lss_dims_t* dims, const lss_grid_t* grid,
+                       float* out_geom, int32_t* cell_of, int32_t* cell_count, int32_t* slot_of,
+                       lss_stream_t stream) {
+    return geometry_cells_launch(frustum, rots, trans, kinv, pinv, post_trans, nullptr, dims, grid, out_geom, cell_of,
+                                 cell_count, slot_of, stream);
+}
+
+int lss_geometry_cells_masked(const float* frustum, const float* rots, const float* trans, const float* kinv,
+                              const float* pinv, const float* post_trans, const lss_dims_t* dims,
+                              const lss_grid_t* grid, float* out_geom, int32_t* cell_of, int32_t* cell_count,
+                              int32_t* slot_of, lss_stream_t stream, const uint8_t* cam_alive) {
+    if (!cam_alive) return LSS_EINVAL;
+    return geometry_cells_launch(frustum, rots, trans, kinv, pinv, post_trans, cam_alive, dims, grid, out_geom,
+                                 cell_of, cell_count, slot_of, stream);
 }
 
 int lss_cells_from_geom(const float* geom, int32_t nprime, int32_t points_per_batch, const lss_grid_t* grid,
@@ -2761,10 +2824,11 @@ size_t lss_csr_lists_bytes(int32_t ncells, int32_t nprime) {
 // points of one sample (the most a cell can hold) and blocks per sample must fit the cell word's fields
 static bool ord_fits(long ppb) { return ppb > 0 && ppb < (1L << kOrdCountBits) - 2L * kGeoBlock; }
 
-int lss_geometry_cells_ordered(const float* frustum, const float* rots, const float* trans, const float* kinv,
-                               const float* pinv, const float* post_trans, const lss_dims_t* dims,
-                               const lss_grid_t* grid, float* out_geom, int32_t* cell_of, int32_t* cell_word,
-                               int32_t* rank_of, void* lists, void* workspace, lss_stream_t stream) {
+static int geometry_cells_ordered_launch(const float* frustum, const float* rots, const float* trans,
+                                         const float* kinv, const float* pinv, const float* post_trans,
+                                         const uint8_t* cam_alive, const lss_dims_t* dims, const lss_grid_t* grid,
+                                         float* out_geom, int32_t* cell_of, int32_t* cell_word, int32_t* rank_of,
+                                         void* lists, void* workspace, lss_stream_t stream) {
     if (!dims_ok(dims) || !grid_ok(grid) || !frustum || !rots || !trans || !kinv || !pinv || !post_trans || !cell_of ||
         !cell_word || !rank_of || !lists || !workspace || (reinterpret_cast<uintptr_t>(lists) & 15))
         return LSS_EINVAL;
@@ -2774,11 +2838,35 @@ int lss_geometry_cells_ordered(const float* frustum, const float* rots, const fl
     const int ncells = grid->nx[0] * grid->nx[1] * grid->nx[2] * dims->B;
     int32_t* list = static_cast<int32_t*>(lists);
     int2* ovf = reinterpret_cast<int2*>(static_cast<char*>(lists) + ord_list_bytes(ncells));
-    hipLaunchKernelGGL(k_geometry_cells_ord, dim3(xcd_grid(grid_blocks(nprime, kGeoBlock))), dim3(kGeoBlock), 0,
-                       (hipStream_t)stream, frustum, rots, trans, kinv, pinv, post_trans, dims->N, (int)DHW,
-                       (int)nprime, *grid, out_geom, cell_of, cell_word, rank_of, list, ovf,
-                       &static_cast<ScanWs*>(workspace)->ovf_count);
+    unsigned* ovf_count = &static_cast<ScanWs*>(workspace)->ovf_count;
+    if (cam_alive != nullptr)
+        hipLaunchKernelGGL(k_geometry_cells_ord_masked, dim3(xcd_grid(grid_blocks(nprime, kGeoBlock))),
+                           dim3(kGeoBlock), 0, (hipStream_t)stream, frustum, rots, trans, kinv, pinv, post_trans,
+                           cam_alive, dims->N, (int)DHW, (int)nprime, *grid, out_geom, cell_of, cell_word, rank_of,
+                           list, ovf, ovf_count);
+    else
+        hipLaunchKernelGGL(k_geometry_cells_ord, dim3(xcd_grid(grid_blocks(nprime, kGeoBlock))), dim3(kGeoBlock), 0,
+                           (hipStream_t)stream, frustum, rots, trans, kinv, pinv, post_trans, dims->N, (int)DHW,
+                           (int)nprime, *grid, out_geom, cell_of, cell_word, rank_of, list, ovf, ovf_count);
     return launch_status();
+}
+
+int lss_geometry_cells_ordered(const float* frustum, const float* rots, const float* trans, const float* kinv,
+                               const float* pinv, const float* post_trans, const lss_dims_t* dims,
+                               const lss_grid_t* grid, float* out_geom, int32_t* cell_of, int32_t* cell_word,
+                               int32_t* rank_of, void* lists, void* workspace, lss_stream_t stream) {
+    return geometry_cells_ordered_launch(frustum, rots, trans, kinv, pinv, post_trans, nullptr, dims, grid, out_geom,
+                                         cell_of, cell_word, rank_of, lists, workspace, stream);
+}
+
+int lss_geometry_cells_ordered_masked(const float* frustum, const float* rots, const float* trans, const float* kinv,
+                                      const float* pinv, const float* post_trans, const lss_dims_t* dims,
+                                      const lss_grid_t* grid, float* out_geom, int32_t* cell_of, int32_t* cell_word,
+                                      int32_t* rank_of, void* lists, void* workspace, lss_stream_t stream,
+                                      const uint8_t* cam_alive) {
+    if (!cam_alive) return LSS_EINVAL;
+    return geometry_cells_ordered_launch(frustum, rots, trans, kinv, pinv, post_trans, cam_alive, dims, grid,
+                                         out_geom, cell_of, cell_word, rank_of, lists, workspace, stream);
 }
 
 int lss_cells_from_geom_ordered(const float* geom, int32_t nprime, int32_t points_per_batch, const lss_grid_t* grid,

@@ -23,6 +23,15 @@ Extra knobs (not in the reference, defaults reproduce it):
                      values either way; strides are not part of the reference interface
   ``static_inverses`` (pinv, kinv) device buffers staged from the host's torch.inverse before a
                      captured step (ops.HostInverses); None: computed per forward, as the reference
+  ``camera_alive``   a (B, N) uint8 device tensor, or None (default: every camera is used). The plan
+                     kernels read it (ops.plan_from_cameras(cam_alive=)): every frustum point of a camera
+                     whose byte is 0 is dropped from the splat, as an out-of-grid point is, so a captured
+                     forward follows whatever the tensor holds at replay -- a deployed graph at N = 6
+                     keeps running when a camera dies. The trunk and the fused lift still run over the
+                     dead cameras' pixels. This is NOT how training drops cameras: in train mode the dead
+                     cameras' images would still enter the trunk's batch statistics, which the reference's
+                     ``Ncams`` never feeds; training runs with only the kept cameras in its tensors
+                     (trainer.train(ncams=k))
   ``fuse_depthnet``  under bf16 autocast, run the depthnet 1x1 conv inside the lift kernel
                      (MFMA); off: the conv runs as its own op (MIOpen)
 """
@@ -775,6 +784,8 @@ class LiftSplatShoot(nn.Module):
         # (pinv, kinv) device buffers filled from host torch.inverse by ops.HostInverses before the
         # step (captured training step); None: get_voxels computes them (host torch.inverse)
         self.static_inverses = None
+        # (B, N) uint8 device tensor read by the plan kernels (0: the camera's points are dropped), or None
+        self.camera_alive = None
         self._grid = ops.GridSpec.from_conf(grid_conf)
 
     def create_frustum(self):
@@ -837,7 +848,7 @@ class LiftSplatShoot(nn.Module):
 
         def make_plan():
             return ops.plan_from_cameras(self.frustum, rots, trans, intrins, post_rots, post_trans, self._grid,
-                                         inverses=inv)
+                                         inverses=inv, cam_alive=self.camera_alive)
 
         if PLAN_AT == "trunk":
             plan = make_plan()

@@ -301,15 +301,28 @@ def _build_csr(cell_of, slot_of, counts, dims, ncells: int, dev, ws=None, ordere
 
 def plan_from_cameras(frustum: torch.Tensor, rots, trans, intrins, post_rots, post_trans, grid: GridSpec,
                       want_geom: bool = False, want_csr: bool = True,
-                      inverses: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> SplatPlan:
+                      inverses: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                      cam_alive: Optional[torch.Tensor] = None) -> SplatPlan:
     """get_geometry + quantise + filter + counting sort, all on the device (src/models.py:170-231).
 
     `inverses` = a (pinv, kinv) pair from camera_inverses / HostInverses, if already computed
     (models.py computes them before the trunk, so the host round trip never waits for device work).
+
+    `cam_alive` = a contiguous (B, N) uint8 tensor on the plan's device (lss_geometry_cells[_ordered]_masked,
+    ABI 33): every point of a camera whose byte is 0 is dropped, as an out-of-grid point is. The kernel
+    reads the bytes, so a captured plan follows what the tensor holds at replay. None launches the
+    unmasked kernels.
     """
     dev = _require_cuda(frustum, rots, trans, intrins, post_rots, post_trans)
     lib = _lib.load()
     B, N = trans.shape[:2]
+    if cam_alive is not None and not (
+            isinstance(cam_alive, torch.Tensor) and cam_alive.dtype == torch.uint8 and cam_alive.device == dev
+            and tuple(cam_alive.shape) == (B, N) and cam_alive.is_contiguous()):
+        what = (f"shape {tuple(cam_alive.shape)}, dtype {cam_alive.dtype}, device {cam_alive.device}"
+                if isinstance(cam_alive, torch.Tensor) else repr(type(cam_alive)))
+        raise RuntimeError(f"plan_from_cameras: cam_alive must be a contiguous ({B}, {N}) uint8 tensor on {dev}; "
+                           f"got {what}")
     D, H, W = frustum.shape[:3]
     nprime = B * N * D * H * W
     ncells = grid.ncells(B)
@@ -326,6 +339,19 @@ def plan_from_cameras(frustum: torch.Tensor, rots, trans, intrins, post_rots, po
     ordered = want_csr and _ordered(ws, N * D * H * W)
 
     def launch_cells():
+        if cam_alive is not None:
+            if ordered:
+                _lib.check(lib.lss_geometry_cells_ordered_masked(
+                    _lib.ptr(fr), _lib.ptr(ro), _lib.ptr(tr), _lib.ptr(kinv), _lib.ptr(pinv), _lib.ptr(pt), dims, g,
+                    _lib.ptr(geom), _lib.ptr(cell_of), _lib.ptr(counts), _lib.ptr(slot_of), _lib.ptr(ws.lists),
+                    _lib.ptr(ws.workspace), _lib.stream_handle(dev), _lib.ptr(cam_alive)),
+                    "lss_geometry_cells_ordered_masked")
+                return
+            _lib.check(lib.lss_geometry_cells_masked(
+                _lib.ptr(fr), _lib.ptr(ro), _lib.ptr(tr), _lib.ptr(kinv), _lib.ptr(pinv), _lib.ptr(pt), dims, g,
+                _lib.ptr(geom), _lib.ptr(cell_of), _lib.ptr(counts), _lib.ptr(slot_of), _lib.stream_handle(dev),
+                _lib.ptr(cam_alive)), "lss_geometry_cells_masked")
+            return
         if ordered:
             _lib.check(lib.lss_geometry_cells_ordered(
                 _lib.ptr(fr), _lib.ptr(ro), _lib.ptr(tr), _lib.ptr(kinv), _lib.ptr(pinv), _lib.ptr(pt), dims, g,

@@ -21,6 +21,18 @@ buffers, valid until the next call. A call does not synchronise the host, HostIn
 calls ahead at most) apart -- except for a rig handed over as device tensors without host copies attached
 (``t._lss_host``, as simbev.finish_batch attaches them), which is read back once: pass the rig on the host.
 
+Dead cameras. ``Predictor(..., camera_mask=True)`` captures the forward with the masked plan kernels
+(``LiftSplatShoot.camera_alive``): the Predictor owns a static (bsz, N) uint8 ``alive`` tensor, all ones, that the
+plan reads on the device, so ONE captured graph serves every pattern of dead cameras, per sample:
+
+    p = L.Predictor(model, bsz, device, camera_mask=True)
+    p.set_alive([1, 1, 0, 1, 1, 1])          # (N,) for every sample, or (b, N); bool / uint8, host or device
+    logits = p(imgs, ..., alive=mask)        # the same, per call
+
+A dead camera's frustum points are dropped from the splat, exactly as if they fell outside the grid; its images
+still pass through the trunk and the lift (eval mode has no op across images, so they change nothing else). A
+Predictor built without ``camera_mask`` captures the unmasked graph, as before, and refuses both calls.
+
 The model's parameters are moved into the Predictor's flat fp32 master (FlatParams; same values, same
 state_dict): build it on a model no training step is bound to. The hot path has no CPU fallback.
 
@@ -28,6 +40,7 @@ state_dict): build it on a model no training step is bound to. The hot path has 
                                     [--dtype bf16|fp32] [--graph 0|1] [--threshold 0.5 | 0.45,0.5,0.35]
                                     [--loss bce|focal] [--focal_gamma G] [--focal_alpha A] [--iou_thresholds 0.35,...]
                                     [--weights auto|ema|model] [--valid_mask none|grid|fov] [--fov_z 0.0[,1.5,...]]
+                                    [--drop_cams front,back_left] [--drop_each 0|1]
 
 runs the val split through ``BatchStager`` and the Predictor and writes one uint8 mask array per sample
 (``DIR/<index>.npy``, (K, X, Y)) and ``DIR/metrics.json``: loss, IoU and per-class IoU from get_val_info's
@@ -38,6 +51,11 @@ is the chosen one (``loss_kind``), the IoU keys are the 0.5 column's, and a ladd
 the masked form of that accumulate (``lss_seg_metrics_accum_masked``): loss and IoU are over valid cells (simbev.valid_mask),
 ``metrics.json`` gains ``valid_mask`` and ``valid_fraction``, and each sample's mask is written to ``DIR/valid/<index>.npy``
 ((X, Y) uint8); the written prediction masks are unchanged. The matplotlib figures of explore.py are not drawn.
+``--drop_cams`` (names of ``simbev.CAMERA_ORDER``, or indices) runs the split with those cameras dead in every sample
+(``metrics.json`` gains ``dropped_cams``). ``--drop_each 1`` runs the split once more per camera after the normal pass,
+that camera dead (besides any of --drop_cams), on the same graph, and writes ``"drop_each": {name: {"loss", "iou", ...}}``
+-- the missing-camera table; prediction masks are written for the normal pass only. With ``--valid_mask fov`` a dead
+camera makes no cell valid (simbev.fov_cameras(alive=)).
 """
 from __future__ import annotations
 
@@ -110,14 +128,16 @@ class Predictor:
     RIG = ("rots", "trans", "intrins", "post_rots", "post_trans")
 
     def __init__(self, model: torch.nn.Module, bsz: int, device, amp_dtype: Optional[torch.dtype] = torch.bfloat16,
-                 threshold=0.5, graph: bool = True, ncams: Optional[int] = None, stager=None):
+                 threshold=0.5, graph: bool = True, ncams: Optional[int] = None, stager=None,
+                 camera_mask: bool = False):
         """model: a LiftSplatShoot on `device` (memory formats as the caller set them). bsz: the static batch.
         threshold: one probability, or one per output class (a sequence of K: e.g. the
         ``best_threshold_per_class`` of a validation over a ladder; ``masks()`` then compares in fp32 with the
         K logit thresholds, the predicate ``lss_seg_metrics_accum`` counts with).
         amp_dtype: autocast dtype (None: fp32). stager: a staging.BatchStager whose static tensors and
         inverses to run on (``run(b)`` after its ``commit()``); None: buffers of the Predictor's own, filled by
-        ``__call__``. The graph is captured by the first call, on that call's inputs."""
+        ``__call__``. The graph is captured by the first call, on that call's inputs. camera_mask: run the masked
+        plan kernels over the static ``alive`` tensor (``set_alive`` / ``alive=``); False: the unmasked forward."""
         from . import ops
         from .flat_params import FlatParams
 
@@ -162,6 +182,25 @@ class Predictor:
         self.graph = None
         self._out = None
         self._b = 0
+        # (bsz, N) uint8, all ones: what the masked plan kernels read; None: the unmasked forward
+        self.alive = torch.ones(self.bsz, N, device=dev, dtype=torch.uint8) if camera_mask else None
+
+    # ------------------------------------------------------------------ dead cameras
+    def set_alive(self, mask) -> None:
+        """Which cameras the splat uses from the next run on: (N,) for every sample, or (b, N) for the first b
+        samples (the rest keep theirs); bool / uint8 / numbers (0 = dead), host or device. Copied into the static
+        ``alive`` tensor on the current stream: no recapture."""
+        if self.alive is None:
+            raise RuntimeError("Predictor: built without camera_mask=True -- its forward has no camera mask")
+        m = torch.as_tensor(mask)
+        if m.dim() not in (1, 2) or m.shape[-1] != self.ncams or (m.dim() == 2 and not 0 < m.shape[0] <= self.bsz):
+            raise ValueError(f"Predictor: an alive mask of shape {tuple(m.shape)}; ({self.ncams},) or "
+                             f"(b <= {self.bsz}, {self.ncams})")
+        m = (m != 0).to(torch.uint8)
+        if m.dim() == 1:
+            self.alive.copy_(m.to(self.device, non_blocking=True).expand_as(self.alive))
+        else:
+            self.alive[:m.shape[0]].copy_(m, non_blocking=True)
 
     # ------------------------------------------------------------------ weights
     def refresh(self) -> None:
@@ -187,8 +226,11 @@ class Predictor:
         model = self.model
         was_training = model.training
         saved_inv = model.static_inverses
+        saved_alive = getattr(model, "camera_alive", None)
         model.eval()
         model.static_inverses = (self.hinv.pinv, self.hinv.kinv)
+        if self.alive is not None:
+            model.camera_alive = self.alive
         try:
             capturing = torch.cuda.is_current_stream_capturing()
             with torch.no_grad(), torch.autocast("cuda", dtype=self.amp_dtype or torch.bfloat16,
@@ -196,6 +238,8 @@ class Predictor:
                 return torch.func.functional_call(model, self.params, self.inputs, strict=False)
         finally:
             model.static_inverses = saved_inv
+            if self.alive is not None:
+                model.camera_alive = saved_alive
             model.train(was_training)
 
     def _capture(self) -> None:
@@ -226,9 +270,11 @@ class Predictor:
         self._b = b
         return self._out[:b]
 
-    def __call__(self, imgs, rots, trans, intrins, post_rots, post_trans) -> torch.Tensor:
+    def __call__(self, imgs, rots, trans, intrins, post_rots, post_trans, alive=None) -> torch.Tensor:
         if self.stager is not None:
             raise RuntimeError("Predictor: built on a stager -- stage / commit there, then run(b)")
+        if alive is not None and self.alive is None:
+            raise RuntimeError("Predictor: built without camera_mask=True -- its forward has no camera mask")
         b = int(imgs.shape[0])
         if not 0 < b <= self.bsz:
             raise ValueError(f"Predictor: a batch of {b} samples against bsz={self.bsz}")
@@ -239,6 +285,8 @@ class Predictor:
         self._host_post_rots[:b].copy_(_host(post_rots))
         self._host_intrins[:b].copy_(_host(intrins))
         self.hinv.update(self._host_post_rots, self._host_intrins)
+        if alive is not None:
+            self.set_alive(alive)
         return self.run(b)
 
     # ------------------------------------------------------------------ outputs of the last call
@@ -282,6 +330,31 @@ def threshold_arg(text):
     return vals[0] if len(vals) == 1 else vals
 
 
+def parse_drop_cams(text) -> list:
+    """``--drop_cams front,back_left`` (names of simbev.CAMERA_ORDER) or ``--drop_cams 1,3`` (indices) -> the sorted
+    distinct camera indices; None or empty: []. ValueError for an unknown name or an index out of range."""
+    from .simbev import CAMERA_ORDER
+    if text is None:
+        return []
+    items = [v.strip() for v in text.split(",")] if isinstance(text, str) else [v for v in text]
+    out = set()
+    for v in items:
+        if isinstance(v, str) and not v:
+            continue
+        if isinstance(v, str) and v in CAMERA_ORDER:
+            out.add(CAMERA_ORDER.index(v))
+            continue
+        try:
+            i = int(v)
+        except (TypeError, ValueError):
+            i = -1
+        if isinstance(v, bool) or not 0 <= i < len(CAMERA_ORDER):
+            raise ValueError(f"--drop_cams {text!r}: {v!r} is neither one of {', '.join(CAMERA_ORDER)} nor an index "
+                             f"0..{len(CAMERA_ORDER) - 1}")
+        out.add(i)
+    return sorted(out)
+
+
 def parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="python -m lss_carla_amd.predict",
                                 description="Run a trained LSS over a SimBEV val split on the MI355X: masks and metrics")
@@ -309,6 +382,10 @@ def parser() -> argparse.ArgumentParser:
                    help="count only valid cells in loss and IoU (fov: cells some camera sees); also writes DIR/valid/")
     p.add_argument("--fov_z", type=str, default="0.0",
                    help="--valid_mask fov: the heights (metres) a cell is tested at, 1 to 8: 0.0[,1.5,...]")
+    p.add_argument("--drop_cams", type=str, default=None,
+                   help="cameras dead in every sample, names or indices: front,back_left")
+    p.add_argument("--drop_each", type=int, default=0, choices=[0, 1],
+                   help="1: after the normal pass, the split once more per camera with that camera dead (same graph)")
     p.add_argument("--gpuid", type=int, default=0)
     p.add_argument("--nworkers", type=int, default=4)
     p.add_argument("--H", type=int, default=224)
@@ -332,6 +409,7 @@ def confs(a) -> tuple:
 def predict(a, grid_conf=None, data_aug_conf=None, model: Optional[torch.nn.Module] = None) -> dict:
     """The command line's work for parsed arguments `a`; returns metrics.json's dict. grid_conf / data_aug_conf
     override the defaults of ``confs``; model: an already built (and loaded) module instead of --modelf."""
+    dropped = parse_drop_cams(getattr(a, "drop_cams", None))  # (a bad name fails before anything else)
     if a.gpuid < 0:
         raise RuntimeError("lss_carla_amd.predict: needs an MI355X (the hot path has no CPU fallback)")
     dev = _require_gpu(f"cuda:{a.gpuid}")
@@ -364,6 +442,8 @@ def predict(a, grid_conf=None, data_aug_conf=None, model: Optional[torch.nn.Modu
     mask_mode = simbev.valid_mask_mode({"valid_mask": getattr(a, "valid_mask", None),
                                         "fov_z": parse_heights(getattr(a, "fov_z", "0.0"))})
     fov_z = parse_heights(getattr(a, "fov_z", "0.0"))
+    drop_each = bool(getattr(a, "drop_each", 0))
+    use_mask = bool(dropped) or drop_each
     amp_dtype = torch.bfloat16 if a.dtype == "bf16" else None
     if model is None:
         sd = model_state_dict(torch.load(a.modelf, map_location="cpu"), getattr(a, "weights", "auto"))
@@ -378,7 +458,8 @@ def predict(a, grid_conf=None, data_aug_conf=None, model: Optional[torch.nn.Modu
     stager = BatchStager(data_aug_conf["final_dim"], a.bsz, len(simbev.CAMERA_ORDER),
                          (data_aug_conf["H"], data_aug_conf["W"]), grid_conf, dev, label_groups=groups,
                          **({} if mask_mode is None else {"valid_mask": mask_mode, "fov_z": fov_z}))
-    p = Predictor(model, a.bsz, dev, amp_dtype=amp_dtype, threshold=threshold, graph=bool(a.graph), stager=stager)
+    p = Predictor(model, a.bsz, dev, amp_dtype=amp_dtype, threshold=threshold, graph=bool(a.graph), stager=stager,
+                  **({"camera_mask": True} if use_mask else {}))
     if K > 1 or not tools.is_scalar_weight(pos_weight):
         pos_weight = tools.class_weights(pos_weight, K, dev)
     totals = torch.zeros(1 + 2 * K, device=dev, dtype=torch.float64)
@@ -396,34 +477,76 @@ def predict(a, grid_conf=None, data_aug_conf=None, model: Optional[torch.nn.Modu
             params = torch.stack([w, torch.ones_like(w), torch.zeros_like(w)], dim=1).contiguous()
         totals = torch.zeros(1 + K + 2 * K * len(columns), device=dev, dtype=torch.float64)
     os.makedirs(a.out, exist_ok=True)
-    masks, valids, frames = [], [], 0
-    it = iter(val_raw)
-    nxt = next(it, None)
-    if nxt is not None:
-        stager.stage(nxt)
-    torch.cuda.synchronize(dev)
-    t0 = None
-    while nxt is not None:
-        b = stager.commit()
-        logits = p.run(b)  # (the first call captures the graph: timed from the second batch on)
-        if ladder_mode:
-            tools.seg_metrics_accumulate(p._out, stager.binimgs, totals, stager.n_valid, params, thetas,
-                                         valid=stager.valid, valid_cells=valid_cells)
-        else:
-            tools.val_accumulate(p._out, stager.binimgs, totals, n_valid=stager.n_valid, pos_weight=pos_weight)
-        masks.append(p.masks())  # a fresh tensor per batch; the logits are static
-        if mask_mode is not None:
-            valids.append(stager.valid[:b].clone())
+    n_cams = len(simbev.CAMERA_ORDER)
+
+    def run_split(dead, keep_masks):
+        """One pass over the split with the cameras `dead` dead in every sample: (masks, valids, frames, seconds);
+        the totals (and valid_cells) are zeroed first and hold the pass's sums afterwards."""
+        totals.zero_()
+        if valid_cells is not None:
+            valid_cells.zero_()
+        if use_mask:
+            on = [0 if c in dead else 1 for c in range(n_cams)]
+            p.set_alive(on)
+            stager.cam_alive = torch.tensor(on, dtype=torch.uint8)  # --valid_mask fov: a dead camera sees no cell
+        masks, valids, frames = [], [], 0
+        it = iter(val_raw)
         nxt = next(it, None)
         if nxt is not None:
             stager.stage(nxt)
-        if t0 is None:
-            torch.cuda.synchronize(dev)
-            t0 = time.perf_counter()
+        torch.cuda.synchronize(dev)
+        t0 = None
+        while nxt is not None:
+            b = stager.commit()
+            p.run(b)  # (the first call captures the graph: timed from the second batch on)
+            if ladder_mode:
+                tools.seg_metrics_accumulate(p._out, stager.binimgs, totals, stager.n_valid, params, thetas,
+                                             valid=stager.valid, valid_cells=valid_cells)
+            else:
+                tools.val_accumulate(p._out, stager.binimgs, totals, n_valid=stager.n_valid, pos_weight=pos_weight)
+            if keep_masks:
+                masks.append(p.masks())  # a fresh tensor per batch; the logits are static
+                if mask_mode is not None:
+                    valids.append(stager.valid[:b].clone())
+            nxt = next(it, None)
+            if nxt is not None:
+                stager.stage(nxt)
+            if t0 is None:
+                torch.cuda.synchronize(dev)
+                t0 = time.perf_counter()
+            else:
+                frames += b
+        torch.cuda.synchronize(dev)
+        return masks, valids, frames, (time.perf_counter() - t0 if t0 is not None else 0.0)
+
+    def summary(t):
+        """loss, the IoU keys and the ladder's keys out of a pass's totals (a list)."""
+        extra = {}
+        if ladder_mode:
+            P, TP, PP = tools.seg_metrics_counts(t, K, len(columns))
+            c = columns.index(0.5)
+            inter, union = [TP[k][c] for k in range(K)], [PP[k][c] + P[k] - TP[k][c] for k in range(K)]
+            if ladder is not None:
+                cols = [columns.index(v) for v in ladder]
+                sub = (t[:1 + K] + [TP[k][j] for k in range(K) for j in cols]
+                       + [PP[k][j] for k in range(K) for j in cols])
+                extra = {k: v for k, v in tools.seg_metrics_summary(sub, K, ladder, n_val).items() if k != "loss"}
+                extra["iou_thresholds"] = ladder
         else:
-            frames += b
-    torch.cuda.synchronize(dev)
-    elapsed = time.perf_counter() - t0 if t0 is not None else 0.0
+            inter, union = t[1:1 + K], t[1 + K:1 + 2 * K]
+        out = {"loss": t[0] / n_val, **tools.iou_summary(inter, union), **extra, "intersection": inter, "union": union}
+        if mask_mode is not None:
+            cells = stager.valid.numel() // stager.valid.shape[0]
+            out["valid_fraction"] = float(valid_cells.item()) / (n_val * cells) if n_val else None
+        return out
+
+    masks, valids, frames, elapsed = run_split(set(dropped), True)
+    main_info = summary(totals.tolist())
+    each = {}
+    if drop_each:
+        for c, name in enumerate(simbev.CAMERA_ORDER):
+            run_split(set(dropped) | {c}, False)
+            each[name] = summary(totals.tolist())
     index = 0
     for m in masks:
         for s in m.cpu().numpy():
@@ -436,27 +559,18 @@ def predict(a, grid_conf=None, data_aug_conf=None, model: Optional[torch.nn.Modu
             for s in m.cpu().numpy():
                 np.save(os.path.join(a.out, "valid", f"{vi}.npy"), s)
                 vi += 1
-    t = totals.tolist()
-    extra = {}
-    if ladder_mode:
-        P, TP, PP = tools.seg_metrics_counts(t, K, len(columns))
-        c = columns.index(0.5)
-        inter, union = [TP[k][c] for k in range(K)], [PP[k][c] + P[k] - TP[k][c] for k in range(K)]
-        if ladder is not None:
-            cols = [columns.index(v) for v in ladder]
-            sub = t[:1 + K] + [TP[k][j] for k in range(K) for j in cols] + [PP[k][j] for k in range(K) for j in cols]
-            extra = {k: v for k, v in tools.seg_metrics_summary(sub, K, ladder, n_val).items() if k != "loss"}
-            extra["iou_thresholds"] = ladder
-    else:
-        inter, union = t[1:1 + K], t[1 + K:1 + 2 * K]
-    info = {"loss": t[0] / n_val, **tools.iou_summary(inter, union), **extra, "loss_kind": loss_kind,
+    valid_fraction = main_info.pop("valid_fraction", None)
+    inter, union = main_info.pop("intersection"), main_info.pop("union")
+    info = {**main_info, "loss_kind": loss_kind,
             "threshold": threshold, "intersection": inter, "union": union, "samples": index, "classes": K,
             "dtype": a.dtype, "graph": bool(a.graph), "bsz": a.bsz,
             "frames_per_s": frames / elapsed if frames and elapsed > 0 else None}
     if mask_mode is not None:
-        cells = stager.valid.numel() // stager.valid.shape[0]
-        info.update({"valid_mask": mask_mode, "fov_z": list(fov_z),
-                     "valid_fraction": float(valid_cells.item()) / (n_val * cells) if n_val else None})
+        info.update({"valid_mask": mask_mode, "fov_z": list(fov_z), "valid_fraction": valid_fraction})
+    if use_mask:
+        info["dropped_cams"] = [simbev.CAMERA_ORDER[c] for c in dropped]
+    if drop_each:
+        info["drop_each"] = each
     with open(os.path.join(a.out, "metrics.json"), "w") as f:
         json.dump(info, f, indent=1)
     return info

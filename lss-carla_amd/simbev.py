@@ -434,21 +434,29 @@ def fov_heights(conf: dict) -> Tuple[float, ...]:
     return z
 
 
-def fov_cameras(rots, trans, intrins, post_rots, post_trans=None) -> torch.Tensor:
+def fov_cameras(rots, trans, intrins, post_rots, post_trans=None, alive=None) -> torch.Tensor:
     """The (..., N, 16) fp32 camera blocks ``lss_simbev_valid_mask`` projects cell centres with, from the host rig
     (rots (..., N, 3, 3), trans (..., N, 3), intrins, post_rots): per camera M = intrins rots^-1 (9, row-major),
     o = -M trans (3) and P = post_rots[:2, :2] (4) -- get_geometry (src/models.py:170-192) inverted: an ego point p
     is the camera point M p + o = (u' d, v' d, d), and its pixel is P (u', v') + post_trans[:2]. Computed in
     float64, rounded once. A rig composed with the BEV-space augmentation needs nothing more:
     (A rots)^-1 (A p - A t) is the original camera point. post_trans is not used (valid_mask takes it beside the
-    blocks); it is accepted so that a batch's five rig tensors can be passed as they come."""
+    blocks); it is accepted so that a batch's five rig tensors can be passed as they come. alive: a (..., N) or (N,)
+    mask (bool / uint8 / numbers, 0 = dead): a dead camera's 16 floats are all zero, and a zero block sees nothing --
+    every cell projects to depth d = 0, which ``lss_simbev_valid_mask`` (d >= d_lo > 0) rejects."""
     r, t = torch.as_tensor(rots).detach().cpu().double(), torch.as_tensor(trans).detach().cpu().double()
     k, p = torch.as_tensor(intrins).detach().cpu().double(), torch.as_tensor(post_rots).detach().cpu().double()
     M = k.matmul(torch.linalg.inv(r))
     o = -M.matmul(t.unsqueeze(-1)).squeeze(-1)
     P = p[..., :2, :2]
     lead = M.shape[:-2]
-    return torch.cat([M.reshape(*lead, 9), o, P.reshape(*lead, 4)], dim=-1).to(torch.float32).contiguous()
+    cams = torch.cat([M.reshape(*lead, 9), o, P.reshape(*lead, 4)], dim=-1).to(torch.float32)
+    if alive is not None:
+        on = torch.as_tensor(alive).detach().cpu() != 0
+        if on.dim() < 1 or on.shape[-1] != cams.shape[-2]:
+            raise ValueError(f"fov_cameras: alive {tuple(on.shape)} for {cams.shape[-2]} cameras")
+        cams = torch.where(on.expand(lead).unsqueeze(-1), cams, torch.zeros((), dtype=torch.float32))
+    return cams.contiguous()
 
 
 def valid_mask(cams, post_trans, grid_conf, final_dim, heights=(0.0,), index_mats=None, mode="fov", out=None,

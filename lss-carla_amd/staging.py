@@ -67,7 +67,10 @@ class BatchStager:
         valid-cell mask of the committed batch (all ones before the first), filled on the staging stream by
         ``lss_simbev_valid_mask`` from the batch's host rig (camera blocks built in float64, uploaded pinned on that
         stream and held until the slot's event) at the heights fov_z; dbound overrides the grid's frustum bounds.
-        Training and validation batches are masked alike; without index matrices every cell is in the grid."""
+        Training and validation batches are masked alike; without index matrices every cell is in the grid. With
+        "fov" the mask comes from the cameras the batch actually holds: a stager of N < 6 cameras (training on a camera
+        subset) marks a cell only a dropped camera would see invalid in that sample. ``cam_alive`` (an attribute, None
+        or an (N,) / (B, N) host mask) further blanks dead cameras' blocks (simbev.fov_cameras(alive=))."""
         dev = torch.device(device)
         if dev.type != "cuda":
             raise RuntimeError("BatchStager: the static tensors live on the MI355X (no CPU fallback)")
@@ -93,6 +96,7 @@ class BatchStager:
         self.grid = dict(grid) if dbound is None else {**grid, "dbound": list(dbound)}
         self.valid = None if valid_mask is None else torch.ones(B, X, Y, device=dev, dtype=torch.uint8)
         self.n_valid = torch.full((1,), B, device=dev, dtype=torch.int32)
+        self.cam_alive = None  # host mask of the cameras "fov" may count: (N,) or (B, N); None: every camera
         self.hinv = ops.HostInverses(B * N, dev)
         # the host rig HostInverses inverts: samples past a partial batch keep their previous matrices
         self._host_post_rots = torch.eye(3).repeat(B, N, 1, 1)
@@ -145,7 +149,10 @@ class BatchStager:
         keep = [raw_batch]  # the copies below read the batch's host memory
         cams = None
         if self.valid_mask == "fov":  # the camera blocks of the batch's (composed) rig: host float64, rounded once
-            cams = simbev.fov_cameras(rots, trans, intrins, post_rots)
+            alive = self.cam_alive
+            if alive is not None and torch.as_tensor(alive).dim() == 2:
+                alive = torch.as_tensor(alive)[:b]
+            cams = simbev.fov_cameras(rots, trans, intrins, post_rots, alive=alive)
         st = self.stream
         if slot.consumed is not None:
             st.wait_event(slot.consumed)  # commit's copies out of this slot come first

@@ -33,6 +33,19 @@ import torch
 import torch.distributed as dist
 
 
+def _with_inverses(model, inverses, forward, inputs):
+    """forward(*inputs) with `inverses` installed as model.static_inverses (None: nothing is touched), the
+    previous value restored afterwards, as predict.Predictor._forward does."""
+    if inverses is None:
+        return forward(*inputs)
+    saved = model.static_inverses
+    model.static_inverses = inverses
+    try:
+        return forward(*inputs)
+    finally:
+        model.static_inverses = saved
+
+
 class TrainStep:
     """forward(*inputs) -> preds; params: what the optimizer updates (e.g. [FlatParams.master]);
     all_reduce: average params' gradients over the process group here (False under DDP)."""
@@ -43,7 +56,8 @@ class TrainStep:
                  max_grad_norm: float = 5.0, pre_step: Optional[Callable[[], None]] = None,
                  overlap_all_reduce: bool = False, force_collectives: bool = False,
                  skip_nonfinite: bool = False, keep_preds: bool = False, lr_schedule=None, ema=None,
-                 ema_decay: float = 0.999, ema_warmup: bool = True, valid: Optional[torch.Tensor] = None):
+                 ema_decay: float = 0.999, ema_warmup: bool = True, valid: Optional[torch.Tensor] = None,
+                 inverses=None, model: Optional[torch.nn.Module] = None):
         """overlap_all_reduce: all-reduce each parameter's gradient (e.g. each FlatParamGroups
         master) from its post-accumulate hook, on a side stream, while the backward continues -- inside
         the captured graph too; the step waits for them before the update. force_collectives: issue
@@ -58,9 +72,15 @@ class TrainStep:
         Either needs the HIP update, as skip_nonfinite does. valid: the static (B, X, Y) uint8 valid-cell mask (e.g.
         ``BatchStager.valid``): the step then calls ``loss_fn(preds, labels, valid)`` -- tools.SimpleLoss / FocalLoss
         average over the valid cells only. The step stays captured: the mask is read on the device and so is the count
-        of valid elements."""
+        of valid elements. inverses: a (pinv, kinv) pair of static device buffers (ops.HostInverses) installed as
+        ``model.static_inverses`` around this step's forward and restored afterwards (it needs ``model``) -- a step
+        whose inputs have another camera count than the module's other steps brings its own; None: the module's
+        attribute as it stands."""
         self.forward, self.inputs, self.labels = forward, tuple(inputs), labels
         self.valid = valid
+        if inverses is not None and model is None:
+            raise ValueError("TrainStep(inverses=...) needs model=: the module whose static_inverses it installs")
+        self.inverses, self.model = (None if inverses is None else tuple(inverses)), model
         # host work staged into the step's static device inputs before each step is launched
         # (e.g. ops.HostInverses.update: the reference's host torch.inverse of the rig)
         self.pre_step = pre_step
@@ -101,7 +121,7 @@ class TrainStep:
         capturing = dev_type == "cuda" and torch.cuda.is_current_stream_capturing()
         with torch.autocast(dev_type, dtype=self.amp_dtype or torch.bfloat16, enabled=self.amp_dtype is not None,
                             cache_enabled=not capturing):
-            preds = self.forward(*self.inputs)
+            preds = _with_inverses(self.model, self.inverses, self.forward, self.inputs)
         if self.keep_preds:
             self.static_preds = preds.detach()
         # (a loss that computes in fp32 itself, tools.SimpleLoss, takes the bf16 logits: no cast kernels)
@@ -229,7 +249,7 @@ class EvalStep:
     def __init__(self, model: torch.nn.Module, forward: Callable[..., torch.Tensor], inputs: Sequence[torch.Tensor],
                  labels: torch.Tensor, n_valid: Optional[torch.Tensor] = None, pos_weight=2.13,
                  amp_dtype: Optional[torch.dtype] = torch.bfloat16, n_samples: Optional[int] = None,
-                 loss=None, thresholds=None, valid: Optional[torch.Tensor] = None):
+                 loss=None, thresholds=None, valid: Optional[torch.Tensor] = None, inverses=None):
         """loss: a tools.FocalLoss whose term the loss total sums (its ``focal_params`` buffer is read on the device;
         None: SimpleLoss(pos_weight)). thresholds: a ladder of probability thresholds to count the IoU at. With
         either, the step accumulates through ``tools.seg_metrics_accumulate`` (``lss_seg_metrics_accum``) at the
@@ -238,8 +258,9 @@ class EvalStep:
         valid: the static (B, X, Y) uint8 valid-cell mask (e.g. ``BatchStager.valid``): the step always accumulates
         through the seg-metrics path (the 0.5 column present), masked -- ``lss_seg_metrics_accum_masked`` -- so the loss
         and every IoU are over valid cells, and ``read()`` adds ``valid_fraction``: valid cells / cells, over the
-        samples counted."""
+        samples counted. inverses: as TrainStep's -- installed as ``model.static_inverses`` around the forward."""
         self.model, self.forward, self.inputs, self.labels = model, forward, tuple(inputs), labels
+        self.inverses = None if inverses is None else tuple(inverses)
         self.n_samples = n_samples  # len(valloader.dataset): what read() divides the loss total by
         self.n_valid, self.amp_dtype = n_valid, amp_dtype
         # K = labels.shape[1] classes: 1 + 2 K totals (loss, K intersections, K unions) and, for K > 1 or a
@@ -288,7 +309,7 @@ class EvalStep:
             with torch.no_grad():
                 with torch.autocast(dev_type, dtype=self.amp_dtype or torch.bfloat16,
                                     enabled=self.amp_dtype is not None, cache_enabled=not capturing):
-                    preds = self.forward(*self.inputs)
+                    preds = _with_inverses(self.model, self.inverses, self.forward, self.inputs)
                 self.static_preds = preds
                 if self.columns is None:
                     tools.val_accumulate(preds, self.labels, self.totals, n_valid=self.n_valid,

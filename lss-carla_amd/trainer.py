@@ -19,9 +19,15 @@ tensorboardX / wandb. ``graph=False`` runs the same loop eagerly on the same sta
     python -m lss_carla_amd.trainer --dataroot /data/simbev --bsz 8 --final_h 128 --final_w 352
 
 Differences from the reference, all deliberate: the matplotlib figures are not drawn; the first
-validation always writes ``model_best.pt`` (the reference skips it while the IoU is 0); every camera is
-used (``ncams=6``: validation uses all six and a captured step has one static shape); a step whose
+validation always writes ``model_best.pt`` (the reference skips it while the IoU is 0); a step whose
 bf16 gradient is not finite is skipped and counted instead of poisoning the weights (``skip_nonfinite``).
+
+``ncams=k`` (1 <= k <= 6) is the reference's ``Ncams``: every training sample holds k cameras drawn at random
+(sorted, ``simbev.SimBEVDataset.choose_cams``; only their k JPEGs are decoded) and validation uses all six. The
+training step then runs over a stager of N = k cameras and the validation step over a second one of N = 6, each
+with its own static tensors, labels, valid mask and host-inverted rig -- two captured shapes, one set of weights.
+The dropped cameras are absent from the tensors, not masked: their images never reach the trunk's batch
+statistics, as in the reference (``LiftSplatShoot.camera_alive`` is the inference-time mask).
 """
 from __future__ import annotations
 
@@ -213,10 +219,19 @@ def _class_setup(label_groups, pos_weight):
     return groups, K, pos_weight
 
 
+def _check_ncams(ncams) -> int:
+    """The reference's ``Ncams``: an integer from 1 to the rig's six cameras, else ValueError."""
+    from . import simbev
+    n_all = len(simbev.CAMERA_ORDER)
+    if isinstance(ncams, bool) or not isinstance(ncams, (int, np.integer)) or not 1 <= int(ncams) <= n_all:
+        raise ValueError(f"ncams {ncams!r}: an integer from 1 to {n_all}")
+    return int(ncams)
+
+
 def build_step(grid_conf, data_aug_conf, bsz, device, *, dtype="bf16", lr=1e-3, weight_decay=1e-7,
                max_grad_norm=5.0, pos_weight=2.13, skip_nonfinite=True, n_val=None, label_groups=None,
                loss="bce", focal_gamma=2.0, focal_alpha=None, iou_thresholds=None, lr_schedule=None,
-               ema_decay=0.0, ema_warmup=True) -> dict:
+               ema_decay=0.0, ema_warmup=True, ncams=6) -> dict:
     """The model and its steps as bench.py's train branch builds them -- unused parameters frozen, one flat
     fp32 master per backward group, fused capturable Adam, TrainStep without a pre_step (the stager's
     commit stages the inverses) -- plus the stager and the EvalStep over the same static tensors. Nothing is
@@ -230,13 +245,19 @@ def build_step(grid_conf, data_aug_conf, bsz, device, *, dtype="bf16", lr=1e-3, 
     A data_aug_conf that asks for the BEV-space augmentation (simbev.bev_aug_enabled) makes the stager expect the
     label index matrices in its raw batches, as ``compile_data``'s loaders of the same conf provide them. One that
     asks for a valid-cell mask (simbev.valid_mask_mode: ``valid_mask`` "grid" / "fov", heights ``fov_z``) makes the
-    stager keep the mask, the TrainStep average its loss over valid cells and the EvalStep count valid cells only."""
+    stager keep the mask, the TrainStep average its loss over valid cells and the EvalStep count valid cells only.
+    ncams: the cameras of a training batch (1..6). Below 6, the TrainStep runs over a training stager of N = ncams
+    and the EvalStep over a second stager of N = 6 (``"val_stager"``), each step with its own labels, ``n_valid``, valid
+    mask and HostInverses, which it installs as ``model.static_inverses`` around its own forward. With "fov" each
+    stager's mask comes from the cameras its batch holds: a cell only a dropped camera would see is invalid in that
+    training sample. At 6, ``"val_stager"`` is ``"stager"`` and nothing is allocated or launched differently."""
     import lss_carla_amd as L
     from . import parallel, simbev, tools
     from .flat_params import FlatParamGroups, lss_backward_groups
     from .staging import BatchStager
     from .train_step import EvalStep, TrainStep
 
+    ncams, n_all = _check_ncams(ncams), len(simbev.CAMERA_ORDER)  # (before anything is built)
     amp_dtype = torch.bfloat16 if dtype == "bf16" else None
     label_groups, outC, pos_weight = _class_setup(label_groups, pos_weight)
     model = L.compile_model(grid_conf, data_aug_conf, outC=outC).to(device)
@@ -249,10 +270,18 @@ def build_step(grid_conf, data_aug_conf, bsz, device, *, dtype="bf16", lr=1e-3, 
     opt = torch.optim.Adam(masters, lr=lr, weight_decay=weight_decay, fused=True, capturable=True)
     mask_mode = simbev.valid_mask_mode(data_aug_conf)
     mask_args = {} if mask_mode is None else {"valid_mask": mask_mode, "fov_z": simbev.fov_heights(data_aug_conf)}
-    stager = BatchStager(data_aug_conf["final_dim"], bsz, len(simbev.CAMERA_ORDER),
+    stager = BatchStager(data_aug_conf["final_dim"], bsz, ncams,
                          (data_aug_conf["H"], data_aug_conf["W"]), grid_conf, device, label_groups=label_groups,
                          bev_aug=simbev.bev_aug_enabled(data_aug_conf), **mask_args)
     step_mask = {} if mask_mode is None else {"valid": stager.valid}
+    val_stager, val_mask, step_inv, val_inv = stager, step_mask, {}, {}
+    if ncams < n_all:  # validation at every camera: static tensors of its own
+        val_stager = BatchStager(data_aug_conf["final_dim"], bsz, n_all, (data_aug_conf["H"], data_aug_conf["W"]),
+                                 grid_conf, device, label_groups=label_groups,
+                                 bev_aug=simbev.bev_aug_enabled(data_aug_conf), **mask_args)
+        val_mask = {} if mask_mode is None else {"valid": val_stager.valid}
+        step_inv = {"inverses": (stager.hinv.pinv, stager.hinv.kinv), "model": model}
+        val_inv = {"inverses": (val_stager.hinv.pinv, val_stager.hinv.kinv)}
     model.static_inverses = (stager.hinv.pinv, stager.hinv.kinv)  # staged by the stager's commit
     if loss not in ("bce", "focal"):
         raise ValueError(f"loss {loss!r}: bce or focal")
@@ -269,11 +298,12 @@ def build_step(grid_conf, data_aug_conf, bsz, device, *, dtype="bf16", lr=1e-3, 
                      amp_dtype=amp_dtype, max_grad_norm=max_grad_norm, pre_step=None,
                      skip_nonfinite=bool(skip_nonfinite), keep_preds=True, lr_schedule=lr_schedule, ema=emas,
                      ema_decay=float(ema_decay) if emas is not None else 0.999, ema_warmup=bool(ema_warmup),
-                     **step_mask)
-    evaluate = EvalStep(model, forward_eval, stager.inputs, stager.binimgs, n_valid=stager.n_valid,
+                     **step_mask, **step_inv)
+    evaluate = EvalStep(model, forward_eval, val_stager.inputs, val_stager.binimgs, n_valid=val_stager.n_valid,
                         pos_weight=pos_weight, amp_dtype=amp_dtype, n_samples=n_val,
-                        loss=loss_fn if loss == "focal" else None, thresholds=iou_thresholds, **step_mask)
-    return {"model": model, "flat": flat, "masters": masters, "opt": opt, "stager": stager, "step": step,
+                        loss=loss_fn if loss == "focal" else None, thresholds=iou_thresholds, **val_mask, **val_inv)
+    return {"model": model, "flat": flat, "masters": masters, "opt": opt, "stager": stager, "val_stager": val_stager,
+            "step": step,
             "evaluate": evaluate, "loss_fn": loss_fn, "forward": forward, "label_groups": label_groups,
             "emas": emas, "forward_eval": forward_eval}
 
@@ -375,9 +405,14 @@ def train(
     the staging stream (simbev.valid_mask), for validation batches too; the step stays captured. The ``config`` event
     then carries ``valid_mask`` and ``fov_z``, ``val`` events gain ``valid_fraction``, and the training IoU counts
     valid cells. Off, nothing differs. Argument errors raise ValueError before anything is looked for or built.
+    ncams: 1 to 6 cameras per training sample, drawn at random per sample (the reference's ``Ncams``; see the module
+    docstring); validation always runs at six. With valid_mask "fov" a training sample's mask comes from the cameras
+    it holds, so a cell only a dropped camera would see is invalid in that sample. Checkpoints do not depend on it: a
+    run resumes at any ncams.
     Returns a summary dict (counter, epoch, best_val_iou, skipped, frames_per_s of the training steps)."""
     from . import checkpoint, simbev, tools
 
+    ncams = _check_ncams(ncams)
     pos_weight, focal = _loss_setup(loss, pos_weight, focal_gamma, focal_alpha)
     iou_thresholds = parse_thresholds(iou_thresholds)
     label_groups, n_out, pos_weight = _class_setup(label_groups, pos_weight)
@@ -392,8 +427,6 @@ def train(
     mask_mode = simbev.valid_mask_mode(mask_conf)
     if gpuid < 0 or not torch.cuda.is_available():
         raise RuntimeError("lss_carla_amd.trainer: needs an MI355X (the hot path has no CPU fallback)")
-    if ncams != len(simbev.CAMERA_ORDER):
-        raise NotImplementedError("ncams must be 6: validation uses every camera and the step's shape is static")
     if dtype not in ("bf16", "fp32"):
         raise ValueError(f"dtype {dtype!r}: bf16 or fp32")
     if resume is not None and os.path.exists(resume):
@@ -462,10 +495,11 @@ def train(
                      max_grad_norm=max_grad_norm, pos_weight=pos_weight, skip_nonfinite=skip_nonfinite,
                      n_val=n_val, label_groups=label_groups, loss=loss, focal_gamma=focal_gamma,
                      focal_alpha=focal_alpha, iou_thresholds=iou_thresholds, lr_schedule=schedule,
-                     ema_decay=float(ema_decay), ema_warmup=ema_warmup)
+                     ema_decay=float(ema_decay), ema_warmup=ema_warmup, ncams=ncams)
     emas = ctx["emas"]
     model, flat, masters, opt = ctx["model"], ctx["flat"], ctx["masters"], ctx["opt"]
     stager, step, evaluate = ctx["stager"], ctx["step"], ctx["evaluate"]
+    val_stager = ctx["val_stager"]  # the stager itself at ncams = 6
 
     counter, start_epoch = 0, 0
     if resume is not None and os.path.exists(resume):
@@ -496,12 +530,13 @@ def train(
         checkpoint.save_checkpoint(path, model, flat, opt, counter, epoch, val_iou)
 
     def validate():
-        """EvalStep over the val loader through the stager (no training batch is staged meanwhile)."""
+        """EvalStep over the val loader through the validation stager (at ncams = 6 the training stager: no
+        training batch is staged meanwhile)."""
         it = iter(val_raw)
-        stager.stage(next(it))
+        val_stager.stage(next(it))
         first = True
         for _ in range(len(val_raw)):
-            stager.commit()
+            val_stager.commit()
             if first and graph and not evaluate.captured:
                 evaluate.capture(warmup=1, error_mode="thread_local")  # on the first validation batch; resets the totals
             if first:
@@ -510,7 +545,7 @@ def train(
             evaluate()
             nxt = next(it, None)
             if nxt is not None:
-                stager.stage(nxt)
+                val_stager.stage(nxt)
         return evaluate.read()
 
     best_val_iou = -1.0
@@ -537,7 +572,7 @@ def train(
                     del snap
                 if on_start is not None:
                     on_start({"model": model, "flat": flat, "opt": opt, "step": step, "stager": stager,
-                              "counter": counter, "epoch": epoch})
+                              "val_stager": val_stager, "counter": counter, "epoch": epoch})
                 torch.cuda.synchronize(device)
                 t_mark = time.perf_counter()
             will_val = (counter + 1) % val_step == 0

@@ -45,6 +45,7 @@ def main():
     ap.add_argument("--bev-flip", type=int, default=0, help="trainer --bev_flip")
     ap.add_argument("--valid-mask", default="none", choices=["none", "grid", "fov"], help="trainer --valid_mask")
     ap.add_argument("--fov-z", default="0.0", help="trainer --fov_z")
+    ap.add_argument("--ncams", type=int, default=6, help="trainer --ncams: cameras per training sample")
     a = ap.parse_args()
     from lss_carla_amd import miopen_db
     miopen_db.use_committed()  # before torch starts
@@ -66,12 +67,12 @@ def main():
                             bev_rot_lim=trainer.parse_pair(a.bev_rot_lim, "--bev-rot-lim"),
                             bev_scale_lim=trainer.parse_pair(a.bev_scale_lim, "--bev-scale-lim"),
                             bev_flip=bool(a.bev_flip), valid_mask=a.valid_mask,
-                            fov_z=trainer.parse_heights(a.fov_z))
+                            fov_z=trainer.parse_heights(a.fov_z), ncams=a.ncams)
     print(json.dumps({"frames_per_s": out["frames_per_s"], "steps": out["counter"], "bsz": a.bsz,
                       "nworkers": a.nworkers, "cycle_batches": a.cycle_batches, "graph": a.graph,
                       "skipped": out["skipped"], "loss": out["loss"], "label_groups": a.label_groups or None,
                       "loss_kind": a.loss, "bev_rot_lim": a.bev_rot_lim, "bev_scale_lim": a.bev_scale_lim,
-                      "bev_flip": a.bev_flip, "valid_mask": a.valid_mask, "fov_z": a.fov_z}))
+                      "bev_flip": a.bev_flip, "valid_mask": a.valid_mask, "fov_z": a.fov_z, "ncams": a.ncams}))
 
 
 if __name__ == "__main__":

@@ -287,6 +287,58 @@ int lss_seg_metrics_accum_masked(const void* x, int32_t dtype, const float* targ
                                  double* valid_cells, void* partial, void* stream);
 int64_t lss_seg_metrics_masked_partial_bytes(int64_t n, int32_t K, int32_t T);
 
+/* (ABI 34) Exclusive classes: every cell has exactly one of C classes (2 <= C <= 8; class 0 is the background). x and
+ * grad are (batch, C, plane) contiguous logits, fp32 or bf16 (the K-channel head's NCHW output with K = C); labels is a
+ * (batch, plane) uint8 class map in device memory, a value >= C (255 by convention) meaning "ignore"; valid is NULL or a
+ * (batch, plane) uint8 mask as above. A cell counts iff its label is < C and (valid == NULL or its mask byte != 0). A cell
+ * that does not count is selected out, not multiplied out: it adds nothing to any sum or count and its C gradient
+ * elements are exactly 0, whatever its logits (NaN, +-Inf) -- lss_seg_loss_masked's rule. The existing entries and
+ * their kernels are untouched.
+ *
+ * lss_softmax_ce: F.cross_entropy(x, labels, weight = w, ignore_index, reduction = "mean") and its input gradient in one
+ * pass. weight: C fp32 class weights in DEVICE memory. Per counted cell, fp32 arithmetic, channel sums in ascending c:
+ *   m = max_c x_c,  e_c = exp(x_c - m),  S = sum_c e_c,  p_c = e_c / S,  l = w_y ((m - x_y) + log S)
+ *   dl/dx_c = w_y (p_c - [c = y]), the c = y element written as -w_y (sum_{c != y} e_c) / S (no cancellation at p_y ~ 1)
+ *   loss[0] = sum l / max(W, tiny),  W = sum of w_y over the counted cells
+ * W is not known while the gradient is written, so grad = dl/dx_c / n_cells (n_cells = batch * plane) in the logits'
+ * type, rounded once, scale[0] = n_cells / W, and the backward is lss_seg_loss_masked_bwd over the batch * C * plane
+ * gradient elements (dx = grad * (grad_loss[0] * scale[0])). W = 0 gives loss 0, scale 0 and so a zero gradient.
+ * partial: lss_softmax_ce_partials(n_cells) fp32 (the block sums of l, then of w_y), folded in a fixed order by a
+ * one-wave kernel: two runs give equal bits. Two launches, no atomics, no host read, capturable; weight, valid and labels
+ * are read on the device, so a replay follows an in-place change of any of them. valid == NULL gives the bits of an
+ * all-ones mask. Two arms, the same arithmetic (lss_softmax_ce_arm says which one a call takes):
+ *   LSS_CE_ARM_VECTOR  plane % 8 == 0, x and grad 16-B aligned, labels and valid 8-B aligned: a thread takes 8
+ *                      consecutive cells -- one 8-B label load, one 8-B mask load and C vector loads of the logits, all
+ *                      from unconditional addresses and issued before the first use; one instantiation per C.
+ *   LSS_CE_ARM_SCALAR  anything else: one cell per thread, a channel past C read from a clamped address.
+ * LSS_CONV_EINVAL without launching: a NULL pointer (valid excepted), another dtype, batch or plane < 1, C outside 2..8,
+ * batch * C * plane not addressable, x or grad not aligned to its element, weight / partial / loss / scale to 4 B. */
+enum { LSS_CE_ARM_SCALAR = 0, LSS_CE_ARM_VECTOR = 1 };
+int lss_softmax_ce(const void* x, int32_t dtype, const uint8_t* labels, const uint8_t* valid, int32_t batch,
+                   int64_t plane, int32_t C, const float* weight, float* partial, float* loss, float* scale, void* grad,
+                   void* stream);
+int lss_softmax_ce_arm(const void* x, int32_t dtype, const uint8_t* labels, const uint8_t* valid, int32_t batch,
+                       int64_t plane, int32_t C, const void* grad);
+int64_t lss_softmax_ce_partials(int64_t n_cells);
+/* The prediction: out (batch, plane) uint8 = argmax_c x_c, compared in fp32 with a strict > scanning c upwards from
+ * channel 0 against a running best that starts at -inf: ties go to the lowest class, a NaN never wins, all-NaN gives 0
+ * (torch.argmax differs on NaN). One launch; 8 cells and one 8-B store per thread when plane % 8 == 0, x is 16-B and
+ * out 8-B aligned, else a cell per thread. LSS_CONV_EINVAL as above. */
+int lss_argmax_classes(const void* x, int32_t dtype, int32_t batch, int64_t plane, int32_t C, uint8_t* out,
+                       void* stream);
+/* Validation: the C x C confusion matrix of exact integer counts conf[y][pred] (pred: lss_argmax_classes' rule, the
+ * same device function) over the counted cells of the first n_valid[0] samples (one int32 in device memory, clamped to
+ * 0..batch; NULL = batch), and the loss. totals: 1 + C * C doubles in device memory, +=:
+ *   [0] nv * (sum l) / max(W, tiny) over those cells (the batch's mean loss times its sample count, as
+ *       lss_seg_metrics_accum_masked weights it; l and w_y summed in fp64),   [1 + y * C + pred] the counts
+ * Each block keeps an LDS histogram of C * C int32; a block record is two doubles plus the histogram, and a one-block
+ * kernel folds the records in block order. partial: lss_confusion_partial_bytes(batch * plane, C) bytes (0 for sizes
+ * out of range), 8-B aligned as totals. Two launches, no host read, capturable; one captured launch serves any n_valid. */
+int lss_confusion_accum(const void* x, int32_t dtype, const uint8_t* labels, const uint8_t* valid, int32_t batch,
+                        int64_t plane, int32_t C, const int32_t* n_valid, const float* weight, double* totals,
+                        void* partial, void* stream);
+int64_t lss_confusion_partial_bytes(int64_t n_cells, int32_t C);
+
 /* out[c] = sum over (n, pixel) of x[n][c][pixel] (fp32, fixed order), x (N, C, HW) NCHW fp32 or bf16: the
  * bias gradient of the fused lift's depthnet conv (src/models.py:47) from d(logits). One launch. */
 int lss_channel_sums(const void* x, int32_t dtype, int32_t N, int32_t C, int32_t HW, float* out, void* stream);

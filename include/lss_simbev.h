@@ -80,6 +80,21 @@ int lss_simbev_class_masks_warp(const uint8_t* bev, int32_t n, int32_t n_classes
                                 const uint32_t* group_bits, int32_t K, const float* index_mats, float* out,
                                 void* stream);
 
+/* (ABI 34) The exclusive class map of K label groups (1 <= K <= LSS_SIMBEV_MAX_EXCLUSIVE_GROUPS, so C = K + 1 <= 8
+ * classes fit the K-channel head): out (n, X, Y) uint8, row i = x cell i, column j = y cell j,
+ *   out[b, i, j] = 0 if no group has a set channel at bev[b, ., X-1-i, j], else 1 + the highest such group index
+ * -- class 0 is the background, class k + 1 is group k, and the groups are painted in order: a later group wins over an
+ * earlier one. Equal, bit for bit, to that rule applied to lss_simbev_class_masks' K planes. group_bits: HOST bit masks
+ * passed by value, exactly as lss_simbev_class_masks takes them. index_mats: NULL, or n x 6 fp32 in DEVICE memory --
+ * then the source cell is lss_simbev_class_masks_warp's su / sv and inside test, operation for operation, and a cell
+ * whose source falls outside the grid is 0 (that entry's convention; lss_simbev_valid_mask's grid mode is what makes
+ * a loss ignore those cells). The identity gives the un-warped map. One launch, thread = pixel along j; each channel
+ * some group names is read once, every byte written exactly once. -1 without launching for what
+ * lss_simbev_class_masks refuses, K > 7, X or Y above 2^23, n * X * Y past the grid limit, a misaligned index_mats. */
+#define LSS_SIMBEV_MAX_EXCLUSIVE_GROUPS 7
+int lss_simbev_class_index(const uint8_t* bev, int32_t n, int32_t n_classes, int32_t X, int32_t Y,
+                           const uint32_t* group_bits, int32_t K, const float* index_mats, uint8_t* out, void* stream);
+
 /* (ABI 32) Valid-cell mask for the losses and metrics: out (n, X, Y) uint8, row i = x cell i, column j = y cell j
  * (one class plane of the logits); out[b, i, j] = 1 iff cell (i, j) of sample b is in the grid and, in FOV mode,
  * seen by at least one of the sample's N cameras.

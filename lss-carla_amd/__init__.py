@@ -17,6 +17,7 @@ _LAZY = {
     "gen_dx_bx": "tools", "SimpleLoss": "tools", "get_batch_iou": "tools", "get_batch_iou_device": "tools",
     "get_val_info": "tools", "val_accumulate": "tools",
     "FocalLoss": "tools", "seg_metrics_accumulate": "tools", "seg_metrics_summary": "tools",
+    "SoftmaxLoss": "tools", "confusion_accumulate": "tools", "confusion_summary": "tools", "argmax_classes": "tools",
     "Predictor": "predict", "LRSchedule": "optim",
     "train": "trainer", "BatchStager": "staging", "EvalStep": "train_step", "QuickCumsum": "tools", "cumsum_trick": "tools",
 }

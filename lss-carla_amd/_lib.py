@@ -18,7 +18,7 @@ DEBUG_LIB_PATH = os.path.join(_HERE, "liblss_hip_debug.so")  # LSS_DEBUG=1: devi
 
 F32, BF16 = 0, 1
 NCHW, NHWC = 0, 1
-ABI_VERSION = 33
+ABI_VERSION = 34
 
 
 class Dims(ctypes.Structure):
@@ -96,6 +96,7 @@ SIGNATURES = {
     "lss_simbev_vehicle_mask": (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _p, _p]),
     "lss_simbev_class_masks": (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _p, _i32, _p, _p]),
     "lss_simbev_class_masks_warp": (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _p, _i32, _p, _p, _p]),
+    "lss_simbev_class_index": (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _p, _i32, _p, _p, _p]),
     "lss_simbev_valid_mask": (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _i32] + [ctypes.c_float] * 4 +
                               [_p, _i32, ctypes.c_float, ctypes.c_float, _i32, _i32, _p, _i32, _p, _p]),
     # include/lss_convs.h (conv-stack kernels, same library)
@@ -125,6 +126,12 @@ SIGNATURES = {
     "lss_seg_metrics_accum_masked": (ctypes.c_int, [_p, _i32, _p, _p, ctypes.c_int64, _i32, _p, ctypes.c_int64, _i32,
                                                     _p, _p, _i32, _p, _p, _p, _p]),
     "lss_seg_metrics_masked_partial_bytes": (ctypes.c_int64, [ctypes.c_int64, _i32, _i32]),
+    "lss_softmax_ce": (ctypes.c_int, [_p, _i32, _p, _p, _i32, ctypes.c_int64, _i32, _p, _p, _p, _p, _p, _p]),
+    "lss_softmax_ce_arm": (ctypes.c_int, [_p, _i32, _p, _p, _i32, ctypes.c_int64, _i32, _p]),
+    "lss_softmax_ce_partials": (ctypes.c_int64, [ctypes.c_int64]),
+    "lss_argmax_classes": (ctypes.c_int, [_p, _i32, _i32, ctypes.c_int64, _i32, _p, _p]),
+    "lss_confusion_accum": (ctypes.c_int, [_p, _i32, _p, _p, _i32, ctypes.c_int64, _i32, _p, _p, _p, _p, _p]),
+    "lss_confusion_partial_bytes": (ctypes.c_int64, [ctypes.c_int64, _i32]),
     "lss_bn_bwd_rank1": (ctypes.c_int, [_p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _i32, _i32, _p, _p, _p, _p, _p,
                                         _p]),
     "lss_scale_add": (ctypes.c_int, [_p, _p, ctypes.c_float, _p, ctypes.c_int64, ctypes.c_int64, _p, _p]),

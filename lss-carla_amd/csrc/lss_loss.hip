@@ -1107,3 +1107,432 @@ int lss_seg_metrics_accum_masked(const void* x, int32_t dtype, const float* targ
 }
 
 }  // extern "C"
+
+// ---- Exclusive classes (ABI 34): softmax cross-entropy over (batch, C, plane) logits against a (batch, plane) uint8
+// class map, the argmax class map and a C x C confusion matrix. A cell counts iff its label is < C and its mask byte
+// (when there is a mask) is != 0; a cell that does not count is selected out -- nothing of it reaches a sum, a count
+// or a gradient, whatever its logits are. Per counted cell, fp32, channel sums in ascending c:
+//   m = max_c x_c,  e_c = exp(x_c - m),  S = sum_c e_c,  l = w_y ((m - x_y) + log S),
+//   dl/dx_c = w_y e_c / S (c != y),  dl/dx_y = -w_y (sum_{c != y} e_c) / S
+// -- p_y - 1 written as minus the other classes' share, so a confident, correct cell (p_y one ulp from 1) keeps a
+// gradient with full relative precision. Two arms share every line of arithmetic:
+//   vector  <T, C, 8>: plane % 8 == 0 and aligned bases. Thread = 8 consecutive cells of one sample: one 8-B label
+//           load, one 8-B mask load (the labels again when there is no mask: the address is never conditional) and C
+//           16-B (bf16) or 2 x 16-B (fp32) loads of the logits, all issued before the first use. Instantiated per C,
+//           so no channel is guarded. A thread past the last group loads the last group's addresses and stores nothing.
+//   scalar  <T, 8, 1>: thread = one cell, any plane and alignment. Channel c >= C reads channel C - 1 (a clamped
+//           address, not a guarded load) and takes the value -inf: e_c = 0 leaves S, the sums and the argmax as they
+//           are, bit for bit.
+namespace {
+
+constexpr int kCeMaxC = 8;
+
+// pred = argmax_c x_c with a strict > scanning upwards from -inf: ties go to the lowest class, a NaN never wins,
+// all-NaN (or all -inf) gives 0.
+template <int C> __device__ __forceinline__ int argmax_class(const float (&x)[C]) {
+    int best = 0;
+    float bv = -INFINITY;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const bool gt = x[c] > bv;
+        best = gt ? c : best;
+        bv = gt ? x[c] : bv;
+    }
+    return best;
+}
+
+struct CeTerm {
+    float l, w;  // the cell's loss term and its class weight w_y
+};
+// The label selects x_y and w_y through compare-and-select chains (no indexed register array: no scratch). A label
+// >= C selects nothing (l = w = 0 from finite logits); the caller drops the term of a cell that does not count.
+template <int C, bool GRAD>
+__device__ __forceinline__ CeTerm ce_cell(const float (&x)[C], int y, const float (&w)[C], float inv_n, float (&g)[C]) {
+    float m = x[0];
+#pragma unroll
+    for (int c = 1; c < C; ++c) m = fmaxf(m, x[c]);
+    float e[C], S = 0.f, so = 0.f, xy = m, wy = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        e[c] = expf(x[c] - m);
+        S += e[c];
+        const bool is = c == y;
+        so += is ? 0.f : e[c];
+        xy = is ? x[c] : xy;
+        wy = is ? w[c] : wy;
+    }
+    if constexpr (GRAD) {
+        const float ws = wy * inv_n;
+#pragma unroll
+        for (int c = 0; c < C; ++c) g[c] = ws * (c == y ? -(so / S) : e[c] / S);
+    }
+    return {wy * ((m - xy) + logf(S)), wy};
+}
+
+// A thread's cells: `live` (inside the grid of cells), the sample b and the first cell's position r in its plane.
+// Past the end everything is clamped to the last group, so every load below has an address inside the tensors.
+template <int V> struct CeCoord {
+    bool live;
+    long long b, r;
+    __device__ CeCoord(long long batch, long long plane) {
+        const long long per = plane / V, total = batch * per;
+        const long long g = (long long)blockIdx.x * kBlock + threadIdx.x;
+        live = g < total;
+        const long long gc = live ? g : total - 1;
+        b = gc / per;
+        r = (gc - b * per) * V;
+    }
+};
+
+template <typename T, int C, int V>
+__device__ __forceinline__ void ce_load_x(const T* __restrict__ x, const CeCoord<V>& at, long long plane, int nc,
+                                          float (&xv)[V][C]) {
+    float raw[C][V];
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const int cc = V == 8 ? c : (c < nc ? c : nc - 1);
+        ldv<V>(x + (at.b * nc + cc) * plane + at.r, raw[c]);
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+#pragma unroll
+        for (int j = 0; j < V; ++j) xv[j][c] = (V == 8 || c < nc) ? raw[c][j] : -INFINITY;
+}
+
+// the V label (or mask) bytes of a thread's cells
+template <int V> __device__ __forceinline__ void ce_load_bytes(const uint8_t* __restrict__ p, const CeCoord<V>& at,
+                                                               long long plane, int (&o)[V]) {
+    if constexpr (V == 8) {
+        const uint2 w = *reinterpret_cast<const uint2*>(p + at.b * plane + at.r);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            o[j] = (int)((w.x >> (8 * j)) & 0xFFu);
+            o[4 + j] = (int)((w.y >> (8 * j)) & 0xFFu);
+        }
+    } else {
+        o[0] = p[at.b * plane + at.r];
+    }
+}
+
+template <int C> __device__ __forceinline__ void ce_load_w(const float* __restrict__ weight, int nc, float (&wv)[C]) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) wv[c] = weight[c < nc ? c : nc - 1];
+}
+
+// Loss terms and the stored gradient dl/dx / n_cells. Block record: partial[block] = sum of l, partial[nb + block] =
+// sum of w_y, folded in k_bce_fwd's order (lane, wave butterfly, the 4 waves in order).
+template <typename T, int C, int V>
+__global__ __launch_bounds__(kBlock) void k_softmax_ce(const T* __restrict__ x, const uint8_t* __restrict__ labels,
+                                                       const uint8_t* __restrict__ valid, int use_valid, long long batch,
+                                                       long long plane, int nc, const float* __restrict__ weight,
+                                                       float inv_n, float* __restrict__ partial, T* __restrict__ grad) {
+    __shared__ float s_l[kBlock / kWave], s_w[kBlock / kWave];
+    const CeCoord<V> at(batch, plane);
+    float xv[V][C], wv[C];
+    int yv[V], mv[V];
+    ce_load_x<T, C, V>(x, at, plane, nc, xv);
+    ce_load_bytes<V>(labels, at, plane, yv);
+    ce_load_bytes<V>(valid, at, plane, mv);  // (valid = labels when there is no mask: use_valid = 0)
+    ce_load_w<C>(weight, nc, wv);
+    float sl = 0.f, sw = 0.f;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+        float g[C];
+        const CeTerm t = ce_cell<C, true>(xv[j], yv[j], wv, inv_n, g);
+        const bool on = at.live && yv[j] < nc && (!use_valid || mv[j] != 0);
+        sl += on ? t.l : 0.f;
+        sw += on ? t.w : 0.f;
+#pragma unroll
+        for (int c = 0; c < C; ++c) xv[j][c] = on ? g[c] : 0.f;
+    }
+    if (at.live) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            if (V == 8 || c < nc) {
+                float o[V];
+#pragma unroll
+                for (int j = 0; j < V; ++j) o[j] = xv[j][c];
+                stv<V>(grad + (at.b * nc + c) * plane + at.r, o);
+            }
+        }
+    }
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+        sl += __shfl_xor(sl, o, kWave);
+        sw += __shfl_xor(sw, o, kWave);
+    }
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+        s_l[threadIdx.x / kWave] = sl;
+        s_w[threadIdx.x / kWave] = sw;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float a = 0.f, b = 0.f;
+#pragma unroll
+        for (int w = 0; w < kBlock / kWave; ++w) {
+            a += s_l[w];
+            b += s_w[w];
+        }
+        partial[blockIdx.x] = a;
+        partial[gridDim.x + blockIdx.x] = b;
+    }
+}
+
+// k_seg_loss_masked_total's fold of both sums: loss = sum l / max(W, tiny), scale = n_cells / W (0 for W = 0)
+__global__ __launch_bounds__(kWave) void k_softmax_ce_total(const float* __restrict__ partial, int nb, float nf,
+                                                            float* __restrict__ loss, float* __restrict__ scale) {
+    float s = 0.f, w = 0.f;
+    for (int b = threadIdx.x; b < nb; b += kWave) {
+        s += partial[b];
+        w += partial[nb + b];
+    }
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+        s += __shfl_xor(s, o, kWave);
+        w += __shfl_xor(w, o, kWave);
+    }
+    if (threadIdx.x == 0) {
+        loss[0] = w > 0.f ? s / fmaxf(w, 1.17549435e-38f) : 0.f;
+        scale[0] = w > 0.f ? nf / w : 0.f;
+    }
+}
+
+// The class map of the prediction rule: one byte per cell, 8 bytes per store in the vector arm.
+template <typename T, int C, int V>
+__global__ __launch_bounds__(kBlock) void k_argmax_classes(const T* __restrict__ x, long long batch, long long plane,
+                                                           int nc, uint8_t* __restrict__ out) {
+    const CeCoord<V> at(batch, plane);
+    float xv[V][C];
+    ce_load_x<T, C, V>(x, at, plane, nc, xv);
+    if (!at.live) return;
+    if constexpr (V == 8) {
+        uint2 w = make_uint2(0u, 0u);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            w.x |= (unsigned)argmax_class<C>(xv[j]) << (8 * j);
+            w.y |= (unsigned)argmax_class<C>(xv[4 + j]) << (8 * j);
+        }
+        *reinterpret_cast<uint2*>(out + at.b * plane + at.r) = w;
+    } else {
+        out[at.b * plane + at.r] = (uint8_t)argmax_class<C>(xv[0]);
+    }
+}
+
+// Validation: the counted cells of the first n_valid samples add one to the block's LDS histogram h[y][pred] (integer
+// adds: any order) and their loss terms and weights to fp64 sums folded in a fixed order. Block record: pl[block],
+// pw[block] (doubles), ph[block][nc nc] (int32).
+template <typename T, int C, int V>
+__global__ __launch_bounds__(kBlock) void k_confusion(const T* __restrict__ x, const uint8_t* __restrict__ labels,
+                                                      const uint8_t* __restrict__ valid, int use_valid, long long batch,
+                                                      long long plane, int nc, const int* __restrict__ n_valid,
+                                                      const float* __restrict__ weight, double* __restrict__ pl,
+                                                      double* __restrict__ pw, int* __restrict__ ph) {
+    __shared__ double s_l[kBlock / kWave], s_w[kBlock / kWave];
+    __shared__ int s_h[kCeMaxC * kCeMaxC];
+    if (threadIdx.x < nc * nc) s_h[threadIdx.x] = 0;
+    __syncthreads();
+    long long nv = n_valid ? n_valid[0] : batch;
+    nv = nv < 0 ? 0 : (nv > batch ? batch : nv);
+    const CeCoord<V> at(batch, plane);
+    float xv[V][C], wv[C];
+    int yv[V], mv[V];
+    ce_load_x<T, C, V>(x, at, plane, nc, xv);
+    ce_load_bytes<V>(labels, at, plane, yv);
+    ce_load_bytes<V>(valid, at, plane, mv);
+    ce_load_w<C>(weight, nc, wv);
+    double sl = 0.0, sw = 0.0;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+        float g[C];
+        const CeTerm t = ce_cell<C, false>(xv[j], yv[j], wv, 0.f, g);
+        const int pred = argmax_class<C>(xv[j]);
+        if (at.live && at.b < nv && yv[j] < nc && (!use_valid || mv[j] != 0)) {
+            sl += (double)t.l;
+            sw += (double)t.w;
+            atomicAdd(&s_h[yv[j] * nc + pred], 1);
+        }
+    }
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+        sl += __shfl_xor(sl, o, kWave);
+        sw += __shfl_xor(sw, o, kWave);
+    }
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+        s_l[threadIdx.x / kWave] = sl;
+        s_w[threadIdx.x / kWave] = sw;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double a = 0.0, b = 0.0;
+#pragma unroll
+        for (int w = 0; w < kBlock / kWave; ++w) {
+            a += s_l[w];
+            b += s_w[w];
+        }
+        pl[blockIdx.x] = a;
+        pw[blockIdx.x] = b;
+    }
+    if (threadIdx.x < nc * nc) ph[(size_t)blockIdx.x * nc * nc + threadIdx.x] = s_h[threadIdx.x];
+}
+
+// totals[0] += nv (sum l) / max(W, tiny), the records folded as k_seg_metrics_fold_masked folds its own;
+// totals[1 + y nc + pred] += the counts summed over the blocks in block order.
+__global__ __launch_bounds__(kBlock) void k_confusion_fold(const double* __restrict__ pl, const double* __restrict__ pw,
+                                                           const int* __restrict__ ph, int nb, int nc, int batch,
+                                                           const int* __restrict__ n_valid, double* __restrict__ totals) {
+    __shared__ double s_l[kBlock / kWave], s_w[kBlock / kWave];
+    double s = 0.0, w = 0.0;
+    for (int b = threadIdx.x; b < nb; b += kBlock) {
+        s += pl[b];
+        w += pw[b];
+    }
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+        s += __shfl_xor(s, o, kWave);
+        w += __shfl_xor(w, o, kWave);
+    }
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+        s_l[threadIdx.x / kWave] = s;
+        s_w[threadIdx.x / kWave] = w;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double l = 0.0, W = 0.0;
+#pragma unroll
+        for (int i = 0; i < kBlock / kWave; ++i) {
+            l += s_l[i];
+            W += s_w[i];
+        }
+        int nv = n_valid ? n_valid[0] : batch;
+        nv = nv < 0 ? 0 : (nv > batch ? batch : nv);
+        totals[0] += W > 0.0 ? (double)nv * l / fmax(W, 1.17549435e-38) : 0.0;
+    }
+    if (threadIdx.x < nc * nc) {
+        long long a = 0;
+        for (int b = 0; b < nb; ++b) a += ph[(size_t)b * nc * nc + threadIdx.x];
+        totals[1 + threadIdx.x] += (double)a;
+    }
+}
+
+// One launch of KERNEL's vector arm <T, C, 8> for the call's C, or of its scalar arm <T, 8, 1>
+#define LSS_CE_LAUNCH(KERNEL, T, vec, nc, nb, s, ...)                                                                \
+    do {                                                                                                             \
+        const dim3 g_((unsigned)(nb)), b_(kBlock);                                                                   \
+        if (!(vec)) hipLaunchKernelGGL((KERNEL<T, kCeMaxC, 1>), g_, b_, 0, s, __VA_ARGS__);                          \
+        else switch (nc) {                                                                                           \
+            case 2: hipLaunchKernelGGL((KERNEL<T, 2, 8>), g_, b_, 0, s, __VA_ARGS__); break;                         \
+            case 3: hipLaunchKernelGGL((KERNEL<T, 3, 8>), g_, b_, 0, s, __VA_ARGS__); break;                         \
+            case 4: hipLaunchKernelGGL((KERNEL<T, 4, 8>), g_, b_, 0, s, __VA_ARGS__); break;                         \
+            case 5: hipLaunchKernelGGL((KERNEL<T, 5, 8>), g_, b_, 0, s, __VA_ARGS__); break;                         \
+            case 6: hipLaunchKernelGGL((KERNEL<T, 6, 8>), g_, b_, 0, s, __VA_ARGS__); break;                         \
+            case 7: hipLaunchKernelGGL((KERNEL<T, 7, 8>), g_, b_, 0, s, __VA_ARGS__); break;                         \
+            default: hipLaunchKernelGGL((KERNEL<T, 8, 8>), g_, b_, 0, s, __VA_ARGS__); break;                        \
+        }                                                                                                            \
+    } while (0)
+
+// What the three entries share: sizes in range (batch * C * plane elements addressable, a grid that fits), and the
+// arm -- vector iff plane % 8 == 0, the logits-sized tensors 16-B and the byte maps 8-B aligned.
+bool ce_sizes(int32_t batch, int64_t plane, int32_t C) {
+    return batch > 0 && plane > 0 && C >= 2 && C <= kCeMaxC && plane <= LLONG_MAX / ((long long)batch * C) &&
+           ((long long)batch * plane + kBlock - 1) / kBlock <= INT_MAX;
+}
+bool ce_vector(int64_t plane, const void* a16, const void* b16, const void* a8, const void* b8) {
+    return plane % 8 == 0 && ((reinterpret_cast<uintptr_t>(a16) | reinterpret_cast<uintptr_t>(b16)) & 15) == 0 &&
+           ((reinterpret_cast<uintptr_t>(a8) | reinterpret_cast<uintptr_t>(b8)) & 7) == 0;
+}
+long long ce_blocks(int32_t batch, int64_t plane, bool vec) {
+    const long long units = (long long)batch * (vec ? plane / 8 : plane);
+    return (units + kBlock - 1) / kBlock;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t lss_softmax_ce_partials(int64_t n_cells) { return n_cells <= 0 ? 0 : 2 * ((n_cells + kBlock - 1) / kBlock); }
+
+int lss_softmax_ce_arm(const void* x, int32_t dtype, const uint8_t* labels, const uint8_t* valid, int32_t batch,
+                       int64_t plane, int32_t C, const void* grad) {
+    const int esz = dtype == LSS_CONV_BF16 ? 2 : dtype == LSS_CONV_F32 ? 4 : 0;
+    if (!x || !labels || !grad || !esz || !ce_sizes(batch, plane, C) ||
+        ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(grad)) & (esz - 1)))
+        return LSS_CONV_EINVAL;
+    return ce_vector(plane, x, grad, labels, valid) ? LSS_CE_ARM_VECTOR : LSS_CE_ARM_SCALAR;
+}
+
+int lss_softmax_ce(const void* x, int32_t dtype, const uint8_t* labels, const uint8_t* valid, int32_t batch,
+                   int64_t plane, int32_t C, const float* weight, float* partial, float* loss, float* scale, void* grad,
+                   void* stream) {
+    const int arm = lss_softmax_ce_arm(x, dtype, labels, valid, batch, plane, C, grad);
+    if (arm < 0 || !weight || !partial || !loss || !scale ||
+        ((reinterpret_cast<uintptr_t>(weight) | reinterpret_cast<uintptr_t>(partial) | reinterpret_cast<uintptr_t>(loss) |
+          reinterpret_cast<uintptr_t>(scale)) & 3))
+        return LSS_CONV_EINVAL;
+    const bool vec = arm == LSS_CE_ARM_VECTOR;
+    const long long nb = ce_blocks(batch, plane, vec);
+    const float nf = (float)((long long)batch * plane);
+    const uint8_t* mask = valid ? valid : labels;
+    const int use_valid = valid != nullptr;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == LSS_CONV_BF16)
+        LSS_CE_LAUNCH(k_softmax_ce, bf16, vec, C, nb, s, (const bf16*)x, labels, mask, use_valid, (long long)batch,
+                      (long long)plane, (int)C, weight, 1.0f / nf, partial, (bf16*)grad);
+    else
+        LSS_CE_LAUNCH(k_softmax_ce, float, vec, C, nb, s, (const float*)x, labels, mask, use_valid, (long long)batch,
+                      (long long)plane, (int)C, weight, 1.0f / nf, partial, (float*)grad);
+    hipLaunchKernelGGL(k_softmax_ce_total, dim3(1), dim3(kWave), 0, s, (const float*)partial, (int)nb, nf, loss, scale);
+    return launch_status();
+}
+
+int lss_argmax_classes(const void* x, int32_t dtype, int32_t batch, int64_t plane, int32_t C, uint8_t* out,
+                       void* stream) {
+    const int esz = dtype == LSS_CONV_BF16 ? 2 : dtype == LSS_CONV_F32 ? 4 : 0;
+    if (!x || !out || !esz || !ce_sizes(batch, plane, C) || (reinterpret_cast<uintptr_t>(x) & (esz - 1)))
+        return LSS_CONV_EINVAL;
+    const bool vec = ce_vector(plane, x, nullptr, out, nullptr);
+    const long long nb = ce_blocks(batch, plane, vec);
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == LSS_CONV_BF16)
+        LSS_CE_LAUNCH(k_argmax_classes, bf16, vec, C, nb, s, (const bf16*)x, (long long)batch, (long long)plane, (int)C,
+                      out);
+    else
+        LSS_CE_LAUNCH(k_argmax_classes, float, vec, C, nb, s, (const float*)x, (long long)batch, (long long)plane,
+                      (int)C, out);
+    return launch_status();
+}
+
+int64_t lss_confusion_partial_bytes(int64_t n_cells, int32_t C) {
+    return n_cells <= 0 || C < 2 || C > kCeMaxC
+               ? 0
+               : ((n_cells + kBlock - 1) / kBlock) * (int64_t)(2 * sizeof(double) + (size_t)C * C * sizeof(int));
+}
+
+int lss_confusion_accum(const void* x, int32_t dtype, const uint8_t* labels, const uint8_t* valid, int32_t batch,
+                        int64_t plane, int32_t C, const int32_t* n_valid, const float* weight, double* totals,
+                        void* partial, void* stream) {
+    const int esz = dtype == LSS_CONV_BF16 ? 2 : dtype == LSS_CONV_F32 ? 4 : 0;
+    if (!x || !labels || !weight || !totals || !partial || !esz || !ce_sizes(batch, plane, C) ||
+        (reinterpret_cast<uintptr_t>(x) & (esz - 1)) ||
+        ((reinterpret_cast<uintptr_t>(weight) | reinterpret_cast<uintptr_t>(n_valid)) & 3) ||
+        ((reinterpret_cast<uintptr_t>(totals) | reinterpret_cast<uintptr_t>(partial)) & 7))
+        return LSS_CONV_EINVAL;
+    const bool vec = ce_vector(plane, x, nullptr, labels, valid);
+    const long long nb = ce_blocks(batch, plane, vec);
+    const uint8_t* mask = valid ? valid : labels;
+    const int use_valid = valid != nullptr;
+    double* pl = (double*)partial;
+    double* pw = pl + nb;
+    int* ph = (int*)(pw + nb);
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == LSS_CONV_BF16)
+        LSS_CE_LAUNCH(k_confusion, bf16, vec, C, nb, s, (const bf16*)x, labels, mask, use_valid, (long long)batch,
+                      (long long)plane, (int)C, (const int*)n_valid, weight, pl, pw, ph);
+    else
+        LSS_CE_LAUNCH(k_confusion, float, vec, C, nb, s, (const float*)x, labels, mask, use_valid, (long long)batch,
+                      (long long)plane, (int)C, (const int*)n_valid, weight, pl, pw, ph);
+    hipLaunchKernelGGL(k_confusion_fold, dim3(1), dim3(kBlock), 0, s, (const double*)pl, (const double*)pw,
+                       (const int*)ph, (int)nb, (int)C, (int)batch, (const int*)n_valid, totals);
+    return launch_status();
+}
+
+}  // extern "C"

@@ -198,6 +198,43 @@ __global__ __launch_bounds__(kThreads) void k_class_masks_warp(const uint8_t* __
         if (k < K) o[(size_t)k * XY] = (set & groups.bits[k]) ? 1.0f : 0.0f;
 }
 
+// The exclusive class map (ABI 34): k_class_masks / k_class_masks_warp (mats != NULL: the same su, sv and range test,
+// operation for operation) with the K planes painted in order into one byte -- 0 where no group has a set channel,
+// else 1 + the highest such group: a later group wins. Each channel some group names is read once, each byte
+// written once; a cell whose source is outside the grid is 0, as the warp kernel's planes are.
+__global__ __launch_bounds__(kThreads) void k_class_index(const uint8_t* __restrict__ bev, int ncls, int X, int Y,
+                                                          long total, ClassGroups groups, uint32_t used, int K,
+                                                          const float* __restrict__ mats, uint8_t* __restrict__ out) {
+    const long i = (long)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= total) return;
+    const long XY = (long)X * Y;
+    const long b = i / XY;
+    const long r = i - b * XY;
+    const int row = (int)(r / Y), col = (int)(r - (long)row * Y);
+    int si = row, sj = col;
+    bool inside = true;
+    if (mats) {
+        const float* m = mats + 6 * b;
+        const float ci = __fadd_rn((float)row, 0.5f), cj = __fadd_rn((float)col, 0.5f);
+        const float su = __fadd_rn(__fadd_rn(__fmul_rn(m[0], ci), __fmul_rn(m[1], cj)), m[2]);
+        const float sv = __fadd_rn(__fadd_rn(__fmul_rn(m[3], ci), __fmul_rn(m[4], cj)), m[5]);
+        inside = su >= 0.0f && su < (float)X && sv >= 0.0f && sv < (float)Y;
+        si = (int)floorf(su);
+        sj = (int)floorf(sv);
+    }
+    uint32_t set = 0;
+    if (inside) {
+        const uint8_t* s = bev + (size_t)b * ncls * XY + (size_t)(X - 1 - si) * Y + sj;
+        for (int c = 0; c < ncls; ++c)
+            if ((used >> c) & 1u) set |= (s[(size_t)c * XY] > 0 ? 1u : 0u) << c;
+    }
+    int cls = 0;
+#pragma unroll
+    for (int k = 0; k < LSS_SIMBEV_MAX_GROUPS; ++k)
+        if (k < K && (set & groups.bits[k])) cls = k + 1;
+    out[i] = (uint8_t)cls;
+}
+
 // ---- Valid-cell mask: valid[b, i, j] = in the grid && seen by a camera, the layout of one class plane of the logits.
 // In the grid: k_class_masks_warp's own su / sv and range test on sample b's index matrix (NULL: every cell is).
 // Seen: the cell centre (x, y) = (x0 + i dx, y0 + j dy) at one of the heights z, taken back through the rig --
@@ -381,6 +418,21 @@ int lss_simbev_class_masks_warp(const uint8_t* bev, int32_t n, int32_t n_classes
     if (X > (1 << 23) || Y > (1 << 23)) return -1;  // i + 0.5 and (float)X exact: the range test bounds the gather
     const long total = (long)n * X * Y;
     hipLaunchKernelGGL(k_class_masks_warp, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+                       (hipStream_t)stream, bev, n_classes, X, Y, total, g, used, K, index_mats, out);
+    return launch_status();
+}
+
+int lss_simbev_class_index(const uint8_t* bev, int32_t n, int32_t n_classes, int32_t X, int32_t Y,
+                           const uint32_t* group_bits, int32_t K, const float* index_mats, uint8_t* out, void* stream) {
+    ClassGroups g{};
+    uint32_t used = 0;
+    if (K > LSS_SIMBEV_MAX_EXCLUSIVE_GROUPS ||
+        !class_mask_args(bev, n, n_classes, X, Y, group_bits, K, reinterpret_cast<const float*>(out), &g, &used))
+        return -1;
+    if (X > (1 << 23) || Y > (1 << 23) || (reinterpret_cast<uintptr_t>(index_mats) & 3)) return -1;
+    const long total = (long)n * X * Y;
+    if ((total + kThreads - 1) / kThreads > 0x7FFFFFFFL) return -1;
+    hipLaunchKernelGGL(k_class_index, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0,
                        (hipStream_t)stream, bev, n_classes, X, Y, total, g, used, K, index_mats, out);
     return launch_status();
 }

@@ -41,6 +41,7 @@ state_dict): build it on a model no training step is bound to. The hot path has 
                                     [--loss bce|focal] [--focal_gamma G] [--focal_alpha A] [--iou_thresholds 0.35,...]
                                     [--weights auto|ema|model] [--valid_mask none|grid|fov] [--fov_z 0.0[,1.5,...]]
                                     [--drop_cams front,back_left] [--drop_each 0|1]
+                                    [--exclusive 0|1] [--class_weight w0,...,wK]
 
 runs the val split through ``BatchStager`` and the Predictor and writes one uint8 mask array per sample
 (``DIR/<index>.npy``, (K, X, Y)) and ``DIR/metrics.json``: loss, IoU and per-class IoU from get_val_info's
@@ -56,6 +57,12 @@ the masked form of that accumulate (``lss_seg_metrics_accum_masked``): loss and 
 that camera dead (besides any of --drop_cams), on the same graph, and writes ``"drop_each": {name: {"loss", "iou", ...}}``
 -- the missing-camera table; prediction masks are written for the normal pass only. With ``--valid_mask fov`` a dead
 camera makes no cell valid (simbev.fov_cameras(alive=)).
+``--exclusive 1`` (with ``--label_groups``, 1 to 7 groups; ``--class_weight`` the K + 1 loss weights, default 1) runs a
+model of exclusive classes: the labels are the painted class map (simbev.class_index), each sample's argmax class map
+((X, Y) uint8, ``lss_argmax_classes``) is written to ``DIR/preds/<index>.npy``, and ``metrics.json`` -- and each
+``drop_each`` entry -- carries ``tools.confusion_summary``'s keys (loss, iou over the foreground classes, iou_per_class,
+miou_all, pixel_acc, precision / recall per class, confusion) from ``lss_confusion_accum``. ``--threshold``,
+``--pos_weight``, ``--loss focal``, ``--focal_*`` and ``--iou_thresholds`` with it are errors before anything is built.
 """
 from __future__ import annotations
 
@@ -129,7 +136,7 @@ class Predictor:
 
     def __init__(self, model: torch.nn.Module, bsz: int, device, amp_dtype: Optional[torch.dtype] = torch.bfloat16,
                  threshold=0.5, graph: bool = True, ncams: Optional[int] = None, stager=None,
-                 camera_mask: bool = False):
+                 camera_mask: bool = False, exclusive: bool = False):
         """model: a LiftSplatShoot on `device` (memory formats as the caller set them). bsz: the static batch.
         threshold: one probability, or one per output class (a sequence of K: e.g. the
         ``best_threshold_per_class`` of a validation over a ladder; ``masks()`` then compares in fp32 with the
@@ -137,12 +144,19 @@ class Predictor:
         amp_dtype: autocast dtype (None: fp32). stager: a staging.BatchStager whose static tensors and
         inverses to run on (``run(b)`` after its ``commit()``); None: buffers of the Predictor's own, filled by
         ``__call__``. The graph is captured by the first call, on that call's inputs. camera_mask: run the masked
-        plan kernels over the static ``alive`` tensor (``set_alive`` / ``alive=``); False: the unmasked forward."""
+        plan kernels over the static ``alive`` tensor (``set_alive`` / ``alive=``); False: the unmasked forward.
+        exclusive: the head's C outputs are exclusive classes (class 0 the background; trained with
+        tools.SoftmaxLoss): ``classes()`` is the (b, X, Y) uint8 argmax map (``lss_argmax_classes``), ``probs()`` a
+        softmax over the classes and ``masks()`` the (b, C - 1, X, Y) planes ``classes() == k + 1``. A threshold other
+        than the default 0.5 is then a ValueError: an argmax has none."""
+        if exclusive and not (isinstance(threshold, (int, float)) and float(threshold) == 0.5):  # (before any GPU work)
+            raise ValueError("Predictor(exclusive=True): threshold= does not apply (the prediction is an argmax)")
         from . import ops
         from .flat_params import FlatParams
 
         dev = _require_gpu(device)
         per_class = not isinstance(threshold, (int, float)) and getattr(threshold, "ndim", None) != 0
+        self.exclusive = bool(exclusive)
         self.logit = None if per_class else threshold_logit(threshold)
         self.thetas = None
         self.model, self.device, self.bsz, self.amp_dtype = model, dev, int(bsz), amp_dtype
@@ -152,6 +166,8 @@ class Predictor:
         fH, fW = (int(v) for v in conf["final_dim"])
         self.ncams = N
         self.n_out = int(model.state_dict()[HEAD_WEIGHT].shape[0])
+        if self.exclusive and not 2 <= self.n_out <= 8:
+            raise ValueError(f"Predictor(exclusive=True): a head of {self.n_out} outputs (2..8 classes)")
         if per_class:
             logits = [threshold_logit(v) for v in threshold]
             if len(logits) != self.n_out:
@@ -296,11 +312,26 @@ class Predictor:
         return self._out[:self._b]
 
     def probs(self) -> torch.Tensor:
-        """sigmoid of the last call's logits, fp32 (``out.sigmoid()``, src/explore.py:322)."""
+        """sigmoid of the last call's logits, fp32 (``out.sigmoid()``, src/explore.py:322); exclusive classes: the
+        softmax over dim 1."""
+        if self.exclusive:
+            return torch.softmax(self.logits().float(), dim=1)
         return self.logits().float().sigmoid()
+
+    def classes(self) -> torch.Tensor:
+        """Exclusive classes: the (b, X, Y) uint8 class map of the last call, ``lss_argmax_classes`` (ties to the
+        lowest class, a NaN never wins). A fresh tensor."""
+        if not self.exclusive:
+            raise RuntimeError("Predictor: classes() needs exclusive=True (sigmoid channels have no argmax)")
+        from . import tools
+        return tools.argmax_classes(self.logits())
 
     def masks(self) -> torch.Tensor:
         """uint8 (b, K, X, Y): probability > threshold, as logits > logit(threshold) (per class: in fp32)."""
+        if self.exclusive:  # (b, C - 1, X, Y): plane k = classes() == k + 1, one plane per label group
+            cls = self.classes().unsqueeze(1)
+            ks = torch.arange(1, self.n_out, device=cls.device, dtype=torch.uint8).view(1, -1, 1, 1)
+            return (cls == ks).to(torch.uint8)
         if self.thetas is not None:
             return (self.logits().float() > self.thetas.view(-1, 1, 1)).to(torch.uint8)
         return (self.logits() > self.logit).to(torch.uint8)
@@ -386,6 +417,10 @@ def parser() -> argparse.ArgumentParser:
                    help="cameras dead in every sample, names or indices: front,back_left")
     p.add_argument("--drop_each", type=int, default=0, choices=[0, 1],
                    help="1: after the normal pass, the split once more per camera with that camera dead (same graph)")
+    p.add_argument("--exclusive", type=int, default=0, choices=[0, 1],
+                   help="1: exclusive classes (argmax class maps in DIR/preds/, confusion-matrix metrics); needs --label_groups")
+    p.add_argument("--class_weight", type=str, default=None,
+                   help="--exclusive 1: the loss's weight per class, the background first: w0,...,wK (default all 1)")
     p.add_argument("--gpuid", type=int, default=0)
     p.add_argument("--nworkers", type=int, default=4)
     p.add_argument("--H", type=int, default=224)
@@ -410,6 +445,20 @@ def predict(a, grid_conf=None, data_aug_conf=None, model: Optional[torch.nn.Modu
     """The command line's work for parsed arguments `a`; returns metrics.json's dict. grid_conf / data_aug_conf
     override the defaults of ``confs``; model: an already built (and loaded) module instead of --modelf."""
     dropped = parse_drop_cams(getattr(a, "drop_cams", None))  # (a bad name fails before anything else)
+    exclusive = bool(getattr(a, "exclusive", 0))
+    class_weight = None
+    if exclusive:  # (argument errors before anything is built, the GPU included)
+        from .trainer import _exclusive_setup, _weights_list, parse_label_groups as _groups, parse_per_class as _pc
+        th = threshold_arg(a.threshold) if isinstance(a.threshold, str) else a.threshold
+        if not (isinstance(th, (int, float)) and float(th) == 0.5):
+            raise ValueError("--threshold does not apply to exclusive classes (the prediction is an argmax)")
+        cw = getattr(a, "class_weight", None)
+        class_weight = _exclusive_setup(
+            _groups(a.label_groups), None if cw is None else (_weights_list(cw) if isinstance(cw, str) else list(cw)),
+            getattr(a, "pos_weight", None), getattr(a, "loss", "bce"), _pc(getattr(a, "focal_gamma", "2.0"), "--focal_gamma"),
+            getattr(a, "focal_alpha", None), getattr(a, "iou_thresholds", None) or None)
+    elif getattr(a, "class_weight", None) is not None:
+        raise ValueError("--class_weight needs --exclusive 1")
     if a.gpuid < 0:
         raise RuntimeError("lss_carla_amd.predict: needs an MI355X (the hot path has no CPU fallback)")
     dev = _require_gpu(f"cuda:{a.gpuid}")
@@ -445,10 +494,11 @@ def predict(a, grid_conf=None, data_aug_conf=None, model: Optional[torch.nn.Modu
     drop_each = bool(getattr(a, "drop_each", 0))
     use_mask = bool(dropped) or drop_each
     amp_dtype = torch.bfloat16 if a.dtype == "bf16" else None
+    n_out = K + 1 if exclusive else K  # exclusive classes: the background and the K groups
     if model is None:
         sd = model_state_dict(torch.load(a.modelf, map_location="cpu"), getattr(a, "weights", "auto"))
-        check_head(sd, K, f"checkpoint {a.modelf}")  # before anything is built
-        model = L.compile_model(grid_conf, data_aug_conf, outC=K).to(dev)
+        check_head(sd, n_out, f"checkpoint {a.modelf}")  # before anything is built
+        model = L.compile_model(grid_conf, data_aug_conf, outC=n_out).to(dev)
         model.load_state_dict(sd)
     model.bevencode.to(memory_format=torch.channels_last)
     model.camencode.up1.to(memory_format=torch.channels_last)
@@ -457,9 +507,10 @@ def predict(a, grid_conf=None, data_aug_conf=None, model: Optional[torch.nn.Modu
     val_raw, n_val = valloader.loader, len(valloader.dataset)
     stager = BatchStager(data_aug_conf["final_dim"], a.bsz, len(simbev.CAMERA_ORDER),
                          (data_aug_conf["H"], data_aug_conf["W"]), grid_conf, dev, label_groups=groups,
-                         **({} if mask_mode is None else {"valid_mask": mask_mode, "fov_z": fov_z}))
+                         **({} if mask_mode is None else {"valid_mask": mask_mode, "fov_z": fov_z}),
+                         **({"exclusive": True} if exclusive else {}))
     p = Predictor(model, a.bsz, dev, amp_dtype=amp_dtype, threshold=threshold, graph=bool(a.graph), stager=stager,
-                  **({"camera_mask": True} if use_mask else {}))
+                  **({"camera_mask": True} if use_mask else {}), **({"exclusive": True} if exclusive else {}))
     if K > 1 or not tools.is_scalar_weight(pos_weight):
         pos_weight = tools.class_weights(pos_weight, K, dev)
     totals = torch.zeros(1 + 2 * K, device=dev, dtype=torch.float64)
@@ -476,6 +527,10 @@ def predict(a, grid_conf=None, data_aug_conf=None, model: Optional[torch.nn.Modu
             w = tools.class_weights(pos_weight, K, dev)
             params = torch.stack([w, torch.ones_like(w), torch.zeros_like(w)], dim=1).contiguous()
         totals = torch.zeros(1 + K + 2 * K * len(columns), device=dev, dtype=torch.float64)
+    if exclusive:  # lss_confusion_accum: 1 + C C totals, the loss with the class weights
+        ladder_mode, valid_cells = False, None
+        totals = torch.zeros(1 + n_out * n_out, device=dev, dtype=torch.float64)
+        weight_dev = torch.tensor(class_weight, device=dev, dtype=torch.float32)
     os.makedirs(a.out, exist_ok=True)
     n_cams = len(simbev.CAMERA_ORDER)
 
@@ -499,13 +554,16 @@ def predict(a, grid_conf=None, data_aug_conf=None, model: Optional[torch.nn.Modu
         while nxt is not None:
             b = stager.commit()
             p.run(b)  # (the first call captures the graph: timed from the second batch on)
-            if ladder_mode:
+            if exclusive:
+                tools.confusion_accumulate(p._out, stager.binimgs, totals, stager.n_valid, weight_dev,
+                                           valid=stager.valid)
+            elif ladder_mode:
                 tools.seg_metrics_accumulate(p._out, stager.binimgs, totals, stager.n_valid, params, thetas,
                                              valid=stager.valid, valid_cells=valid_cells)
             else:
                 tools.val_accumulate(p._out, stager.binimgs, totals, n_valid=stager.n_valid, pos_weight=pos_weight)
             if keep_masks:
-                masks.append(p.masks())  # a fresh tensor per batch; the logits are static
+                masks.append(p.classes() if exclusive else p.masks())  # a fresh tensor per batch; the logits are static
                 if mask_mode is not None:
                     valids.append(stager.valid[:b].clone())
             nxt = next(it, None)
@@ -521,6 +579,9 @@ def predict(a, grid_conf=None, data_aug_conf=None, model: Optional[torch.nn.Modu
 
     def summary(t):
         """loss, the IoU keys and the ladder's keys out of a pass's totals (a list)."""
+        if exclusive:
+            cells = None if mask_mode is None else n_val * (stager.valid.numel() // stager.valid.shape[0])
+            return tools.confusion_summary(t, n_out, n_val, cells=cells)
         extra = {}
         if ladder_mode:
             P, TP, PP = tools.seg_metrics_counts(t, K, len(columns))
@@ -548,9 +609,11 @@ def predict(a, grid_conf=None, data_aug_conf=None, model: Optional[torch.nn.Modu
             run_split(set(dropped) | {c}, False)
             each[name] = summary(totals.tolist())
     index = 0
+    pred_dir = os.path.join(a.out, "preds") if exclusive else a.out  # exclusive classes: the (X, Y) class maps
+    os.makedirs(pred_dir, exist_ok=True)
     for m in masks:
         for s in m.cpu().numpy():
-            np.save(os.path.join(a.out, f"{index}.npy"), s)
+            np.save(os.path.join(pred_dir, f"{index}.npy"), s)
             index += 1
     if mask_mode is not None:
         os.makedirs(os.path.join(a.out, "valid"), exist_ok=True)
@@ -560,11 +623,16 @@ def predict(a, grid_conf=None, data_aug_conf=None, model: Optional[torch.nn.Modu
                 np.save(os.path.join(a.out, "valid", f"{vi}.npy"), s)
                 vi += 1
     valid_fraction = main_info.pop("valid_fraction", None)
-    inter, union = main_info.pop("intersection"), main_info.pop("union")
-    info = {**main_info, "loss_kind": loss_kind,
-            "threshold": threshold, "intersection": inter, "union": union, "samples": index, "classes": K,
-            "dtype": a.dtype, "graph": bool(a.graph), "bsz": a.bsz,
-            "frames_per_s": frames / elapsed if frames and elapsed > 0 else None}
+    if exclusive:
+        info = {**main_info, "loss_kind": "softmax", "exclusive": True, "class_weight": class_weight, "samples": index,
+                "classes": n_out, "dtype": a.dtype, "graph": bool(a.graph), "bsz": a.bsz,
+                "frames_per_s": frames / elapsed if frames and elapsed > 0 else None}
+    else:
+        inter, union = main_info.pop("intersection"), main_info.pop("union")
+        info = {**main_info, "loss_kind": loss_kind,
+                "threshold": threshold, "intersection": inter, "union": union, "samples": index, "classes": K,
+                "dtype": a.dtype, "graph": bool(a.graph), "bsz": a.bsz,
+                "frames_per_s": frames / elapsed if frames and elapsed > 0 else None}
     if mask_mode is not None:
         info.update({"valid_mask": mask_mode, "fov_z": list(fov_z), "valid_fraction": valid_fraction})
     if use_mask:

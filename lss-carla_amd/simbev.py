@@ -405,6 +405,69 @@ def class_masks(bev_u8: torch.Tensor, label_groups=None, out=None, index_mats=No
     return out
 
 
+MAX_EXCLUSIVE_GROUPS = 7  # LSS_SIMBEV_MAX_EXCLUSIVE_GROUPS: C = K + 1 classes on the K-channel head (C <= 8)
+IGNORE_LABEL = 255        # the class-map value no class has: losses and metrics skip the cell
+
+
+def exclusive_bits(label_groups) -> List[int]:
+    """group_bits for the exclusive class map: 1..7 groups (class 0 is the background, class k + 1 is group k)."""
+    bits = group_bits(label_groups)
+    if len(bits) > MAX_EXCLUSIVE_GROUPS:
+        raise ValueError(f"exclusive classes: 1..{MAX_EXCLUSIVE_GROUPS} label groups, got {len(bits)}")
+    return bits
+
+
+def class_index(bev_u8: torch.Tensor, label_groups, out=None, index_mats=None, keep=None) -> torch.Tensor:
+    """(n, C, X, Y) uint8 device BEV maps -> the (n, X, Y) uint8 exclusive class map of K = len(label_groups) groups,
+    ``lss_simbev_class_index``: 0 where no group has a set channel (background), else 1 + the highest such group --
+    the groups are painted in order and a later one wins, so with "0;1,2,3;6,7" a road cell under a vehicle is
+    vehicle. Equal to that rule applied to ``class_masks``' planes. out: a contiguous uint8 device tensor of
+    n * X * Y elements to write. index_mats / keep: as ``class_masks`` -- the map under the BEV-space augmentation;
+    a cell whose source is outside the grid is 0 (``valid_mask`` mode "grid" is what ignores it)."""
+    if not bev_u8.is_cuda:
+        raise RuntimeError("lss_carla_amd.simbev: BEV maps must be on the MI355X (no CPU fallback)")
+    if bev_u8.dtype == torch.bool:
+        bev_u8 = bev_u8.view(torch.uint8)
+    if bev_u8.dtype != torch.uint8:
+        bev_u8 = (bev_u8 > 0).to(torch.uint8)
+    n, C, X, Y = bev_u8.shape
+    bits = exclusive_bits(label_groups)
+    K = len(bits)
+    if out is None:
+        out = torch.empty(n, X, Y, device=bev_u8.device, dtype=torch.uint8)
+    elif not (out.is_cuda and out.device == bev_u8.device and out.dtype == torch.uint8 and out.is_contiguous()
+              and out.numel() == n * X * Y):
+        raise RuntimeError(f"out= must be a contiguous uint8 device tensor of {(n, X, Y)}")
+    b = bev_u8.contiguous()
+    host = (ctypes.c_uint32 * K)(*bits)
+    mats = None
+    if index_mats is not None:
+        mats = torch.as_tensor(index_mats)
+        if mats.dtype != torch.float32 or tuple(mats.shape) != (n, 2, 3):
+            raise RuntimeError(f"index_mats= must be {(n, 2, 3)} fp32, got {mats.dtype} {tuple(mats.shape)}")
+        if not mats.is_cuda:
+            mats = mats.contiguous().pin_memory().to(b.device, non_blocking=True)
+        elif mats.device != b.device:
+            raise RuntimeError(f"index_mats= is on {mats.device}, the BEV maps on {b.device}")
+        mats = mats.contiguous()
+        if keep is not None:
+            keep.extend([mats, b])
+    _lib.check(_lib.load().lss_simbev_class_index(_lib.ptr(b), n, C, X, Y, ctypes.cast(host, ctypes.c_void_p), K,
+                                                  _lib.ptr(mats), _lib.ptr(out), _lib.stream_handle(b.device)),
+               "lss_simbev_class_index")
+    return out
+
+
+def class_index_from_masks(masks) -> "np.ndarray":
+    """The paint-order rule on (n, K, X, Y) group planes (a tensor or an array, any value != 0 = set), on the host:
+    0 where no plane is set, else 1 + the highest set plane. What ``class_index`` equals bit for bit."""
+    m = np.asarray(masks.detach().cpu() if torch.is_tensor(masks) else masks) != 0
+    out = np.zeros((m.shape[0],) + m.shape[2:], dtype=np.uint8)
+    for k in range(m.shape[1]):
+        out[m[:, k]] = k + 1
+    return out
+
+
 # ----------------------------------------------------------------------------- valid-cell mask
 VALID_MASK_MODES = ("grid", "fov")   # LSS_SIMBEV_VALID_GRID / LSS_SIMBEV_VALID_FOV of include/lss_simbev.h
 MAX_FOV_HEIGHTS = 8                  # LSS_SIMBEV_MAX_HEIGHTS
@@ -668,14 +731,17 @@ def worker_rnd_init(x):
     np.random.seed(13 + x)  # src/data_simbev.py:310-312
 
 
-def finish_batch(batch, final_dim, device, label_groups=None, bev_aug=False, valid_mask_conf=None):
+def finish_batch(batch, final_dim, device, label_groups=None, bev_aug=False, valid_mask_conf=None, exclusive=False):
     """A collated raw batch -> the reference's (imgs, rots, trans, intrins, post_rots, post_trans,
     [lidar,] binimgs) on `device`, the pixel work done by the HIP kernels. label_groups: K lists of BEV
     channels -> binimgs (B, K, X, Y) (class_masks); None: the reference's vehicle mask, (B, 1, X, Y).
     bev_aug: the batch comes from a conf with the BEV-space augmentation (bev_aug_enabled): the element before
     the BEV maps is the (B, 2, 3) label index matrices, which warp the labels; the rig is already composed.
     valid_mask_conf: None (the tuple is as above), or (mode, grid_conf, heights) -- the finished batch then carries,
-    after the labels, the (B, X, Y) uint8 valid-cell mask of ``valid_mask`` on the batch's host rig."""
+    after the labels, the (B, X, Y) uint8 valid-cell mask of ``valid_mask`` on the batch's host rig.
+    exclusive: binimgs is the (B, X, Y) uint8 exclusive class map of the groups (class_index) instead."""
+    if exclusive and label_groups is None:
+        raise ValueError("exclusive classes need label_groups")
     imgs_u8, rots, trans, intrins, post_rots, post_trans, aug, rot = batch[:8]
     rest = batch[8:]
     index_mats = None
@@ -696,7 +762,10 @@ def finish_batch(batch, final_dim, device, label_groups=None, bev_aug=False, val
     out[4]._lss_host, out[4]._lss_host_version = post_rots, out[4]._version
     for t in rest[:-1]:
         out.append(t)  # lidar placeholder (VizData)
-    out.append(class_masks(rest[-1].to(device, non_blocking=True), label_groups, index_mats=index_mats))
+    if exclusive:
+        out.append(class_index(rest[-1].to(device, non_blocking=True), label_groups, index_mats=index_mats))
+    else:
+        out.append(class_masks(rest[-1].to(device, non_blocking=True), label_groups, index_mats=index_mats))
     if valid_mask_conf is not None:
         mode, grid_conf, heights = valid_mask_conf
         X, Y = out[-1].shape[-2:]
@@ -710,9 +779,11 @@ def finish_batch(batch, final_dim, device, label_groups=None, bev_aug=False, val
 class DeviceLoader:
     """Iterates a DataLoader of raw samples and yields finished device batches (finish_batch)."""
 
-    def __init__(self, loader, final_dim, device, label_groups=None, bev_aug=False, valid_mask_conf=None):
+    def __init__(self, loader, final_dim, device, label_groups=None, bev_aug=False, valid_mask_conf=None,
+                 exclusive=False):
         self.loader, self.final_dim, self.device = loader, final_dim, torch.device(device)
         self.label_groups, self.bev_aug = label_groups, bool(bev_aug)
+        self.exclusive = bool(exclusive)  # the labels are the (B, X, Y) uint8 class map (class_index)
         self.valid_mask_conf = valid_mask_conf  # None, or (mode, grid_conf, heights): finish_batch appends the mask
         self.dataset = loader.dataset
         self.batch_size = loader.batch_size
@@ -722,7 +793,10 @@ class DeviceLoader:
 
     def __iter__(self):
         for batch in self.loader:
-            if self.valid_mask_conf is None:
+            if self.exclusive:
+                yield finish_batch(batch, self.final_dim, self.device, self.label_groups, self.bev_aug,
+                                   self.valid_mask_conf, exclusive=True)
+            elif self.valid_mask_conf is None:
                 yield finish_batch(batch, self.final_dim, self.device, self.label_groups, self.bev_aug)
             else:
                 yield finish_batch(batch, self.final_dim, self.device, self.label_groups, self.bev_aug,
@@ -730,19 +804,24 @@ class DeviceLoader:
 
 
 def compile_data(version, dataroot, data_aug_conf, grid_conf, bsz, nworkers, parser_name, device="cuda",
-                 label_groups=None):
+                 label_groups=None, exclusive=False):
     """src/data_simbev.py:315-354 with the same loaders' settings; returns DeviceLoaders. label_groups: the
     BEV channel groups of a multi-class model's labels (finish_batch); None: the reference's vehicle mask.
     A data_aug_conf with bev_rot_lim / bev_scale_lim / bev_flip (bev_aug_enabled) adds the BEV-space augmentation to
     the training loader -- the rig composed, the labels warped -- and never to the validation loader; both loaders
     carry the flag (``bev_aug``) that says their raw batches hold the label index matrices. A data_aug_conf with
     ``valid_mask`` "grid" or "fov" (valid_mask_mode; heights ``fov_z``) makes both loaders' finished batches carry the
-    valid-cell mask after the labels -- validation's too: that is the point of a masked metric."""
+    valid-cell mask after the labels -- validation's too: that is the point of a masked metric. exclusive: the labels
+    of both loaders are the (B, X, Y) uint8 exclusive class map of the 1..7 label_groups (class_index)."""
     bev_aug = bev_aug_enabled(data_aug_conf)  # (a bad limit fails here)
     mask_mode = valid_mask_mode(data_aug_conf)
     mask_conf = None if mask_mode is None else (mask_mode, grid_conf, fov_heights(data_aug_conf))
     if label_groups is not None:
         group_bits(label_groups)  # a bad group list fails here, not in the first batch
+    if exclusive:
+        if label_groups is None:
+            raise ValueError("exclusive classes need label_groups")
+        exclusive_bits(label_groups)
     parser = {"vizdata": VizData, "segmentationdata": SegmentationData}[parser_name]
     traindata = parser(dataroot, is_train=True, data_aug_conf=data_aug_conf, grid_conf=grid_conf)
     valdata = parser(dataroot, is_train=False, data_aug_conf=data_aug_conf, grid_conf=grid_conf)
@@ -751,5 +830,8 @@ def compile_data(version, dataroot, data_aug_conf, grid_conf, bsz, nworkers, par
     valloader = torch.utils.data.DataLoader(valdata, batch_size=bsz, shuffle=False, num_workers=nworkers,
                                             pin_memory=True)
     fd = data_aug_conf["final_dim"]
+    if exclusive:
+        return (DeviceLoader(trainloader, fd, device, label_groups, bev_aug, mask_conf, exclusive=True),
+                DeviceLoader(valloader, fd, device, label_groups, bev_aug, mask_conf, exclusive=True))
     return (DeviceLoader(trainloader, fd, device, label_groups, bev_aug, mask_conf),
             DeviceLoader(valloader, fd, device, label_groups, bev_aug, mask_conf))

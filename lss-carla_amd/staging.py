@@ -34,7 +34,7 @@ from . import ops, simbev
 
 
 class _Slot:
-    def __init__(self, B, N, fH, fW, src_hw, K, X, Y, dev):
+    def __init__(self, B, N, fH, fW, src_hw, K, X, Y, dev, exclusive=False):
         H, W = int(src_hw[0]), int(src_hw[1])
         self.u8 = torch.empty(B * N, H, W, 3, device=dev, dtype=torch.uint8)
         self.bev_u8 = None  # (B, classes, X, Y): sized by the first batch
@@ -44,7 +44,10 @@ class _Slot:
         self.intrins = torch.zeros(B, N, 3, 3, device=dev)
         self.post_rots = torch.zeros(B, N, 3, 3, device=dev)
         self.post_trans = torch.zeros(B, N, 3, device=dev)
-        self.binimgs = torch.zeros(B, K, X, Y, device=dev, dtype=torch.float32)
+        if exclusive:  # the (B, X, Y) uint8 exclusive class map of the K groups
+            self.binimgs = torch.zeros(B, X, Y, device=dev, dtype=torch.uint8)
+        else:
+            self.binimgs = torch.zeros(B, K, X, Y, device=dev, dtype=torch.float32)
         self.valid = None  # (B, X, Y) uint8, all ones, when the stager keeps a valid-cell mask
         self.host_post_rots = None
         self.host_intrins = None
@@ -58,7 +61,7 @@ class BatchStager:
     RIG = ("rots", "trans", "intrins", "post_rots", "post_trans")
 
     def __init__(self, final_dim: Sequence[int], B: int, N: int, src_hw: Sequence[int], grid: dict, device,
-                 label_groups=None, bev_aug=False, valid_mask=None, fov_z=(0.0,), dbound=None):
+                 label_groups=None, bev_aug=False, valid_mask=None, fov_z=(0.0,), dbound=None, exclusive=False):
         """label_groups: K lists of BEV channels, one label channel each (simbev.class_masks): ``binimgs`` and
         both slots are (B, K, X, Y); None: the reference's vehicle mask, K = 1. bev_aug: the raw batches come from a
         conf with the BEV-space augmentation (simbev.bev_aug_enabled): the element before the BEV maps is the
@@ -70,7 +73,10 @@ class BatchStager:
         Training and validation batches are masked alike; without index matrices every cell is in the grid. With
         "fov" the mask comes from the cameras the batch actually holds: a stager of N < 6 cameras (training on a camera
         subset) marks a cell only a dropped camera would see invalid in that sample. ``cam_alive`` (an attribute, None
-        or an (N,) / (B, N) host mask) further blanks dead cameras' blocks (simbev.fov_cameras(alive=))."""
+        or an (N,) / (B, N) host mask) further blanks dead cameras' blocks (simbev.fov_cameras(alive=)).
+        exclusive: ``binimgs`` and both slots are the (B, X, Y) uint8 exclusive class map of the 1..7 label_groups
+        (0 the background, k + 1 group k, a later group wins), written by ``lss_simbev_class_index`` on the staging
+        stream in ``lss_simbev_class_masks``' place; nothing else differs."""
         dev = torch.device(device)
         if dev.type != "cuda":
             raise RuntimeError("BatchStager: the static tensors live on the MI355X (no CPU fallback)")
@@ -88,7 +94,14 @@ class BatchStager:
         self.label_groups = None if label_groups is None else [list(g) for g in label_groups]
         self.bev_aug = bool(bev_aug)
         K = 1 if label_groups is None else len(self.label_groups)
-        self.binimgs = torch.zeros(B, K, X, Y, device=dev, dtype=torch.float32)
+        self.exclusive = bool(exclusive)
+        if self.exclusive:
+            if label_groups is None:
+                raise ValueError("BatchStager: exclusive classes need label_groups")
+            simbev.exclusive_bits(label_groups)
+            self.binimgs = torch.zeros(B, X, Y, device=dev, dtype=torch.uint8)
+        else:
+            self.binimgs = torch.zeros(B, K, X, Y, device=dev, dtype=torch.float32)
         if valid_mask is not None and valid_mask not in simbev.VALID_MASK_MODES:
             raise ValueError(f"BatchStager: valid_mask {valid_mask!r}: None, grid or fov")
         self.valid_mask = valid_mask
@@ -102,7 +115,10 @@ class BatchStager:
         self._host_post_rots = torch.eye(3).repeat(B, N, 1, 1)
         self._host_intrins = torch.eye(3).repeat(B, N, 1, 1)
         self.stream = torch.cuda.Stream(dev)
-        self._slots = [_Slot(B, N, fH, fW, src_hw, K, X, Y, dev) for _ in range(2)]
+        if self.exclusive:
+            self._slots = [_Slot(B, N, fH, fW, src_hw, K, X, Y, dev, exclusive=True) for _ in range(2)]
+        else:
+            self._slots = [_Slot(B, N, fH, fW, src_hw, K, X, Y, dev) for _ in range(2)]
         if valid_mask is not None:
             for slot in self._slots:
                 slot.valid = torch.ones(B, X, Y, device=dev, dtype=torch.uint8)
@@ -132,7 +148,7 @@ class BatchStager:
                                f"B={self.B}, N={self.N}, source {tuple(slot.u8.shape[1:3])}")
         if bev.dtype == torch.bool:
             bev = bev.view(torch.uint8)
-        if bev.dtype != torch.uint8 or bev.dim() != 4 or tuple(bev.shape[2:]) != tuple(slot.binimgs.shape[2:]):
+        if bev.dtype != torch.uint8 or bev.dim() != 4 or tuple(bev.shape[2:]) != tuple(slot.binimgs.shape[-2:]):
             raise RuntimeError(f"BatchStager.stage: BEV maps {bev.dtype} {tuple(bev.shape)} against labels "
                                f"{tuple(slot.binimgs.shape)}")
         if index_mats is not None and (index_mats.dtype != torch.float32 or tuple(index_mats.shape) != (b, 2, 3)):
@@ -164,8 +180,12 @@ class BatchStager:
             for name, t in zip(self.RIG, (rots, trans, intrins, post_rots, post_trans)):
                 getattr(slot, name)[:b].copy_(t, non_blocking=True)
             simbev.augment_images(slot.u8[:b * N], augs, self.final_dim, out=slot.imgs[:b], keep=keep)
-            simbev.class_masks(slot.bev_u8[:b], self.label_groups, out=slot.binimgs[:b], index_mats=index_mats,
-                               keep=keep)
+            if self.exclusive:
+                simbev.class_index(slot.bev_u8[:b], self.label_groups, out=slot.binimgs[:b], index_mats=index_mats,
+                                   keep=keep)
+            else:
+                simbev.class_masks(slot.bev_u8[:b], self.label_groups, out=slot.binimgs[:b], index_mats=index_mats,
+                                   keep=keep)
             if self.valid_mask is not None:
                 simbev.valid_mask(cams, post_trans if cams is not None else None, self.grid, self.final_dim,
                                   self.fov_z, index_mats=index_mats, mode=self.valid_mask, out=slot.valid[:b],

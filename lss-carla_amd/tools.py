@@ -613,6 +613,252 @@ def seg_metrics_summary(totals, K: int, thresholds, n_samples) -> dict:
             "best_threshold_per_class": best_th, "iou_max": sum(seen) / len(seen) if seen else None}
 
 
+# ----------------------------------------------------------------------------- exclusive classes
+IGNORE_LABEL = 255   # a class-map value >= C means "ignore"; 255 by convention (F.cross_entropy's ignore_index here)
+MAX_CLASSES = 8      # the K-channel head's width: C = label groups + 1 <= 8
+USE_HIP_SOFTMAX = True  # SoftmaxLoss takes ``lss_softmax_ce`` where it applies; False: always the torch composition
+
+
+def _check_class_map(x: torch.Tensor, labels: torch.Tensor, valid, C: int, who: str):
+    """Logits (batch, C, ...) against a (batch, ...) uint8 class map and an optional uint8 mask of the same cells."""
+    if x.dim() < 2 or x.shape[1] != C:
+        raise RuntimeError(f"{who}: {C} classes for logits {tuple(x.shape)}")
+    cells = (x.shape[0],) + tuple(x.shape[2:])
+    if labels.dtype != torch.uint8 or tuple(labels.shape) != cells:
+        raise RuntimeError(f"{who}: labels must be the {cells} uint8 class map, got {labels.dtype} {tuple(labels.shape)}")
+    if valid is not None and (valid.shape[0] != x.shape[0] or valid.numel() != labels.numel()):
+        raise RuntimeError(f"{who}: valid {tuple(valid.shape)} is not one plane per sample of logits {tuple(x.shape)}")
+
+
+def counted_cells(labels: torch.Tensor, valid, C: int) -> torch.Tensor:
+    """The cell selection of the exclusive forms as booleans of labels' shape: label < C and (no mask or mask != 0)."""
+    on = labels < C
+    if valid is not None:
+        on = on & (valid.to(labels.device).reshape(labels.shape) != 0)
+    return on
+
+
+def softmax_ce_terms(x: torch.Tensor, labels: torch.Tensor, valid, weight: torch.Tensor):
+    """(loss, d loss / dx) of the exclusive-class loss in torch, in x's dtype (fp32 or fp64): per counted cell
+    l = w_y (m + log S - x_y) and dl/dx_c = w_y (p_c - [c = y]) as ``lss_softmax_ce`` writes them (the c = y element
+    as minus the other classes' share), cells that do not count selected out by torch.where -- a NaN there reaches
+    nothing -- and both divided by max(W, tiny), W the counted cells' summed weights (W = 0: loss 0, gradient 0)."""
+    C = x.shape[1]
+    on = counted_cells(labels, valid, C)
+    y = torch.where(on, labels, torch.zeros_like(labels)).long().unsqueeze(1)
+    w = weight.to(device=x.device, dtype=x.dtype)
+    m = x.max(dim=1, keepdim=True).values
+    e = torch.exp(x - m)
+    S = e.sum(dim=1, keepdim=True)
+    hot = torch.zeros_like(x, dtype=torch.bool).scatter_(1, y, True)
+    wy = w[y.squeeze(1)].unsqueeze(1)
+    xy = x.gather(1, y)
+    l = wy * ((m - xy) + torch.log(S))
+    others = torch.where(hot, torch.zeros_like(e), e).sum(dim=1, keepdim=True)
+    g = wy * torch.where(hot, -(others / S), e / S)
+    zero = torch.zeros((), device=x.device, dtype=x.dtype)
+    on1 = on.unsqueeze(1)
+    W = torch.where(on1, wy, zero).sum()
+    d = W.clamp(min=torch.finfo(torch.float32).tiny)
+    live = (W > 0).to(x.dtype)
+    return torch.where(on1, l, zero).sum() / d * live, torch.where(on1, g, zero) / d * live
+
+
+class _SoftmaxCeTorch(torch.autograd.Function):
+    """The exclusive-class loss where the kernel does not apply (CPU, strided logits, other dtypes): softmax_ce_terms
+    in fp32 (fp64 logits: in fp64), the gradient kept in the logits' type."""
+
+    @staticmethod
+    def forward(ctx, x, labels, valid, weight):
+        xd = x.detach()
+        loss, g = softmax_ce_terms(xd if xd.dtype == torch.float64 else xd.float(), labels, valid, weight)
+        ctx.save_for_backward(g.to(x.dtype))
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return (grad.to(g.dtype if g.dtype == torch.float64 else torch.float32) * g).to(grad.dtype), None, None, None
+
+
+class _SoftmaxCe(torch.autograd.Function):
+    """``lss_softmax_ce``: loss, stored gradient (dl/dx / n_cells) and the device scalar n_cells / W in two launches;
+    the backward is ``lss_seg_loss_masked_bwd`` over the batch * C * plane gradient elements."""
+
+    @staticmethod
+    def forward(ctx, x, labels, valid, weight):
+        from . import _lib
+        lib = _lib.load()
+        batch, C = x.shape[0], x.shape[1]
+        plane = x.numel() // (batch * C)
+        partial = torch.empty(int(lib.lss_softmax_ce_partials(batch * plane)), device=x.device, dtype=torch.float32)
+        loss = torch.empty((), device=x.device, dtype=torch.float32)
+        scale = torch.empty((), device=x.device, dtype=torch.float32)
+        grad = torch.empty_like(x)
+        _lib.check(lib.lss_softmax_ce(_lib.ptr(x), _lib.dtype_code(x.dtype), _lib.ptr(labels), _lib.ptr(valid), batch,
+                                      plane, C, _lib.ptr(weight), _lib.ptr(partial), _lib.ptr(loss), _lib.ptr(scale),
+                                      _lib.ptr(grad), _lib.stream_handle(x.device)), "lss_softmax_ce")
+        ctx.save_for_backward(grad, scale)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        dx, _, _, _ = _SegLossMasked.backward(ctx, g)
+        return dx, None, None, None
+
+
+def softmax_ce_arm(x: torch.Tensor, labels: torch.Tensor, valid=None, grad=None) -> int:
+    """``lss_softmax_ce_arm``: 0 (one cell per thread) or 1 (8 cells per thread, vector loads) for a call on these
+    tensors. grad None: the fresh allocation SoftmaxLoss makes (16-B aligned, so x's own address stands in)."""
+    from . import _lib
+    batch, C = x.shape[0], x.shape[1]
+    arm = _lib.load().lss_softmax_ce_arm(_lib.ptr(x), _lib.dtype_code(x.dtype), _lib.ptr(labels), _lib.ptr(valid), batch,
+                                         x.numel() // (batch * C), C, _lib.ptr(x if grad is None else grad))
+    if arm < 0:
+        raise RuntimeError(f"lss_softmax_ce_arm refuses logits {tuple(x.shape)} {x.dtype}")
+    return arm
+
+
+class SoftmaxLoss(torch.nn.Module):
+    """Softmax cross-entropy over exclusive classes: ``F.cross_entropy(logits, labels, weight=w, ignore_index=255,
+    reduction="mean")`` for (N, C, H, W) logits and an (N, H, W) uint8 class map (simbev.class_index; every value
+    >= C is ignored, 255 by convention), with an optional uint8 valid-cell mask. ``class_weight``: the C fp32 class
+    weights, a device buffer the kernel reads -- changed in place, a captured step follows. On the GPU under
+    SimpleLoss's conditions (fp32 or bf16 contiguous logits, contiguous uint8 labels and mask on their device) loss
+    and gradient come from ``lss_softmax_ce``, computed in fp32; otherwise from the same definition in torch
+    (softmax_ce_terms). Drops in wherever SimpleLoss / FocalLoss do; ``exclusive`` marks the label format."""
+
+    computes_in_fp32 = True
+    exclusive = True
+
+    def __init__(self, classes: int, weight=None):
+        super().__init__()
+        C = int(classes)
+        if not 2 <= C <= MAX_CLASSES:
+            raise ValueError(f"SoftmaxLoss: {classes!r} classes (2..{MAX_CLASSES}: the background and 1..7 groups)")
+        w = [1.0] * C if weight is None else [float(v) for v in (weight.tolist() if torch.is_tensor(weight) else weight)]
+        if len(w) != C or any(not (v >= 0.0 and v < float("inf")) for v in w):
+            raise ValueError(f"SoftmaxLoss: class weights {w!r}: {C} finite numbers >= 0")
+        self.classes = C
+        self.register_buffer("class_weight", torch.tensor(w, dtype=torch.float32), persistent=False)
+
+    def forward(self, ypred, ytgt, valid=None):
+        C, w = self.classes, self.class_weight
+        _check_class_map(ypred, ytgt, valid, C, "SoftmaxLoss")
+        if (USE_HIP_SOFTMAX and ypred.is_cuda and ypred.dtype in (torch.float32, torch.bfloat16)
+                and ytgt.device == ypred.device and ypred.is_contiguous() and ytgt.is_contiguous()
+                and ypred.numel() > 0 and w.device == ypred.device and w.dtype == torch.float32 and w.is_contiguous()
+                and (valid is None or (valid.dtype == torch.uint8 and valid.device == ypred.device
+                                       and valid.is_contiguous()))):
+            return _SoftmaxCe.apply(ypred, ytgt, valid, w)
+        return _SoftmaxCeTorch.apply(ypred, ytgt, valid, w)
+
+
+def argmax_classes(preds: torch.Tensor, out=None) -> torch.Tensor:
+    """The (N, H, W) uint8 class map of (N, C, H, W) device logits, ``lss_argmax_classes``: argmax over the classes
+    compared in fp32 with a strict > from class 0 up (ties to the lowest class, a NaN never wins, all-NaN gives 0)."""
+    from . import _lib
+    if not (preds.is_cuda and preds.dim() >= 2 and 2 <= preds.shape[1] <= MAX_CLASSES and preds.numel() > 0):
+        raise RuntimeError(f"argmax_classes: device logits (N, 2..{MAX_CLASSES}, ...), got {tuple(preds.shape)} on "
+                           f"{preds.device}")
+    x = preds.detach().contiguous()
+    batch, C = x.shape[0], x.shape[1]
+    cells = (batch,) + tuple(x.shape[2:])
+    if out is None:
+        out = torch.empty(cells, device=x.device, dtype=torch.uint8)
+    elif not (out.device == x.device and out.dtype == torch.uint8 and out.is_contiguous()
+              and out.numel() * C == x.numel()):
+        raise RuntimeError(f"argmax_classes: out= must be a contiguous uint8 device tensor of {cells}")
+    _lib.check(_lib.load().lss_argmax_classes(_lib.ptr(x), _lib.dtype_code(x.dtype), batch, x.numel() // (batch * C), C,
+                                              _lib.ptr(out), _lib.stream_handle(x.device)), "lss_argmax_classes")
+    return out
+
+
+def argmax_classes_host(x) -> "numpy.ndarray":
+    """argmax_classes' rule on the host for (N, C, ...) logits (a tensor or an array), as uint8."""
+    import numpy as np
+    a = np.asarray(x.detach().float().cpu() if torch.is_tensor(x) else x, dtype=np.float32)
+    best = np.zeros((a.shape[0],) + a.shape[2:], dtype=np.uint8)
+    bv = np.full(best.shape, -np.inf, dtype=np.float32)
+    for c in range(a.shape[1]):
+        with np.errstate(invalid="ignore"):
+            gt = a[:, c] > bv
+        best[gt] = c
+        bv = np.where(gt, a[:, c], bv)
+    return best
+
+
+def confusion_accumulate(preds: torch.Tensor, labels: torch.Tensor, totals: torch.Tensor, n_valid, weight: torch.Tensor,
+                         valid=None) -> torch.Tensor:
+    """One validation batch of exclusive classes into its accumulators, ``lss_confusion_accum``: totals (1 + C C
+    float64 on the device) += the batch's mean loss times the samples counted, then the confusion counts
+    conf[y][pred] over the counted cells (label < C, mask != 0) of the first ``n_valid`` samples (one int32 on the
+    device; None: all). preds (N, C, H, W) fp32 or bf16, labels (N, H, W) uint8, weight the C fp32 class weights
+    (SoftmaxLoss.class_weight), valid an optional (N, H, W) uint8 mask. Device tensors only; two launches, no host
+    synchronisation, capturable (the scratch is kept per device and size, as val_accumulate's)."""
+    from . import _lib
+    if not (preds.is_cuda and all(v.device == preds.device for v in (labels, totals, weight))):
+        raise RuntimeError("confusion_accumulate: device tensors only (no CPU fallback)")
+    C = preds.shape[1] if preds.dim() >= 2 else 0
+    if not 2 <= C <= MAX_CLASSES or preds.numel() == 0:
+        raise RuntimeError(f"confusion_accumulate: logits (N, 2..{MAX_CLASSES}, ...), got {tuple(preds.shape)}")
+    _check_class_map(preds, labels, valid, C, "confusion_accumulate")
+    if (totals.dtype != torch.float64 or totals.numel() != 1 + C * C or not totals.is_contiguous()
+            or weight.dtype != torch.float32 or weight.numel() != C or not weight.is_contiguous()):
+        raise RuntimeError(f"confusion_accumulate: totals {tuple(totals.shape)} {totals.dtype} (1 + {C * C} float64), "
+                           f"weight {tuple(weight.shape)} {weight.dtype} ({C} float32)")
+    if n_valid is not None and not (n_valid.device == preds.device and n_valid.dtype == torch.int32
+                                    and n_valid.numel() == 1):
+        raise RuntimeError("confusion_accumulate: n_valid must be one int32 on the logits' device")
+    if valid is not None and not (valid.device == preds.device and valid.dtype == torch.uint8 and valid.is_contiguous()):
+        raise RuntimeError("confusion_accumulate: valid must be a contiguous uint8 mask on the logits' device")
+    lib = _lib.load()
+    x, t = preds.detach().contiguous(), labels.contiguous()
+    batch = x.shape[0]
+    plane = x.numel() // (batch * C)
+    nbytes = int(lib.lss_confusion_partial_bytes(batch * plane, C))
+    key = (x.device, "confusion", nbytes)
+    partial = _VAL_PARTIAL.get(key)
+    if partial is None:  # (an odd C's histogram ends on a 4-byte boundary: rounded up to whole doubles)
+        partial = _VAL_PARTIAL[key] = torch.empty((nbytes + 7) // 8, device=x.device, dtype=torch.float64)
+    _lib.check(lib.lss_confusion_accum(_lib.ptr(x), _lib.dtype_code(x.dtype), _lib.ptr(t), _lib.ptr(valid), batch, plane,
+                                       C, _lib.ptr(n_valid), _lib.ptr(weight), _lib.ptr(totals), _lib.ptr(partial),
+                                       _lib.stream_handle(x.device)), "lss_confusion_accum")
+    return totals
+
+
+def confusion_summary(totals, C: int, n_samples, cells=None) -> dict:
+    """The totals of ``lss_confusion_accum`` (a sequence or a tensor of 1 + C C numbers) as a report:
+    "loss" (the total over n_samples), "confusion" (C lists of C ints, conf[y][pred]), "iou_per_class" (TP / (TP + FP
+    + FN), None for an empty union), "iou" (the mean over the foreground classes 1..C-1 that were seen -- the number
+    a best checkpoint is chosen by, comparable with the sigmoid mode's), "miou_all" (the background included),
+    "pixel_acc", "precision_per_class" and "recall_per_class". cells: the number of cells the counted ones are a
+    fraction of (samples x plane, with a mask in use) -- adds "valid_fraction". Never raises for counts of any value:
+    what cannot be computed is None."""
+    C = int(C)
+    t = [float(v) for v in (totals.tolist() if torch.is_tensor(totals) else totals)]
+    t += [0.0] * max(0, 1 + C * C - len(t))
+    conf = [[int(t[1 + y * C + p]) for p in range(C)] for y in range(C)]
+    tp = [conf[c][c] for c in range(C)]
+    row = [sum(conf[c]) for c in range(C)]                          # cells labelled c: TP + FN
+    col = [sum(conf[y][c] for y in range(C)) for c in range(C)]     # cells predicted c: TP + FP
+    per = [tp[c] / (row[c] + col[c] - tp[c]) if row[c] + col[c] - tp[c] > 0 else None for c in range(C)]
+    fg = [v for v in per[1:] if v is not None]
+    seen = [v for v in per if v is not None]
+    total = sum(row)
+    info = {"loss": t[0] / n_samples if n_samples else None,
+            "iou": sum(fg) / len(fg) if fg else None,
+            "iou_per_class": per,
+            "miou_all": sum(seen) / len(seen) if seen else None,
+            "pixel_acc": sum(tp) / total if total > 0 else None,
+            "precision_per_class": [tp[c] / col[c] if col[c] > 0 else None for c in range(C)],
+            "recall_per_class": [tp[c] / row[c] if row[c] > 0 else None for c in range(C)],
+            "confusion": conf}
+    if cells is not None:
+        info["valid_fraction"] = total / cells if cells else None
+    return info
+
+
 def val_totals(model, loader, loss_fn, device):
     """The device accumulators of get_val_info: (sum of loss x batch size, intersection, union) as
     float64 device tensors; nothing in the loop synchronises the host. The counts

@@ -258,7 +258,27 @@ class EvalStep:
         valid: the static (B, X, Y) uint8 valid-cell mask (e.g. ``BatchStager.valid``): the step always accumulates
         through the seg-metrics path (the 0.5 column present), masked -- ``lss_seg_metrics_accum_masked`` -- so the loss
         and every IoU are over valid cells, and ``read()`` adds ``valid_fraction``: valid cells / cells, over the
-        samples counted. inverses: as TrainStep's -- installed as ``model.static_inverses`` around the forward."""
+        samples counted. inverses: as TrainStep's -- installed as ``model.static_inverses`` around the forward.
+        loss a tools.SoftmaxLoss (``exclusive``): labels is the (B, X, Y) uint8 class map and the step accumulates
+        through ``tools.confusion_accumulate`` (``lss_confusion_accum``) into 1 + C C totals with the loss's
+        ``class_weight`` buffer, masked when valid is given; ``read()`` returns ``tools.confusion_summary``'s dict.
+        thresholds= with such a loss is a ValueError: an argmax has no threshold."""
+        self.exclusive = bool(getattr(loss, "exclusive", False))
+        if self.exclusive:
+            if thresholds is not None:
+                raise ValueError("EvalStep: thresholds= with an exclusive loss (the prediction is an argmax)")
+            self.model, self.forward, self.inputs, self.labels = model, forward, tuple(inputs), labels
+            self.inverses = None if inverses is None else tuple(inverses)
+            self.n_samples, self.n_valid, self.amp_dtype = n_samples, n_valid, amp_dtype
+            self.classes = int(loss.classes)
+            w = loss.class_weight
+            self.class_weight = w if w.device == labels.device else w.to(labels.device)
+            self.totals = torch.zeros(1 + self.classes ** 2, device=labels.device, dtype=torch.float64)
+            self.ladder = self.columns = self.params = self.thetas = self.valid_cells = None
+            self.valid = valid
+            self.graph = None
+            self.static_preds = None
+            return
         self.model, self.forward, self.inputs, self.labels = model, forward, tuple(inputs), labels
         self.inverses = None if inverses is None else tuple(inverses)
         self.n_samples = n_samples  # len(valloader.dataset): what read() divides the loss total by
@@ -311,7 +331,10 @@ class EvalStep:
                                     enabled=self.amp_dtype is not None, cache_enabled=not capturing):
                     preds = _with_inverses(self.model, self.inverses, self.forward, self.inputs)
                 self.static_preds = preds
-                if self.columns is None:
+                if self.exclusive:
+                    tools.confusion_accumulate(preds, self.labels, self.totals, self.n_valid, self.class_weight,
+                                               valid=self.valid)
+                elif self.columns is None:
                     tools.val_accumulate(preds, self.labels, self.totals, n_valid=self.n_valid,
                                          pos_weight=self.pos_weight)
                 else:
@@ -358,6 +381,9 @@ class EvalStep:
         t = self.totals.tolist()
         K = self.classes
         n = self.n_samples if n_samples is None else n_samples
+        if self.exclusive:  # (valid_fraction: counted cells over the cells of the samples counted, with a mask)
+            cells = None if self.valid is None or not n else n * (self.valid.numel() // self.valid.shape[0])
+            return tools.confusion_summary(t, K, n, cells=cells)
         if self.columns is None:
             return {"loss": t[0] / n, **tools.iou_summary(t[1:1 + K], t[1 + K:1 + 2 * K])}
         # the ladder's totals: intersection = TP, union = PP + P - TP, at the 0.5 column for today's keys

@@ -133,6 +133,12 @@ def parse_per_class(text, name="value"):
     return vals[0] if len(vals) == 1 else vals
 
 
+def _weights_list(text, name="--class_weight") -> list:
+    """``--class_weight 0.5,1,2`` -> [0.5, 1.0, 2.0]: always a list, one weight per class."""
+    v = parse_per_class(text, name)
+    return [v] if isinstance(v, float) else v
+
+
 def parse_pair(text, name="value"):
     """``--bev_rot_lim -22.5,22.5`` -> (-22.5, 22.5): the two ends of a range, as the loader's *_lim keys."""
     items = [v.strip() for v in str(text).split(",") if v.strip()]
@@ -219,6 +225,32 @@ def _class_setup(label_groups, pos_weight):
     return groups, K, pos_weight
 
 
+EXCLUSIVE_KEYS = ("iou_per_class", "miou_all", "pixel_acc", "precision_per_class", "recall_per_class", "confusion")
+
+
+def _exclusive_setup(label_groups, class_weight, pos_weight=None, loss="bce", focal_gamma=2.0, focal_alpha=None,
+                     iou_thresholds=None) -> list:
+    """The C = K + 1 class weights of an exclusive run (default all 1), after its argument errors: exclusive classes
+    need 1..7 label_groups, and the sigmoid mode's options -- pos_weight, the focal loss and its parameters, a
+    threshold ladder -- do not apply to a softmax over the classes (ValueError, before anything is built)."""
+    from . import simbev
+    if label_groups is None:
+        raise ValueError("exclusive classes need label_groups (class 0 is the background, class k + 1 is group k)")
+    simbev.exclusive_bits(label_groups)
+    for given, name in ((pos_weight is not None, "pos_weight"), (loss != "bce", "loss=focal"),
+                        (focal_alpha is not None, "focal_alpha"),
+                        (not (isinstance(focal_gamma, (int, float)) and float(focal_gamma) == 2.0), "focal_gamma"),
+                        (iou_thresholds is not None, "iou_thresholds")):
+        if given:
+            raise ValueError(f"{name} does not apply to exclusive classes (softmax cross-entropy with class_weight; "
+                             "the prediction is an argmax)")
+    C = len(label_groups) + 1
+    w = [1.0] * C if class_weight is None else [float(v) for v in class_weight]
+    if len(w) != C or any(not (0.0 <= v < float("inf")) for v in w):
+        raise ValueError(f"class_weight {class_weight!r}: {C} finite weights >= 0 (the background, then one per group)")
+    return w
+
+
 def _check_ncams(ncams) -> int:
     """The reference's ``Ncams``: an integer from 1 to the rig's six cameras, else ValueError."""
     from . import simbev
@@ -231,7 +263,7 @@ def _check_ncams(ncams) -> int:
 def build_step(grid_conf, data_aug_conf, bsz, device, *, dtype="bf16", lr=1e-3, weight_decay=1e-7,
                max_grad_norm=5.0, pos_weight=2.13, skip_nonfinite=True, n_val=None, label_groups=None,
                loss="bce", focal_gamma=2.0, focal_alpha=None, iou_thresholds=None, lr_schedule=None,
-               ema_decay=0.0, ema_warmup=True, ncams=6) -> dict:
+               ema_decay=0.0, ema_warmup=True, ncams=6, exclusive=False, class_weight=None) -> dict:
     """The model and its steps as bench.py's train branch builds them -- unused parameters frozen, one flat
     fp32 master per backward group, fused capturable Adam, TrainStep without a pre_step (the stager's
     commit stages the inverses) -- plus the stager and the EvalStep over the same static tensors. Nothing is
@@ -250,7 +282,11 @@ def build_step(grid_conf, data_aug_conf, bsz, device, *, dtype="bf16", lr=1e-3, 
     and the EvalStep over a second stager of N = 6 (``"val_stager"``), each step with its own labels, ``n_valid``, valid
     mask and HostInverses, which it installs as ``model.static_inverses`` around its own forward. With "fov" each
     stager's mask comes from the cameras its batch holds: a cell only a dropped camera would see is invalid in that
-    training sample. At 6, ``"val_stager"`` is ``"stager"`` and nothing is allocated or launched differently."""
+    training sample. At 6, ``"val_stager"`` is ``"stager"`` and nothing is allocated or launched differently.
+    exclusive: the K label_groups are painted into one (B, X, Y) uint8 class map (simbev.class_index: 0 the
+    background, k + 1 group k, a later group wins), the model has outC = K + 1, the loss is
+    tools.SoftmaxLoss(K + 1, class_weight) and the EvalStep accumulates a confusion matrix; pos_weight, loss and
+    iou_thresholds are not used."""
     import lss_carla_amd as L
     from . import parallel, simbev, tools
     from .flat_params import FlatParamGroups, lss_backward_groups
@@ -260,6 +296,10 @@ def build_step(grid_conf, data_aug_conf, bsz, device, *, dtype="bf16", lr=1e-3, 
     ncams, n_all = _check_ncams(ncams), len(simbev.CAMERA_ORDER)  # (before anything is built)
     amp_dtype = torch.bfloat16 if dtype == "bf16" else None
     label_groups, outC, pos_weight = _class_setup(label_groups, pos_weight)
+    excl_args = {}
+    if exclusive:
+        class_weight = _exclusive_setup(label_groups, class_weight)
+        outC, excl_args = outC + 1, {"exclusive": True}
     model = L.compile_model(grid_conf, data_aug_conf, outC=outC).to(device)
     model.bevencode.to(memory_format=torch.channels_last)
     model.camencode.up1.to(memory_format=torch.channels_last)
@@ -272,20 +312,22 @@ def build_step(grid_conf, data_aug_conf, bsz, device, *, dtype="bf16", lr=1e-3, 
     mask_args = {} if mask_mode is None else {"valid_mask": mask_mode, "fov_z": simbev.fov_heights(data_aug_conf)}
     stager = BatchStager(data_aug_conf["final_dim"], bsz, ncams,
                          (data_aug_conf["H"], data_aug_conf["W"]), grid_conf, device, label_groups=label_groups,
-                         bev_aug=simbev.bev_aug_enabled(data_aug_conf), **mask_args)
+                         bev_aug=simbev.bev_aug_enabled(data_aug_conf), **mask_args, **excl_args)
     step_mask = {} if mask_mode is None else {"valid": stager.valid}
     val_stager, val_mask, step_inv, val_inv = stager, step_mask, {}, {}
     if ncams < n_all:  # validation at every camera: static tensors of its own
         val_stager = BatchStager(data_aug_conf["final_dim"], bsz, n_all, (data_aug_conf["H"], data_aug_conf["W"]),
                                  grid_conf, device, label_groups=label_groups,
-                                 bev_aug=simbev.bev_aug_enabled(data_aug_conf), **mask_args)
+                                 bev_aug=simbev.bev_aug_enabled(data_aug_conf), **mask_args, **excl_args)
         val_mask = {} if mask_mode is None else {"valid": val_stager.valid}
         step_inv = {"inverses": (stager.hinv.pinv, stager.hinv.kinv), "model": model}
         val_inv = {"inverses": (val_stager.hinv.pinv, val_stager.hinv.kinv)}
     model.static_inverses = (stager.hinv.pinv, stager.hinv.kinv)  # staged by the stager's commit
     if loss not in ("bce", "focal"):
         raise ValueError(f"loss {loss!r}: bce or focal")
-    if loss == "focal":
+    if exclusive:
+        loss_fn = tools.SoftmaxLoss(outC, class_weight).to(device)
+    elif loss == "focal":
         loss_fn = tools.FocalLoss(outC, gamma=focal_gamma, alpha=focal_alpha,
                                   pos_weight=None if focal_alpha is not None else pos_weight).to(device)
     else:
@@ -301,7 +343,8 @@ def build_step(grid_conf, data_aug_conf, bsz, device, *, dtype="bf16", lr=1e-3, 
                      **step_mask, **step_inv)
     evaluate = EvalStep(model, forward_eval, val_stager.inputs, val_stager.binimgs, n_valid=val_stager.n_valid,
                         pos_weight=pos_weight, amp_dtype=amp_dtype, n_samples=n_val,
-                        loss=loss_fn if loss == "focal" else None, thresholds=iou_thresholds, **val_mask, **val_inv)
+                        loss=loss_fn if (loss == "focal" or exclusive) else None, thresholds=iou_thresholds,
+                        **val_mask, **val_inv)
     return {"model": model, "flat": flat, "masters": masters, "opt": opt, "stager": stager, "val_stager": val_stager,
             "step": step,
             "evaluate": evaluate, "loss_fn": loss_fn, "forward": forward, "label_groups": label_groups,
@@ -366,6 +409,8 @@ def train(
     bev_flip=False,
     valid_mask=None,
     fov_z=(0.0,),
+    exclusive=False,
+    class_weight=None,
 ):
     """Train LiftSplatShoot on a SimBEV tree; the reference's arguments (train_simbev.py:23-98) plus:
 
@@ -409,13 +454,30 @@ def train(
     docstring); validation always runs at six. With valid_mask "fov" a training sample's mask comes from the cameras
     it holds, so a cell only a dropped camera would see is invalid in that sample. Checkpoints do not depend on it: a
     run resumes at any ncams.
+    exclusive: every cell has exactly one class -- 0 the background, k + 1 label group k, the groups painted in order
+    so that a later group wins (needs label_groups, 1 to 7 groups). The labels are the (B, X, Y) uint8 class map
+    (simbev.class_index on the staging stream), the model has outC = K + 1, the loss is tools.SoftmaxLoss with
+    class_weight (K + 1 weights, default all 1) and the metrics come from a confusion matrix (``lss_confusion_accum``):
+    ``val`` and ``train_iou`` events carry tools.confusion_summary's keys, ``iou`` is the mean IoU of the foreground
+    classes seen (None when there is none: such a validation never replaces the best). pos_weight, loss="focal",
+    focal_gamma / focal_alpha and iou_thresholds with it raise ValueError before anything is built. The ``config``
+    event records ``exclusive`` and ``class_weight``. Works with the BEV-space augmentation, the valid-cell mask,
+    ncams, the schedules, the EMA and resume as the sigmoid mode does.
     Returns a summary dict (counter, epoch, best_val_iou, skipped, frames_per_s of the training steps)."""
     from . import checkpoint, simbev, tools
 
     ncams = _check_ncams(ncams)
+    exclusive = bool(exclusive)
+    if exclusive:
+        class_weight = _exclusive_setup(label_groups, class_weight, pos_weight, loss, focal_gamma, focal_alpha,
+                                        parse_thresholds(iou_thresholds))
+    elif class_weight is not None:
+        raise ValueError("class_weight is the exclusive loss's: it needs exclusive=True")
     pos_weight, focal = _loss_setup(loss, pos_weight, focal_gamma, focal_alpha)
     iou_thresholds = parse_thresholds(iou_thresholds)
     label_groups, n_out, pos_weight = _class_setup(label_groups, pos_weight)
+    if exclusive:
+        n_out += 1  # the background
     if focal is not None:
         tools.focal_rows(n_out, **focal)  # (argument errors come before anything is looked for or built)
     sched_on = _schedule_setup(lr, lr_schedule, warmup_steps, warmup_factor, lr_min, lr_total_steps, ema_decay)
@@ -462,9 +524,11 @@ def train(
         config.update({k: list(v) if isinstance(v, tuple) else v for k, v in bev_aug_conf.items()})
     if mask_mode is not None:
         config.update({"valid_mask": mask_mode, "fov_z": list(mask_conf["fov_z"])})
+    if exclusive:
+        config.update({"exclusive": True, "class_weight": class_weight, "pos_weight": None})
     log = _Log(logdir, use_wandb, {"project": wandb_project, "name": wandb_name, "entity": wandb_entity}, config)
 
-    if ("loss" in config or bev_on or mask_mode is not None) and not (sched_on or ema_on):
+    if ("loss" in config or bev_on or mask_mode is not None or exclusive) and not (sched_on or ema_on):
         log.event("config", 0, **config)
 
     device = torch.device(f"cuda:{gpuid}")
@@ -495,7 +559,8 @@ def train(
                      max_grad_norm=max_grad_norm, pos_weight=pos_weight, skip_nonfinite=skip_nonfinite,
                      n_val=n_val, label_groups=label_groups, loss=loss, focal_gamma=focal_gamma,
                      focal_alpha=focal_alpha, iou_thresholds=iou_thresholds, lr_schedule=schedule,
-                     ema_decay=float(ema_decay), ema_warmup=ema_warmup, ncams=ncams)
+                     ema_decay=float(ema_decay), ema_warmup=ema_warmup, ncams=ncams,
+                     **({"exclusive": True, "class_weight": class_weight} if exclusive else {}))
     emas = ctx["emas"]
     model, flat, masters, opt = ctx["model"], ctx["flat"], ctx["masters"], ctx["opt"]
     stager, step, evaluate = ctx["stager"], ctx["step"], ctx["evaluate"]
@@ -593,11 +658,20 @@ def train(
             if counter % iou_step == 0:
                 extra = {}
                 iou_pred, iou_tgt = step.static_preds, stager.binimgs
-                if mask_mode is not None:  # valid cells only: masked-out cells are neither predicted nor labelled
+                if exclusive:  # the batch's confusion matrix, on the tensors the sigmoid path reads
+                    tot = torch.zeros(1 + n_out * n_out, device=device, dtype=torch.float64)
+                    tools.confusion_accumulate(iou_pred, iou_tgt, tot, None, ctx["loss_fn"].class_weight,
+                                               valid=stager.valid if mask_mode is not None else None)
+                    binfo = tools.confusion_summary(tot, n_out, bsz)
+                    iou = binfo["iou"]
+                    extra = {k: binfo[k] for k in EXCLUSIVE_KEYS}
+                elif mask_mode is not None:  # valid cells only: masked-out cells are neither predicted nor labelled
                     on = (stager.valid != 0).unsqueeze(1)
                     iou_pred = torch.where(on, iou_pred.float(), torch.full((), -1.0, device=device))
                     iou_tgt = torch.where(on, iou_tgt, torch.zeros((), device=device))
-                if n_out > 1:
+                if exclusive:
+                    pass
+                elif n_out > 1:
                     ci, cu = tools.get_batch_iou_per_class(iou_pred, iou_tgt)
                     ci, cu = ci.tolist(), cu.tolist()
                     extra["iou_per_class"] = [i / u if u > 0 else None for i, u in zip(ci, cu)]
@@ -612,8 +686,11 @@ def train(
                 t_train += time.perf_counter() - t_mark
             if will_val:
                 info = validate()
-                print(f"  Validation at {counter} - Loss: {info['loss']:.4f}, IoU: {info['iou']:.4f}")
+                print(f"  Validation at {counter} - Loss: {info['loss']:.4f}, IoU: "
+                      + ("none" if info["iou"] is None else f"{info['iou']:.4f}"))
                 extra = {"iou_per_class": info["iou_per_class"]} if n_out > 1 else {}
+                if exclusive:
+                    extra = {k: info[k] for k in EXCLUSIVE_KEYS}
                 if iou_thresholds is not None:
                     extra.update({k: info[k] for k in ("iou_max", "iou_max_per_class", "best_threshold_per_class")})
                 if ema_on:
@@ -621,7 +698,7 @@ def train(
                 if mask_mode is not None:
                     extra["valid_fraction"] = info["valid_fraction"]
                 log.event("val", counter, epoch=epoch, loss=info["loss"], iou=info["iou"], **extra)
-                if info["iou"] > best_val_iou:
+                if info["iou"] is not None and info["iou"] > best_val_iou:
                     best_val_iou = info["iou"]
                     save(os.path.join(logdir, "model_best.pt"), epoch, best_val_iou)
             if counter % save_step == 0:
@@ -725,7 +802,21 @@ def main(argv=None):
                         "augmentation (grid), and seen by a camera (fov)")
     p.add_argument("--fov_z", type=str, default="0.0",
                    help="--valid_mask fov: the heights (metres) a cell is tested at, 1 to 8: 0.0[,1.5,...]")
+    p.add_argument("--exclusive", type=int, default=0, choices=[0, 1],
+                   help="1: exclusive classes -- the label groups painted in order into one class map (0 the background), "
+                        "softmax cross-entropy, confusion-matrix mIoU; needs --label_groups")
+    p.add_argument("--class_weight", type=str, default=None,
+                   help="--exclusive 1: one weight per class, the background first: w0,...,wK (default all 1)")
     a = p.parse_args(argv)
+    if a.exclusive:  # the sigmoid mode's flags are errors here, before anything is built
+        _exclusive_setup(parse_label_groups(a.label_groups),
+                         None if a.class_weight is None else _weights_list(a.class_weight),
+                         None if a.pos_weight is None else parse_pos_weight(a.pos_weight), a.loss,
+                         parse_per_class(a.focal_gamma, "--focal_gamma"),
+                         None if a.focal_alpha is None else parse_per_class(a.focal_alpha, "--focal_alpha"),
+                         parse_thresholds(a.iou_thresholds))
+    elif a.class_weight is not None:
+        raise ValueError("--class_weight needs --exclusive 1")
     return train(dataroot=a.dataroot, nepochs=a.nepochs, gpuid=a.gpuid, H=a.H, W=a.W, final_dim=(a.final_h, a.final_w),
                  ncams=a.ncams, bsz=a.bsz, nworkers=a.nworkers, lr=a.lr, weight_decay=a.weight_decay, logdir=a.logdir,
                  val_step=a.val_step, save_step=a.save_step, resume=a.resume, use_wandb=a.use_wandb,
@@ -734,7 +825,7 @@ def main(argv=None):
                  max_steps=a.max_steps, skip_nonfinite=bool(a.skip_nonfinite),
                  label_groups=parse_label_groups(a.label_groups),
                  pos_weight=parse_pos_weight(a.pos_weight) if a.pos_weight is not None
-                 else (None if a.loss == "focal" else 2.13), loss=a.loss,
+                 else (None if a.loss == "focal" or a.exclusive else 2.13), loss=a.loss,
                  focal_gamma=parse_per_class(a.focal_gamma, "--focal_gamma"),
                  focal_alpha=None if a.focal_alpha is None else parse_per_class(a.focal_alpha, "--focal_alpha"),
                  iou_thresholds=parse_thresholds(a.iou_thresholds), lr_schedule=a.lr_schedule,
@@ -742,7 +833,9 @@ def main(argv=None):
                  lr_total_steps=a.lr_total_steps, ema_decay=a.ema_decay, ema_warmup=bool(a.ema_warmup),
                  bev_rot_lim=parse_pair(a.bev_rot_lim, "--bev_rot_lim"),
                  bev_scale_lim=parse_pair(a.bev_scale_lim, "--bev_scale_lim"), bev_flip=bool(a.bev_flip),
-                 valid_mask=a.valid_mask, fov_z=parse_heights(a.fov_z))
+                 valid_mask=a.valid_mask, fov_z=parse_heights(a.fov_z),
+                 **({"exclusive": True, "class_weight": None if a.class_weight is None else _weights_list(a.class_weight)}
+                    if a.exclusive else {}))
 
 
 if __name__ == "__main__":

@@ -11,6 +11,8 @@ train_loop step): one JSON line {"frames_per_s", "steps", "nworkers", "cycle_bat
   python scripts/train_loop.py --dataroot DIR --bev-rot-lim=-22.5,22.5 --bev-scale-lim 0.9,1.1 --bev-flip 1
                                                                                     the BEV-space augmentation
   python scripts/train_loop.py --dataroot DIR --valid-mask fov [--fov-z 0.0,1.5]   the valid-cell mask (none | grid | fov)
+  python scripts/train_loop.py --dataroot DIR --label-groups "0;1,2;3" --exclusive 1 [--class-weight 1,1,2,4]
+                                                                                    exclusive classes (softmax loss)
 """
 from __future__ import annotations
 
@@ -46,6 +48,8 @@ def main():
     ap.add_argument("--valid-mask", default="none", choices=["none", "grid", "fov"], help="trainer --valid_mask")
     ap.add_argument("--fov-z", default="0.0", help="trainer --fov_z")
     ap.add_argument("--ncams", type=int, default=6, help="trainer --ncams: cameras per training sample")
+    ap.add_argument("--exclusive", type=int, default=0, help="trainer --exclusive (needs --label-groups)")
+    ap.add_argument("--class-weight", default="", help="trainer --class_weight: one weight per class, background first")
     a = ap.parse_args()
     from lss_carla_amd import miopen_db
     miopen_db.use_committed()  # before torch starts
@@ -62,17 +66,20 @@ def main():
                             val_step=10 ** 9, save_step=10 ** 9, use_wandb=False, graph=bool(a.graph),
                             miopen_find=bool(a.miopen_find), seed=0, max_steps=a.steps,
                             cycle_batches=a.cycle_batches, label_groups=trainer.parse_label_groups(a.label_groups),
-                            pos_weight=trainer.parse_pos_weight(a.pos_weight), loss=a.loss,
+                            pos_weight=None if a.exclusive else trainer.parse_pos_weight(a.pos_weight), loss=a.loss,
                             focal_gamma=trainer.parse_per_class(a.focal_gamma, "--focal-gamma"),
                             bev_rot_lim=trainer.parse_pair(a.bev_rot_lim, "--bev-rot-lim"),
                             bev_scale_lim=trainer.parse_pair(a.bev_scale_lim, "--bev-scale-lim"),
                             bev_flip=bool(a.bev_flip), valid_mask=a.valid_mask,
-                            fov_z=trainer.parse_heights(a.fov_z), ncams=a.ncams)
+                            fov_z=trainer.parse_heights(a.fov_z), ncams=a.ncams,
+                            **({"exclusive": True, "class_weight": [float(v) for v in a.class_weight.split(",")]
+                                if a.class_weight else None} if a.exclusive else {}))
     print(json.dumps({"frames_per_s": out["frames_per_s"], "steps": out["counter"], "bsz": a.bsz,
                       "nworkers": a.nworkers, "cycle_batches": a.cycle_batches, "graph": a.graph,
                       "skipped": out["skipped"], "loss": out["loss"], "label_groups": a.label_groups or None,
                       "loss_kind": a.loss, "bev_rot_lim": a.bev_rot_lim, "bev_scale_lim": a.bev_scale_lim,
-                      "bev_flip": a.bev_flip, "valid_mask": a.valid_mask, "fov_z": a.fov_z, "ncams": a.ncams}))
+                      "bev_flip": a.bev_flip, "valid_mask": a.valid_mask, "fov_z": a.fov_z, "ncams": a.ncams,
+                      "exclusive": a.exclusive}))
 
 
 if __name__ == "__main__":

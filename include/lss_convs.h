@@ -418,6 +418,9 @@ int lss_bn_fwd(const void* x, const void* residual, int32_t dtype, int32_t layou
  * type dtype; dgamma, dbeta fp32 (nullable). y is the forward output (needed for ReLU). With
  * LSS_CONV_NHWC and a forward WITHOUT a residual, y may be NULL for ReLU: the kernels then recompute
  * it from x and the saved scale / shift exactly as the forward rounded it (one tensor read less).
+ * Swish takes its slope at the pre-activation recomputed from x, scale and shift alone, so the backward of a
+ * forward with LSS_ACT_SWISH AND a residual does not exist: LSS_ACT_SWISH with dresidual != NULL is
+ * LSS_CONV_EINVAL (ABI 35), and a caller that gave such a forward a residual must not call this.
  * coef: (C, 2) fp32 scratch. */
 int lss_bn_bwd(const void* dy, const void* x, const void* y, int32_t dtype, int32_t layout, int32_t N, int32_t C,
                int32_t HW, const float* scale, const float* shift, const float* save_mean, const float* save_rstd,
@@ -472,6 +475,36 @@ int lss_bn_eval(const void* x, const void* residual, int32_t dtype, int32_t layo
  * the normalised map, as src/explore.py:244-246, 317-328 run it. One small launch. */
 int lss_bn_eval_coef(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
                      float eps, int32_t C, float* stats /* (4, C) */, void* stream);
+
+/* Which kernels a batch-norm entry point launches (ABI 35; host only: no HIP call, no allocation -- lss_bn_fwd2,
+ * lss_bn_bwd2 and lss_bn_eval switch on the same rule, so it reports what this build launches). pass: the entry
+ * point; dtype, layout, N, C, HW, act, ngroups as that entry point's (ngroups is not read for LSS_BN_EVAL);
+ * has_sync: whether a sync workspace is passed (lss_bn_fwd / lss_bn_bwd: 0). The rule depends on these alone:
+ * every entry point already refuses pointers off the alignment above. Families:
+ *   LSS_BN_ARM_NHWC       channels-last training: statistics (ngroups blocks), fold, row-walking apply; v = 8,
+ *     launches = 3 (the forward with y = NULL skips the apply: 2)
+ *   LSS_BN_ARM_CLUSTER    NCHW bf16, HW % 8 == 0, a sync workspace, 2 <= ngroups <= 64, N / ngroups >= 2,
+ *     C * ngroups <= 1024 (forward) / 2304 (backward), C <= 4096, and the largest group's 16-B vectors fit 8 per
+ *     thread: one launch, it = 6 (at most 6 vectors per thread) or 8; relu = 1 for the backward's ReLU form
+ *   LSS_BN_ARM_FUSED_REG  NCHW bf16, ngroups = 1, v in {8, 4}, cnt = N * HW / v <= 2048 vectors held in registers:
+ *     (v, it) = (8, 4) cnt <= 1024, (8, 5) cnt <= 1280, (8, 8); (4, 4) cnt <= 1024, (4, 8)
+ *   LSS_BN_ARM_FUSED      NCHW, ngroups = 1, anything else: one launch, v in {8, 4, 1}
+ *   LSS_BN_ARM_TWO_PASS   NCHW, ngroups > 1 and no cluster: statistics + apply, v in {8, 4, 1}
+ *   LSS_BN_ARM_EVAL_NCHW  lss_bn_eval: v as above except fp32 with HW % 8 == 0 takes 4; chunks = pieces of
+ *     1024 vectors a channel is cut into
+ *   LSS_BN_ARM_EVAL_NHWC  lss_bn_eval, channels-last: v = 8
+ * v = elements per vector access (HW % 8 == 0: 8; HW % 4 == 0: 4; else 1); it, relu, chunks are 0 where the
+ * kernel has none; blocks = the grid of the first launch. ngroups may exceed N (NCHW) or N * HW (NHWC): the
+ * groups then left without an image or row publish zero sums, which is defined behaviour (lss_bn_groups never
+ * picks such a count). Returns 0, or LSS_CONV_EINVAL as the entry point would for these arguments. */
+enum { LSS_BN_FWD = 0, LSS_BN_BWD = 1, LSS_BN_EVAL = 2 };
+enum { LSS_BN_ARM_NHWC = 0, LSS_BN_ARM_CLUSTER = 1, LSS_BN_ARM_FUSED_REG = 2, LSS_BN_ARM_FUSED = 3,
+       LSS_BN_ARM_TWO_PASS = 4, LSS_BN_ARM_EVAL_NCHW = 5, LSS_BN_ARM_EVAL_NHWC = 6, LSS_BN_ARM_FAMILIES = 7 };
+typedef struct lss_bn_arm {
+    int32_t family, v, it, relu, launches, chunks, blocks;
+} lss_bn_arm_t;
+int lss_bn_arm(int32_t pass, int32_t dtype, int32_t layout, int32_t N, int32_t C, int32_t HW, int32_t act,
+               int32_t ngroups, int32_t has_sync, lss_bn_arm_t* arm);
 
 /* Bilinear upsampling with align_corners=True (nn.Upsample(mode="bilinear", align_corners=True),
  * src/models.py:19, 109) fused with Up's channel concatenation (torch.cat([x2, x1], 1),

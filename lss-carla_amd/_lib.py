@@ -18,7 +18,7 @@ DEBUG_LIB_PATH = os.path.join(_HERE, "liblss_hip_debug.so")  # LSS_DEBUG=1: devi
 
 F32, BF16 = 0, 1
 NCHW, NHWC = 0, 1
-ABI_VERSION = 34
+ABI_VERSION = 35
 
 
 class Dims(ctypes.Structure):
@@ -32,6 +32,11 @@ class ImgAug(ctypes.Structure):
                 ("rs_h", ctypes.c_int32), ("crop", ctypes.c_int32 * 4), ("flip", ctypes.c_int32),
                 ("rot_mode", ctypes.c_int32), ("affine", ctypes.c_int32 * 6), ("h_off", ctypes.c_int32),
                 ("h_ksize", ctypes.c_int32), ("v_off", ctypes.c_int32), ("v_ksize", ctypes.c_int32)]
+
+
+class BnArm(ctypes.Structure):
+    """lss_bn_arm_t of include/lss_convs.h: the kernels lss_bn_arm reports for a batch-norm entry point."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("family", "v", "it", "relu", "launches", "chunks", "blocks")]
 
 
 class DwArm(ctypes.Structure):
@@ -162,6 +167,7 @@ SIGNATURES = {
     "lss_bn_bwd": (ctypes.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _i32, _i32, _p, _p,
                                   _p, _p, _p, _p, _p]),
     "lss_bn_sync_words": (ctypes.c_int, []),
+    "lss_bn_arm": (ctypes.c_int, [_i32] * 9 + [ctypes.POINTER(BnArm)]),
     "lss_bn_fwd2": (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, ctypes.c_float, ctypes.c_float,
                                    _p, _p, _p, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p]),
     "lss_bn_bwd2": (ctypes.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _i32, _i32, _p, _p,

@@ -1333,9 +1333,7 @@ inline bool bn_ok(const BnGeo& g, int layout) {
 #endif
 
 // register-resident one-group kernels: bf16, V in {8, 4}, at most 8 vectors per thread
-template <typename T> inline bool fused_reg(int V, long cnt) {
-    return std::is_same<T, bf16>::value && (V == 8 || V == 4) && cnt <= 8 * kBlock;
-}
+inline bool fused_reg(bool is_bf16, int V, long cnt) { return is_bf16 && (V == 8 || V == 4) && cnt <= 8 * kBlock; }
 
 inline int vec_nchw(int HW) { return HW % 8 == 0 ? 8 : (HW % 4 == 0 ? 4 : 1); }
 
@@ -1370,8 +1368,10 @@ inline int cluster_it(int G, int V, const BnGeo& g) {
 // at <= 960 blocks 8.5-15.4 vs 11.1-16.9 us. The backward (two tensors read, three written or read
 // again) also wins at 1,536-2,304 blocks of 3-12 images per group (30.6-40.6 vs 32.5-44.7 us), not at
 // one image per group (G = 48 at 64 x 176: 43.9 vs 39.0; forward 768 blocks: 15.5 vs 14.2).
-template <typename T> inline bool cluster_ok(const uint32_t* sync, int G, int V, const BnGeo& g, bool bwd) {
-    if (!LSS_BN_CLUSTER || sync == nullptr || !std::is_same<T, bf16>::value || V != 8) return false;
+// (g.C > kBnSyncMaxC decides nothing on its own today -- C > 4096 with G >= 2 already passes both block
+// limits below -- it is kept as the statement of what the workspace covers)
+inline bool cluster_ok(bool sync, bool is_bf16, int G, int V, const BnGeo& g, bool bwd) {
+    if (!LSS_BN_CLUSTER || !sync || !is_bf16 || V != 8) return false;
     if (G < 2 || G > kBnClusterMaxG || g.C > kBnSyncMaxC) return false;
     const long blocks = (long)g.C * G;
     if (g.N / G < 2 || blocks > (bwd ? 2304 : 1024)) return false;
@@ -1383,6 +1383,66 @@ inline int apply_blocks(const BnGeo& g) {  // grid-stride elementwise passes: up
     const long nv = (long)g.N * g.HW * g.C / 8;
     const long b = (nv + kBlock - 1) / kBlock;
     return (int)(b < 2048 ? b : 2048);
+}
+
+// The one statement of which kernels a batch-norm entry point launches (lss_bn_arm reports it, lss_bn_fwd2 /
+// lss_bn_bwd2 / lss_bn_eval switch on it). LSS_CONV_EINVAL for what every entry point refuses by shape alone.
+inline int bn_arm(int pass, int dtype, int layout, const BnGeo& g, int act, int G, bool sync, lss_bn_arm_t* a) {
+    if (!a || (pass != LSS_BN_FWD && pass != LSS_BN_BWD && pass != LSS_BN_EVAL) || !bn_ok(g, layout))
+        return LSS_CONV_EINVAL;
+    if (dtype != LSS_CONV_F32 && dtype != LSS_CONV_BF16) return LSS_CONV_EINVAL;
+    if (act != LSS_ACT_NONE && act != LSS_ACT_RELU && act != LSS_ACT_SWISH) return LSS_CONV_EINVAL;
+    const bool is_bf16 = dtype == LSS_CONV_BF16;
+    *a = lss_bn_arm_t{};
+    if (pass == LSS_BN_EVAL) {
+        a->launches = 1;
+        if (layout == LSS_CONV_NHWC) {
+            const long rows = (long)g.N * g.HW, per_block = (long)(kBlock / (g.C / 8)) * kEvalU;
+            const long b = (rows + per_block - 1) / per_block;
+            a->family = LSS_BN_ARM_EVAL_NHWC;
+            a->v = 8;
+            a->blocks = (int)(b < kEvalBlocks ? b : kEvalBlocks);
+            return 0;
+        }
+        // bf16 with HW % 8 == 4 and fp32 with HW % 4 == 0: V = 4
+        const int V8 = vec_nchw(g.HW), V = (V8 == 8 && !is_bf16) ? 4 : V8;
+        const long cnt = (long)g.N * (g.HW / V);
+        const long chunks = (cnt + kBlock * kEvalU - 1) / (kBlock * kEvalU), units = (long)g.C * chunks;
+        a->family = LSS_BN_ARM_EVAL_NCHW;
+        a->v = V;
+        a->chunks = (int)chunks;
+        a->blocks = (int)(units < kEvalBlocks ? units : kEvalBlocks);
+        return 0;
+    }
+    if (G <= 0 || (layout == LSS_CONV_NHWC && G > kMaxGroupsNhwc)) return LSS_CONV_EINVAL;
+    const bool bwd = pass == LSS_BN_BWD;
+    if (layout == LSS_CONV_NHWC) {
+        a->family = LSS_BN_ARM_NHWC;
+        a->v = 8;
+        a->launches = 3;
+        a->blocks = G;
+        return 0;
+    }
+    const int V = vec_nchw(g.HW);
+    const long cnt = (long)g.N * (g.HW / V);
+    a->v = V;
+    a->launches = 1;
+    a->blocks = g.C * G;
+    if (cluster_ok(sync, is_bf16, G, V, g, bwd)) {
+        a->family = LSS_BN_ARM_CLUSTER;
+        a->it = cluster_it(G, V, g) <= 6 ? 6 : 8;
+        a->relu = bwd && act == LSS_ACT_RELU;
+    } else if (G == 1 && LSS_BN_FUSED && fused_reg(is_bf16, V, cnt)) {
+        a->family = LSS_BN_ARM_FUSED_REG;
+        if (V == 8) a->it = cnt <= 4 * kBlock ? 4 : (cnt <= 5 * kBlock ? 5 : 8);
+        else a->it = cnt <= 4 * kBlock ? 4 : 8;
+    } else if (G == 1 && LSS_BN_FUSED) {
+        a->family = LSS_BN_ARM_FUSED;
+    } else {
+        a->family = LSS_BN_ARM_TWO_PASS;
+        a->launches = 2;
+    }
+    return 0;
 }
 
 }  // namespace
@@ -1405,6 +1465,11 @@ int lss_bn_groups(int32_t N, int32_t C, int32_t HW, int32_t layout) {
 }
 
 int lss_bn_sync_words(void) { return kBnSyncMaxC * kBnSyncStride + 1; }
+
+int lss_bn_arm(int32_t pass, int32_t dtype, int32_t layout, int32_t N, int32_t C, int32_t HW, int32_t act,
+               int32_t ngroups, int32_t has_sync, lss_bn_arm_t* arm) {
+    return bn_arm(pass, dtype, layout, BnGeo{N, C, HW}, act, ngroups, has_sync != 0, arm);
+}
 
 int lss_bn_fwd(const void* x, const void* residual, int32_t dtype, int32_t layout, int32_t N, int32_t C, int32_t HW,
                const float* gamma, const float* beta, float eps, float momentum, float* running_mean,
@@ -1436,71 +1501,64 @@ int lss_bn_fwd2(const void* x, const void* residual, int32_t dtype, int32_t layo
     hipStream_t s = (hipStream_t)stream;
     const BnParams P{gamma, beta, eps, momentum, running_mean, running_var, save_mean, num_batches_tracked};
     const int G = ngroups;
-#define LSS_BN_FWD(T)                                                                                              \
-    do {                                                                                                           \
-        const T* xx = (const T*)x;                                                                                 \
-        const T* rr = (const T*)residual;                                                                          \
-        T* yy = (T*)y;                                                                                             \
-        if (layout == LSS_CONV_NHWC) {                                                                             \
-            const size_t lds = 2 * C * sizeof(float);                                                              \
-            hipLaunchKernelGGL(k_bn_stats_nhwc<T>, dim3(G), dim3(kBlock), kNhwcStatsLds * C * sizeof(float), s, xx, \
-                               g, G, partial);                                                                     \
-            hipLaunchKernelGGL(k_bn_fold_nhwc<T>, dim3((C + 3) / 4), dim3(kBlock), 0, s, partial, G, xx, g, P);   \
-            if (!yy) {                                                                                             \
-            } else if (LSS_BN_ROWS)                                                                                \
-                hipLaunchKernelGGL(k_bn_apply_rows_nhwc<T>, dim3(apply_blocks(g)), dim3(kBlock), 0, s, xx, rr, g,  \
-                                   save_mean, (int)act, yy);                                                       \
-            else                                                                                                   \
-                hipLaunchKernelGGL(k_bn_apply_nhwc<T>, dim3(apply_blocks(g)), dim3(kBlock), lds, s, xx, rr, g,    \
-                                   save_mean, (int)act, yy);                                                       \
-        } else {                                                                                                   \
-            const int V = vec_nchw(HW);                                                                            \
-            const dim3 gr(C * G), bl(kBlock);                                                                      \
-            const long cnt = (long)N * (HW / V);                                                                   \
-            if (cluster_ok<T>(sync, G, V, g, false)) {                                                             \
-                if (cluster_it(G, V, g) <= 6)                                                                      \
-                    hipLaunchKernelGGL((k_bn_cluster_nchw<8, 6>), gr, bl, 0, s, (const bf16*)xx, (const bf16*)rr,  \
-                                       g, G, partial, P, (int)act, (unsigned*)sync, (bf16*)yy);                    \
-                else                                                                                               \
-                    hipLaunchKernelGGL((k_bn_cluster_nchw<8, 8>), gr, bl, 0, s, (const bf16*)xx, (const bf16*)rr,  \
-                                       g, G, partial, P, (int)act, (unsigned*)sync, (bf16*)yy);                    \
-            } else if (G == 1 && LSS_BN_FUSED && fused_reg<T>(V, cnt)) {                                           \
-                if (V == 8 && cnt <= 4 * kBlock)                                                                   \
-                    hipLaunchKernelGGL((k_bn_fused_reg_nchw<8, 4>), gr, bl, 0, s, (const bf16*)xx,                \
-                                       (const bf16*)rr, g, P, (int)act, (bf16*)yy);                                \
-                else if (V == 8 && cnt <= 5 * kBlock)                                                              \
-                    hipLaunchKernelGGL((k_bn_fused_reg_nchw<8, 5>), gr, bl, 0, s, (const bf16*)xx,                \
-                                       (const bf16*)rr, g, P, (int)act, (bf16*)yy);                                \
-                else if (V == 8)                                                                                   \
-                    hipLaunchKernelGGL((k_bn_fused_reg_nchw<8, 8>), gr, bl, 0, s, (const bf16*)xx,                \
-                                       (const bf16*)rr, g, P, (int)act, (bf16*)yy);                                \
-                else if (cnt <= 4 * kBlock)                                                                        \
-                    hipLaunchKernelGGL((k_bn_fused_reg_nchw<4, 4>), gr, bl, 0, s, (const bf16*)xx,                \
-                                       (const bf16*)rr, g, P, (int)act, (bf16*)yy);                                \
-                else                                                                                               \
-                    hipLaunchKernelGGL((k_bn_fused_reg_nchw<4, 8>), gr, bl, 0, s, (const bf16*)xx,                \
-                                       (const bf16*)rr, g, P, (int)act, (bf16*)yy);                                \
-            } else if (G == 1 && LSS_BN_FUSED) {                                                                   \
-                if (V == 8) hipLaunchKernelGGL((k_bn_fused_nchw<8, T>), gr, bl, 0, s, xx, rr, g, P, (int)act, yy); \
-                else if (V == 4) hipLaunchKernelGGL((k_bn_fused_nchw<4, T>), gr, bl, 0, s, xx, rr, g, P, (int)act, \
-                                                    yy);                                                           \
-                else hipLaunchKernelGGL((k_bn_fused_nchw<1, T>), gr, bl, 0, s, xx, rr, g, P, (int)act, yy);        \
-            } else if (V == 8) {                                                                                   \
-                hipLaunchKernelGGL((k_bn_stats_nchw<8, T>), gr, bl, 0, s, xx, g, G, partial);                     \
-                hipLaunchKernelGGL((k_bn_apply_nchw<8, T>), gr, bl, 0, s, xx, rr, g, G, partial, P, (int)act, yy); \
-            } else if (V == 4) {                                                                                   \
-                hipLaunchKernelGGL((k_bn_stats_nchw<4, T>), gr, bl, 0, s, xx, g, G, partial);                     \
-                hipLaunchKernelGGL((k_bn_apply_nchw<4, T>), gr, bl, 0, s, xx, rr, g, G, partial, P, (int)act, yy); \
-            } else {                                                                                               \
-                hipLaunchKernelGGL((k_bn_stats_nchw<1, T>), gr, bl, 0, s, xx, g, G, partial);                     \
-                hipLaunchKernelGGL((k_bn_apply_nchw<1, T>), gr, bl, 0, s, xx, rr, g, G, partial, P, (int)act, yy); \
-            }                                                                                                      \
-        }                                                                                                          \
+    lss_bn_arm_t arm;
+    if (bn_arm(LSS_BN_FWD, dtype, layout, g, act, G, sync != nullptr, &arm) != 0) return LSS_CONV_EINVAL;
+    const int vit = arm.v * 10 + arm.it;  // (V, IT) of the register kernels as one switch key
+#define LAUNCH_BN_FWD(T)                                                                                                  \
+    do {                                                                                                               \
+        const T* xx = (const T*)x;                                                                                     \
+        const T* rr = (const T*)residual;                                                                              \
+        T* yy = (T*)y;                                                                                                 \
+        const bf16 *xb = (const bf16*)x, *rb = (const bf16*)residual;                                                  \
+        bf16* yb = (bf16*)y;                                                                                           \
+        const dim3 gr(arm.blocks), bl(kBlock);                                                                         \
+        if (arm.family == LSS_BN_ARM_NHWC) {                                                                           \
+            const size_t lds = 2 * C * sizeof(float);                                                                  \
+            hipLaunchKernelGGL(k_bn_stats_nhwc<T>, dim3(G), dim3(kBlock), kNhwcStatsLds * C * sizeof(float), s, xx,    \
+                               g, G, partial);                                                                         \
+            hipLaunchKernelGGL(k_bn_fold_nhwc<T>, dim3((C + 3) / 4), dim3(kBlock), 0, s, partial, G, xx, g, P);        \
+            if (!yy) {                                                                                                 \
+            } else if (LSS_BN_ROWS)                                                                                    \
+                hipLaunchKernelGGL(k_bn_apply_rows_nhwc<T>, dim3(apply_blocks(g)), dim3(kBlock), 0, s, xx, rr, g,      \
+                                   save_mean, (int)act, yy);                                                           \
+            else                                                                                                       \
+                hipLaunchKernelGGL(k_bn_apply_nhwc<T>, dim3(apply_blocks(g)), dim3(kBlock), lds, s, xx, rr, g,         \
+                                   save_mean, (int)act, yy);                                                           \
+        } else if (arm.family == LSS_BN_ARM_CLUSTER) {                                                                 \
+            if (arm.it == 6)                                                                                           \
+                hipLaunchKernelGGL((k_bn_cluster_nchw<8, 6>), gr, bl, 0, s, xb, rb, g, G, partial, P, (int)act,        \
+                                   (unsigned*)sync, yb);                                                               \
+            else                                                                                                       \
+                hipLaunchKernelGGL((k_bn_cluster_nchw<8, 8>), gr, bl, 0, s, xb, rb, g, G, partial, P, (int)act,        \
+                                   (unsigned*)sync, yb);                                                               \
+        } else if (arm.family == LSS_BN_ARM_FUSED_REG) {                                                               \
+            if (vit == 84) hipLaunchKernelGGL((k_bn_fused_reg_nchw<8, 4>), gr, bl, 0, s, xb, rb, g, P, (int)act, yb);  \
+            else if (vit == 85)                                                                                        \
+                hipLaunchKernelGGL((k_bn_fused_reg_nchw<8, 5>), gr, bl, 0, s, xb, rb, g, P, (int)act, yb);             \
+            else if (vit == 88)                                                                                        \
+                hipLaunchKernelGGL((k_bn_fused_reg_nchw<8, 8>), gr, bl, 0, s, xb, rb, g, P, (int)act, yb);             \
+            else if (vit == 44)                                                                                        \
+                hipLaunchKernelGGL((k_bn_fused_reg_nchw<4, 4>), gr, bl, 0, s, xb, rb, g, P, (int)act, yb);             \
+            else hipLaunchKernelGGL((k_bn_fused_reg_nchw<4, 8>), gr, bl, 0, s, xb, rb, g, P, (int)act, yb);            \
+        } else if (arm.family == LSS_BN_ARM_FUSED) {                                                                   \
+            if (arm.v == 8) hipLaunchKernelGGL((k_bn_fused_nchw<8, T>), gr, bl, 0, s, xx, rr, g, P, (int)act, yy);     \
+            else if (arm.v == 4)                                                                                       \
+                hipLaunchKernelGGL((k_bn_fused_nchw<4, T>), gr, bl, 0, s, xx, rr, g, P, (int)act, yy);                 \
+            else hipLaunchKernelGGL((k_bn_fused_nchw<1, T>), gr, bl, 0, s, xx, rr, g, P, (int)act, yy);                \
+        } else if (arm.v == 8) {                                                                                       \
+            hipLaunchKernelGGL((k_bn_stats_nchw<8, T>), gr, bl, 0, s, xx, g, G, partial);                              \
+            hipLaunchKernelGGL((k_bn_apply_nchw<8, T>), gr, bl, 0, s, xx, rr, g, G, partial, P, (int)act, yy);         \
+        } else if (arm.v == 4) {                                                                                       \
+            hipLaunchKernelGGL((k_bn_stats_nchw<4, T>), gr, bl, 0, s, xx, g, G, partial);                              \
+            hipLaunchKernelGGL((k_bn_apply_nchw<4, T>), gr, bl, 0, s, xx, rr, g, G, partial, P, (int)act, yy);         \
+        } else {                                                                                                       \
+            hipLaunchKernelGGL((k_bn_stats_nchw<1, T>), gr, bl, 0, s, xx, g, G, partial);                              \
+            hipLaunchKernelGGL((k_bn_apply_nchw<1, T>), gr, bl, 0, s, xx, rr, g, G, partial, P, (int)act, yy);         \
+        }                                                                                                              \
     } while (0)
-    if (dtype == LSS_CONV_F32) LSS_BN_FWD(float);
-    else if (dtype == LSS_CONV_BF16) LSS_BN_FWD(bf16);
-    else return LSS_CONV_EINVAL;
-#undef LSS_BN_FWD
+    if (dtype == LSS_CONV_F32) LAUNCH_BN_FWD(float);
+    else LAUNCH_BN_FWD(bf16);
+#undef LAUNCH_BN_FWD
     return launch_status();
 }
 
@@ -1522,6 +1580,9 @@ int lss_bn_bwd2(const void* dy, const void* x, const void* y, int32_t dtype, int
         return LSS_CONV_EINVAL;
     if (save_rstd != save_mean + C || scale != save_mean + 2 * C || shift != save_mean + 3 * C) return LSS_CONV_EINVAL;
     if (act == LSS_ACT_RELU && !y && layout != LSS_CONV_NHWC) return LSS_CONV_EINVAL;
+    // swish's slope is taken at the pre-activation recomputed from x alone: with a residual in the forward it
+    // would be the slope at another point
+    if (act == LSS_ACT_SWISH && dresidual) return LSS_CONV_EINVAL;
     if (act != LSS_ACT_NONE && act != LSS_ACT_RELU && act != LSS_ACT_SWISH) return LSS_CONV_EINVAL;
     if (layout == LSS_CONV_NHWC && ngroups > kMaxGroupsNhwc) return LSS_CONV_EINVAL;
     if (!ptrs_ok(bn_align_mask(dtype, layout, HW), dy, x, y, dx, dresidual) ||
@@ -1530,94 +1591,89 @@ int lss_bn_bwd2(const void* dy, const void* x, const void* y, int32_t dtype, int
     hipStream_t s = (hipStream_t)stream;
     const int G = ngroups;
     const float* stats = save_mean;
-#define LSS_BN_BWD(T)                                                                                              \
-    do {                                                                                                           \
-        const T* d = (const T*)dy;                                                                                 \
-        const T* xx = (const T*)x;                                                                                 \
-        const T* yy = (const T*)y;                                                                                 \
-        T* o = (T*)dx;                                                                                             \
-        T* orr = (T*)dresidual;                                                                                    \
-        if (layout == LSS_CONV_NHWC) {                                                                             \
-            hipLaunchKernelGGL(k_bn_bwd_stats_nhwc<T>, dim3(G), dim3(kBlock), kNhwcStatsLds * C * sizeof(float), s, d, xx, yy, \
-                               g, G, stats, (int)act, partial);                                                    \
-            hipLaunchKernelGGL(k_bn_bwd_fold_nhwc, dim3((C + 3) / 4), dim3(kBlock), 0, s, partial, G, g, dgamma,  \
-                               dbeta, coef);                                                                       \
-            if (LSS_BN_ROWS)                                                                                       \
-                hipLaunchKernelGGL(k_bn_bwd_apply_rows_nhwc<T>, dim3(apply_blocks(g)), dim3(kBlock), 0, s, d, xx, yy, \
-                                   g, stats, coef, (int)act, o, orr);                                              \
-            else                                                                                                   \
+    lss_bn_arm_t arm;
+    if (bn_arm(LSS_BN_BWD, dtype, layout, g, act, G, sync != nullptr, &arm) != 0) return LSS_CONV_EINVAL;
+    const int vit = arm.v * 10 + arm.it;
+#define LAUNCH_BN_BWD(T)                                                                                                  \
+    do {                                                                                                               \
+        const T* d = (const T*)dy;                                                                                     \
+        const T* xx = (const T*)x;                                                                                     \
+        const T* yy = (const T*)y;                                                                                     \
+        T* o = (T*)dx;                                                                                                 \
+        T* orr = (T*)dresidual;                                                                                        \
+        const bf16 *db = (const bf16*)dy, *xb = (const bf16*)x, *yb = (const bf16*)y;                                  \
+        bf16 *ob = (bf16*)dx, *orb = (bf16*)dresidual;                                                                 \
+        const dim3 gr(arm.blocks), bl(kBlock);                                                                         \
+        if (arm.family == LSS_BN_ARM_NHWC) {                                                                           \
+            hipLaunchKernelGGL(k_bn_bwd_stats_nhwc<T>, dim3(G), dim3(kBlock), kNhwcStatsLds * C * sizeof(float), s, d, \
+                               xx, yy, g, G, stats, (int)act, partial);                                                \
+            hipLaunchKernelGGL(k_bn_bwd_fold_nhwc, dim3((C + 3) / 4), dim3(kBlock), 0, s, partial, G, g, dgamma,       \
+                               dbeta, coef);                                                                           \
+            if (LSS_BN_ROWS)                                                                                           \
+                hipLaunchKernelGGL(k_bn_bwd_apply_rows_nhwc<T>, dim3(apply_blocks(g)), dim3(kBlock), 0, s, d, xx, yy,  \
+                                   g, stats, coef, (int)act, o, orr);                                                  \
+            else                                                                                                       \
                 hipLaunchKernelGGL(k_bn_bwd_apply_nhwc<T>, dim3(apply_blocks(g)), dim3(kBlock), 6 * C * sizeof(float), \
-                                   s, d, xx, yy, g, stats, coef, (int)act, o, orr);                                \
-        } else {                                                                                                   \
-            const int V = vec_nchw(HW);                                                                            \
-            const dim3 gr(C * G), bl(kBlock);                                                                      \
-            const long cnt = (long)N * (HW / V);                                                                   \
-            if (cluster_ok<T>(sync, G, V, g, true)) {                                                              \
-                const bf16 *db = (const bf16*)d, *xb = (const bf16*)xx, *yb = (const bf16*)yy;                     \
-                const bool it6 = cluster_it(G, V, g) <= 6;                                                         \
-                if (act == LSS_ACT_RELU && it6)                                                                    \
-                    hipLaunchKernelGGL((k_bn_bwd_cluster_nchw<8, 6, true>), gr, bl, 0, s, db, xb, yb, g, G, stats, \
-                                       partial, (int)act, (unsigned*)sync, dgamma, dbeta, (bf16*)o, (bf16*)orr);   \
-                else if (act == LSS_ACT_RELU)                                                                      \
-                    hipLaunchKernelGGL((k_bn_bwd_cluster_nchw<8, 8, true>), gr, bl, 0, s, db, xb, yb, g, G, stats, \
-                                       partial, (int)act, (unsigned*)sync, dgamma, dbeta, (bf16*)o, (bf16*)orr);   \
-                else if (it6)                                                                                      \
-                    hipLaunchKernelGGL((k_bn_bwd_cluster_nchw<8, 6, false>), gr, bl, 0, s, db, xb, yb, g, G,       \
-                                       stats, partial, (int)act, (unsigned*)sync, dgamma, dbeta, (bf16*)o,         \
-                                       (bf16*)orr);                                                                \
-                else                                                                                               \
-                    hipLaunchKernelGGL((k_bn_bwd_cluster_nchw<8, 8, false>), gr, bl, 0, s, db, xb, yb, g, G,       \
-                                       stats, partial, (int)act, (unsigned*)sync, dgamma, dbeta, (bf16*)o,         \
-                                       (bf16*)orr);                                                                \
-            } else if (G == 1 && LSS_BN_FUSED && fused_reg<T>(V, cnt)) {                                           \
-                const bf16 *db = (const bf16*)d, *xb = (const bf16*)xx, *yb = (const bf16*)yy;                     \
-                if (V == 8 && cnt <= 4 * kBlock)                                                                   \
-                    hipLaunchKernelGGL((k_bn_bwd_fused_reg_nchw<8, 4>), gr, bl, 0, s, db, xb, yb, g, stats,       \
-                                       (int)act, dgamma, dbeta, (bf16*)o, (bf16*)orr);                             \
-                else if (V == 8 && cnt <= 5 * kBlock)                                                              \
-                    hipLaunchKernelGGL((k_bn_bwd_fused_reg_nchw<8, 5>), gr, bl, 0, s, db, xb, yb, g, stats,       \
-                                       (int)act, dgamma, dbeta, (bf16*)o, (bf16*)orr);                             \
-                else if (V == 8)                                                                                   \
-                    hipLaunchKernelGGL((k_bn_bwd_fused_reg_nchw<8, 8>), gr, bl, 0, s, db, xb, yb, g, stats,       \
-                                       (int)act, dgamma, dbeta, (bf16*)o, (bf16*)orr);                             \
-                else if (cnt <= 4 * kBlock)                                                                        \
-                    hipLaunchKernelGGL((k_bn_bwd_fused_reg_nchw<4, 4>), gr, bl, 0, s, db, xb, yb, g, stats,       \
-                                       (int)act, dgamma, dbeta, (bf16*)o, (bf16*)orr);                             \
-                else                                                                                               \
-                    hipLaunchKernelGGL((k_bn_bwd_fused_reg_nchw<4, 8>), gr, bl, 0, s, db, xb, yb, g, stats,       \
-                                       (int)act, dgamma, dbeta, (bf16*)o, (bf16*)orr);                             \
-            } else if (G == 1 && LSS_BN_FUSED) {                                                                   \
-                if (V == 8)                                                                                        \
-                    hipLaunchKernelGGL((k_bn_bwd_fused_nchw<8, T>), gr, bl, 0, s, d, xx, yy, g, stats, (int)act,  \
-                                       dgamma, dbeta, o, orr);                                                     \
-                else if (V == 4)                                                                                   \
-                    hipLaunchKernelGGL((k_bn_bwd_fused_nchw<4, T>), gr, bl, 0, s, d, xx, yy, g, stats, (int)act,  \
-                                       dgamma, dbeta, o, orr);                                                     \
-                else                                                                                               \
-                    hipLaunchKernelGGL((k_bn_bwd_fused_nchw<1, T>), gr, bl, 0, s, d, xx, yy, g, stats, (int)act,  \
-                                       dgamma, dbeta, o, orr);                                                     \
-            } else if (V == 8) {                                                                                   \
-                hipLaunchKernelGGL((k_bn_bwd_stats_nchw<8, T>), gr, bl, 0, s, d, xx, yy, g, G, stats, (int)act,    \
-                                   partial);                                                                       \
-                hipLaunchKernelGGL((k_bn_bwd_apply_nchw<8, T>), gr, bl, 0, s, d, xx, yy, g, G, stats, partial,    \
-                                   (int)act, dgamma, dbeta, o, orr);                                               \
-            } else if (V == 4) {                                                                                   \
-                hipLaunchKernelGGL((k_bn_bwd_stats_nchw<4, T>), gr, bl, 0, s, d, xx, yy, g, G, stats, (int)act,    \
-                                   partial);                                                                       \
-                hipLaunchKernelGGL((k_bn_bwd_apply_nchw<4, T>), gr, bl, 0, s, d, xx, yy, g, G, stats, partial,    \
-                                   (int)act, dgamma, dbeta, o, orr);                                               \
-            } else {                                                                                               \
-                hipLaunchKernelGGL((k_bn_bwd_stats_nchw<1, T>), gr, bl, 0, s, d, xx, yy, g, G, stats, (int)act,    \
-                                   partial);                                                                       \
-                hipLaunchKernelGGL((k_bn_bwd_apply_nchw<1, T>), gr, bl, 0, s, d, xx, yy, g, G, stats, partial,    \
-                                   (int)act, dgamma, dbeta, o, orr);                                               \
-            }                                                                                                      \
-        }                                                                                                          \
+                                   s, d, xx, yy, g, stats, coef, (int)act, o, orr);                                    \
+        } else if (arm.family == LSS_BN_ARM_CLUSTER) {                                                                 \
+            if (arm.relu && arm.it == 6)                                                                               \
+                hipLaunchKernelGGL((k_bn_bwd_cluster_nchw<8, 6, true>), gr, bl, 0, s, db, xb, yb, g, G, stats,         \
+                                   partial, (int)act, (unsigned*)sync, dgamma, dbeta, ob, orb);                        \
+            else if (arm.relu)                                                                                         \
+                hipLaunchKernelGGL((k_bn_bwd_cluster_nchw<8, 8, true>), gr, bl, 0, s, db, xb, yb, g, G, stats,         \
+                                   partial, (int)act, (unsigned*)sync, dgamma, dbeta, ob, orb);                        \
+            else if (arm.it == 6)                                                                                      \
+                hipLaunchKernelGGL((k_bn_bwd_cluster_nchw<8, 6, false>), gr, bl, 0, s, db, xb, yb, g, G, stats,        \
+                                   partial, (int)act, (unsigned*)sync, dgamma, dbeta, ob, orb);                        \
+            else                                                                                                       \
+                hipLaunchKernelGGL((k_bn_bwd_cluster_nchw<8, 8, false>), gr, bl, 0, s, db, xb, yb, g, G, stats,        \
+                                   partial, (int)act, (unsigned*)sync, dgamma, dbeta, ob, orb);                        \
+        } else if (arm.family == LSS_BN_ARM_FUSED_REG) {                                                               \
+            if (vit == 84)                                                                                             \
+                hipLaunchKernelGGL((k_bn_bwd_fused_reg_nchw<8, 4>), gr, bl, 0, s, db, xb, yb, g, stats, (int)act,      \
+                                   dgamma, dbeta, ob, orb);                                                            \
+            else if (vit == 85)                                                                                        \
+                hipLaunchKernelGGL((k_bn_bwd_fused_reg_nchw<8, 5>), gr, bl, 0, s, db, xb, yb, g, stats, (int)act,      \
+                                   dgamma, dbeta, ob, orb);                                                            \
+            else if (vit == 88)                                                                                        \
+                hipLaunchKernelGGL((k_bn_bwd_fused_reg_nchw<8, 8>), gr, bl, 0, s, db, xb, yb, g, stats, (int)act,      \
+                                   dgamma, dbeta, ob, orb);                                                            \
+            else if (vit == 44)                                                                                        \
+                hipLaunchKernelGGL((k_bn_bwd_fused_reg_nchw<4, 4>), gr, bl, 0, s, db, xb, yb, g, stats, (int)act,      \
+                                   dgamma, dbeta, ob, orb);                                                            \
+            else                                                                                                       \
+                hipLaunchKernelGGL((k_bn_bwd_fused_reg_nchw<4, 8>), gr, bl, 0, s, db, xb, yb, g, stats, (int)act,      \
+                                   dgamma, dbeta, ob, orb);                                                            \
+        } else if (arm.family == LSS_BN_ARM_FUSED) {                                                                   \
+            if (arm.v == 8)                                                                                            \
+                hipLaunchKernelGGL((k_bn_bwd_fused_nchw<8, T>), gr, bl, 0, s, d, xx, yy, g, stats, (int)act,           \
+                                   dgamma, dbeta, o, orr);                                                             \
+            else if (arm.v == 4)                                                                                       \
+                hipLaunchKernelGGL((k_bn_bwd_fused_nchw<4, T>), gr, bl, 0, s, d, xx, yy, g, stats, (int)act,           \
+                                   dgamma, dbeta, o, orr);                                                             \
+            else                                                                                                       \
+                hipLaunchKernelGGL((k_bn_bwd_fused_nchw<1, T>), gr, bl, 0, s, d, xx, yy, g, stats, (int)act,           \
+                                   dgamma, dbeta, o, orr);                                                             \
+        } else if (arm.v == 8) {                                                                                       \
+            hipLaunchKernelGGL((k_bn_bwd_stats_nchw<8, T>), gr, bl, 0, s, d, xx, yy, g, G, stats, (int)act,            \
+                               partial);                                                                               \
+            hipLaunchKernelGGL((k_bn_bwd_apply_nchw<8, T>), gr, bl, 0, s, d, xx, yy, g, G, stats, partial,             \
+                               (int)act, dgamma, dbeta, o, orr);                                                       \
+        } else if (arm.v == 4) {                                                                                       \
+            hipLaunchKernelGGL((k_bn_bwd_stats_nchw<4, T>), gr, bl, 0, s, d, xx, yy, g, G, stats, (int)act,            \
+                               partial);                                                                               \
+            hipLaunchKernelGGL((k_bn_bwd_apply_nchw<4, T>), gr, bl, 0, s, d, xx, yy, g, G, stats, partial,             \
+                               (int)act, dgamma, dbeta, o, orr);                                                       \
+        } else {                                                                                                       \
+            hipLaunchKernelGGL((k_bn_bwd_stats_nchw<1, T>), gr, bl, 0, s, d, xx, yy, g, G, stats, (int)act,            \
+                               partial);                                                                               \
+            hipLaunchKernelGGL((k_bn_bwd_apply_nchw<1, T>), gr, bl, 0, s, d, xx, yy, g, G, stats, partial,             \
+                               (int)act, dgamma, dbeta, o, orr);                                                       \
+        }                                                                                                              \
     } while (0)
-    if (dtype == LSS_CONV_F32) LSS_BN_BWD(float);
-    else if (dtype == LSS_CONV_BF16) LSS_BN_BWD(bf16);
-    else return LSS_CONV_EINVAL;
-#undef LSS_BN_BWD
+    if (dtype == LSS_CONV_F32) LAUNCH_BN_BWD(float);
+    else LAUNCH_BN_BWD(bf16);
+#undef LAUNCH_BN_BWD
     return launch_status();
 }
 
@@ -1659,31 +1715,24 @@ int lss_bn_eval(const void* x, const void* residual, int32_t dtype, int32_t layo
         return LSS_CONV_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     const BnEval E{gamma, beta, running_mean, running_var, eps};
-#define LSS_BN_EVAL(T)                                                                                             \
-    do {                                                                                                           \
-        const T* xx = (const T*)x;                                                                                 \
-        const T* rr = (const T*)residual;                                                                          \
-        T* yy = (T*)y;                                                                                             \
-        if (layout == LSS_CONV_NHWC) {                                                                             \
-            const long rows = (long)N * HW, per_block = (long)(kBlock / (C / 8)) * kEvalU;                         \
-            const long b = (rows + per_block - 1) / per_block;                                                     \
-            hipLaunchKernelGGL(k_bn_eval_nhwc<T>, dim3((int)(b < kEvalBlocks ? b : kEvalBlocks)), dim3(kBlock), 0, \
-                               s, xx, rr, g, E, (int)act, yy);                                                     \
-        } else {                                                                                                   \
-            /* bf16 with HW % 8 == 4 and fp32 with HW % 4 == 0: V = 4 */                                           \
-            const int V8 = vec_nchw(HW), V = (V8 == 8 && sizeof(T) == 4) ? 4 : V8;                                 \
-            const long cnt = (long)N * (HW / V);                                                                   \
-            const int G = (int)((cnt + kBlock * kEvalU - 1) / (kBlock * kEvalU));                                  \
-            const long units = (long)C * G;                                                                        \
-            const dim3 gr((int)(units < kEvalBlocks ? units : kEvalBlocks)), bl(kBlock);                           \
-            if (V == 8) hipLaunchKernelGGL((k_bn_eval_nchw<8, T>), gr, bl, 0, s, xx, rr, g, G, E, (int)act, yy);   \
-            else if (V == 4) hipLaunchKernelGGL((k_bn_eval_nchw<4, T>), gr, bl, 0, s, xx, rr, g, G, E, (int)act, yy); \
-            else hipLaunchKernelGGL((k_bn_eval_nchw<1, T>), gr, bl, 0, s, xx, rr, g, G, E, (int)act, yy);          \
-        }                                                                                                          \
+    lss_bn_arm_t arm;
+    if (bn_arm(LSS_BN_EVAL, dtype, layout, g, act, 1, false, &arm) != 0) return LSS_CONV_EINVAL;
+#define LAUNCH_BN_EVAL(T)                                                                                                 \
+    do {                                                                                                               \
+        const T* xx = (const T*)x;                                                                                     \
+        const T* rr = (const T*)residual;                                                                              \
+        T* yy = (T*)y;                                                                                                 \
+        const dim3 gr(arm.blocks), bl(kBlock);                                                                         \
+        const int G = arm.chunks;                                                                                      \
+        if (arm.family == LSS_BN_ARM_EVAL_NHWC)                                                                        \
+            hipLaunchKernelGGL(k_bn_eval_nhwc<T>, gr, bl, 0, s, xx, rr, g, E, (int)act, yy);                           \
+        else if (arm.v == 8) hipLaunchKernelGGL((k_bn_eval_nchw<8, T>), gr, bl, 0, s, xx, rr, g, G, E, (int)act, yy);  \
+        else if (arm.v == 4) hipLaunchKernelGGL((k_bn_eval_nchw<4, T>), gr, bl, 0, s, xx, rr, g, G, E, (int)act, yy);  \
+        else hipLaunchKernelGGL((k_bn_eval_nchw<1, T>), gr, bl, 0, s, xx, rr, g, G, E, (int)act, yy);                  \
     } while (0)
-    if (dtype == LSS_CONV_F32) LSS_BN_EVAL(float);
-    else LSS_BN_EVAL(bf16);
-#undef LSS_BN_EVAL
+    if (dtype == LSS_CONV_F32) LAUNCH_BN_EVAL(float);
+    else LAUNCH_BN_EVAL(bf16);
+#undef LAUNCH_BN_EVAL
     return launch_status();
 }
 

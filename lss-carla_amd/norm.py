@@ -10,7 +10,8 @@ In eval mode with no gradient wanted (inference: ``model.eval()`` under ``no_gra
 activation, and writes nothing but the output (``USE_HIP_BN_EVAL``; ``eval_eligible`` is the guard).
 Eval mode with gradients (frozen-BN fine-tuning), CPU tensors, a module whose parameters are not fp32,
 ``affine=False``, ``track_running_stats=False`` in eval mode, channels-last maps whose channel count the
-kernels do not take, or ``USE_HIP_BN = False`` run the same computation with stock PyTorch ops.
+kernels do not take, swish with a residual in training mode (the backward kernels do not have it), or
+``USE_HIP_BN = False`` run the same computation with stock PyTorch ops.
 """
 from __future__ import annotations
 
@@ -190,6 +191,8 @@ def bn_act(bn: nn.BatchNorm2d, x: torch.Tensor, act: str = "none", residual: Opt
                 return _bn_eval(bn, x, ACT[act], residual, _layout(x))
         return _torch_bn_act(bn, x, act, residual)
     layout = _layout(x)
-    if not (USE_HIP_BN and _shape_ok(bn, x, layout)):
+    # (swish with a residual: the backward kernels take swish's slope without the residual -- lss_bn_bwd2
+    # refuses it -- so that combination, which no model here uses, trains on the stock ops)
+    if not (USE_HIP_BN and _shape_ok(bn, x, layout)) or (act == "swish" and residual is not None):
         return _torch_bn_act(bn, x, act, residual)
     return _BnAct.apply(x, bn.weight, bn.bias, residual, bn, ACT[act], layout)

@@ -2,8 +2,8 @@
 tests/test_host.py proves on the CPU that they cover every arm).
 
 The C entry points choose among many kernel instantiations by shape and dtype; the library reports each
-choice through a host-only query (lss_splat_bwd_arm, lss_lift_prep_arm, lss_dwconv_arm; the launchers
-switch on the same functions). Every case here carries its arguments and the arm it is meant to hit.
+choice through a host-only query (lss_splat_bwd_arm, lss_lift_prep_arm, lss_dwconv_arm, lss_bn_arm; the
+launchers switch on the same functions). Every case here carries its arguments and the arm it is meant to hit.
 No GPU is needed to import this module: inputs and references are numpy / CPU torch.
 """
 from collections import namedtuple
@@ -28,6 +28,12 @@ EUNSUPPORTED = -2
 #   depthwise, the banded 700 x 8 plane (K = 5):      y / dx 0.032, dw 0.013
 #   depthwise, 3 x 2 planes of 128 x 176 (stride 2):  y / dx 0.010, dw 0.035
 # (so every bar has 28x room or more over fp32 arithmetic: no input needed scaling)
+# Batch norm (its own bars, derived at bn_map_bar / bn_fwd_bars below), the largest case of each family, numpy's
+# pairwise order | one element after the other; per-channel outputs with BN_K = 64, BN_K_SQ = 512:
+#   one group, 16,384 elements a channel:   save_mean 0.007 | 0.144, rstd 0.001 | 0.093, dbeta / dgamma 0.000 | 0.009
+#   two-pass and cluster, 32,800 / 32,768:  save_mean 0.012 | 0.143, rstd 0.002 | 0.218, dbeta / dgamma 0.000 | 0.010
+#   NHWC, 2,048 rows:                       save_mean 0.010 | 0.010, rstd 0.001 | 0.032, dbeta / dgamma 0.001 | 0.007
+#   fp32 maps against rtol = atol = 1e-4:   y 0.008 | 0.873 (through the sequentially summed statistics), dx 0.002
 F32_TOL = dict(rtol=1e-4, atol=1e-4)
 
 
@@ -332,3 +338,331 @@ def dw_inputs(case, dtype):
     w = torch.randn(case.C, 1, case.K, case.K, generator=g) * 0.2
     dy = torch.randn(case.N, case.C, Ho, Wo, generator=g).to(dtype)
     return x, w, dy
+
+
+# ----------------------------------------------------------------------------- batch norm
+# lss_bn_arm's passes, families and names (include/lss_convs.h)
+BN_FWD, BN_BWD, BN_EVAL = 0, 1, 2
+BN_FAMILIES = ("nhwc", "cluster", "fused_reg", "fused", "two_pass", "eval_nchw", "eval_nhwc")
+ACT = {"none": 0, "relu": 1, "swish": 2}
+BN_EPS, BN_MOM = 1e-3, 0.1
+BN_SEED = 100000  # (committed with the draws: test_host.py's caps and left-out-element proofs hold for this one)
+
+
+def bn_arm_name(family: int, v: int, it: int, relu: int) -> str:
+    """lss_bn_arm_t as the table writes it."""
+    name = BN_FAMILIES[family]
+    if name == "cluster":
+        return "cluster<%d,%d%s>" % (v, it, ",relu" if relu else "")
+    if name == "fused_reg":
+        return "fused_reg<%d,%d>" % (v, it)
+    return name if name.endswith("nhwc") else "%s<%d>" % (name, v)
+
+
+def bn_arms(pas: int, dtype) -> set:
+    """Every training arm include/lss_convs.h enumerates for a pass and dtype."""
+    arms = {"nhwc"} | {"%s<%d>" % (f, v) for f in ("fused", "two_pass") for v in (8, 4, 1)}
+    if dtype == BF16:
+        arms |= {"fused_reg<8,4>", "fused_reg<8,5>", "fused_reg<8,8>", "fused_reg<4,4>", "fused_reg<4,8>",
+                 "cluster<8,6>", "cluster<8,8>"}
+        if pas == BN_BWD:
+            arms |= {"cluster<8,6,relu>", "cluster<8,8,relu>"}
+    return arms
+
+
+# (N, C, H, W), layout (0 NCHW, 1 NHWC), ngroups, whether a sync workspace is passed; the arm the forward takes
+# with fp32 / bf16 maps, the backward's where it differs (bwd: a (f32, bf16) pair or None); py: the shape also runs
+# through norm.bn_act, where lss_bn_groups must pick this ngroups
+BnCase = namedtuple("BnCase", "N C H W layout G sync f32 bf16 bwd py note", defaults=(None, False, ""))
+_T8, _T4, _T1 = "two_pass<8>", "two_pass<4>", "two_pass<1>"
+BN_CASES = [
+    # ---- NCHW, one group, C = 3: both sides of every bound on cnt = N * HW / V (bf16: the register kernels)
+    BnCase(2, 3, 32, 128, 0, 1, True, "fused<8>", "fused_reg<8,4>", py=True, note="cnt 1024: every register full"),
+    BnCase(93, 3, 8, 11, 0, 1, True, "fused<8>", "fused_reg<8,4>", note="cnt 1023, 11 vectors an image"),
+    BnCase(25, 3, 8, 41, 0, 1, True, "fused<8>", "fused_reg<8,5>", py=True, note="cnt 1025, 41 vectors an image"),
+    BnCase(8, 3, 32, 40, 0, 1, True, "fused<8>", "fused_reg<8,5>", note="cnt 1280: full"),
+    BnCase(21, 3, 8, 61, 0, 1, True, "fused<8>", "fused_reg<8,8>", py=True, note="cnt 1281, 61 vectors an image"),
+    BnCase(23, 3, 8, 89, 0, 1, True, "fused<8>", "fused_reg<8,8>", py=True, note="cnt 2047: lss_bn_groups' last"),
+    BnCase(2, 3, 64, 128, 0, 1, True, "fused<8>", "fused_reg<8,8>", note="cnt 2048 at ngroups 1: full"),
+    BnCase(3, 3, 8, 683, 0, 1, True, "fused<8>", "fused<8>", note="cnt 2049 at ngroups 1: generic bf16"),
+    BnCase(1024, 3, 2, 2, 0, 1, True, "fused<4>", "fused_reg<4,4>", note="V 4, cnt 1024"),
+    BnCase(93, 3, 4, 11, 0, 1, True, "fused<4>", "fused_reg<4,4>", py=True, note="V 4, cnt 1023, 11 vectors an image"),
+    BnCase(25, 3, 4, 41, 0, 1, True, "fused<4>", "fused_reg<4,8>", py=True, note="V 4, cnt 1025, 41 vectors an image"),
+    BnCase(2048, 3, 2, 2, 0, 1, True, "fused<4>", "fused_reg<4,8>", note="V 4, cnt 2048: full"),
+    BnCase(3, 3, 4, 683, 0, 1, True, "fused<4>", "fused<4>", py=True, note="V 4, cnt 2049: generic bf16"),
+    BnCase(2, 3, 5, 7, 0, 1, True, "fused<1>", "fused<1>", py=True, note="V 1"),
+    # ---- NCHW two-pass: several groups, no workspace; groups of unequal image counts, one image a group
+    BnCase(5, 3, 2, 4, 0, 2, False, _T8, _T8, note="groups of 2 and 3 images"),
+    BnCase(5, 3, 2, 4, 0, 3, False, _T8, _T8, note="groups of 1, 2, 2"),
+    BnCase(5, 3, 2, 4, 0, 5, False, _T8, _T8, note="G = N"),
+    BnCase(5, 3, 2, 6, 0, 2, False, _T4, _T4, note="groups of 2 and 3 images"),
+    BnCase(5, 3, 2, 6, 0, 3, False, _T4, _T4, note="groups of 1, 2, 2"),
+    BnCase(5, 3, 2, 6, 0, 5, False, _T4, _T4, note="G = N"),
+    BnCase(5, 3, 3, 5, 0, 2, False, _T1, _T1, note="groups of 2 and 3 images"),
+    BnCase(5, 3, 3, 5, 0, 3, False, _T1, _T1, note="groups of 1, 2, 2"),
+    BnCase(5, 3, 3, 5, 0, 5, False, _T1, _T1, note="G = N"),
+    BnCase(65, 3, 1, 3, 0, 65, False, _T1, _T1, note="65 groups: fold_groups' second lap"),
+    BnCase(2, 3, 2, 4, 0, 3, False, _T8, _T8, note="ngroups > N: an empty group"),
+    BnCase(4, 2, 50, 82, 0, 2, True, _T4, _T4, py=True, note="lss_bn_groups' first G > 1 at V 4"),
+    BnCase(5, 2, 65, 63, 0, 2, True, _T1, _T1, py=True, note="lss_bn_groups' first G > 1 at V 1"),
+    # ---- NCHW cluster (bf16, V 8, a workspace) and what it refuses
+    BnCase(4, 3, 64, 96, 0, 2, True, _T8, "cluster<8,6>", note="6 vectors a thread: full"),
+    BnCase(4, 3, 8, 769, 0, 2, True, _T8, "cluster<8,8>", note="1538 vectors: first of <8,8>"),
+    BnCase(4, 3, 64, 128, 0, 2, True, _T8, "cluster<8,8>", note="8 vectors a thread: full"),
+    BnCase(4, 3, 8, 1025, 0, 2, True, _T8, _T8, note="2050 vectors: past the registers"),
+    BnCase(5, 3, 48, 96, 0, 2, True, _T8, "cluster<8,8>", py=True, note="groups of 2 and 3 images, 7 vectors"),
+    BnCase(4, 3, 2, 4, 0, 2, True, _T8, "cluster<8,6>", note="N / G = 2"),
+    BnCase(3, 3, 2, 4, 0, 2, True, _T8, _T8, note="refused: N / G < 2"),
+    BnCase(128, 3, 2, 4, 0, 64, True, _T8, "cluster<8,6>", note="G = 64"),
+    BnCase(130, 3, 2, 4, 0, 65, True, _T8, _T8, note="refused: G = 65"),
+    BnCase(4, 3, 2, 4, 0, 2, False, _T8, _T8, note="refused: no workspace"),
+    BnCase(4, 3, 2, 6, 0, 2, True, _T4, _T4, note="refused: V 4"),
+    BnCase(4, 512, 2, 4, 0, 2, True, _T8, "cluster<8,6>", note="C G = 1024"),
+    BnCase(4, 513, 8, 8, 0, 2, True, _T8, _T8, bwd=(_T8, "cluster<8,6>"), note="C G = 1026: forward two-pass"),
+    BnCase(4, 1152, 2, 4, 0, 2, True, _T8, _T8, bwd=(_T8, "cluster<8,6>"), note="C G = 2304"),
+    BnCase(4, 1153, 2, 4, 0, 2, True, _T8, _T8, note="C G = 2306: both two-pass"),
+    # ---- NHWC: C / 8 = 1, 2, 8, 64, 256 octets a row; rows M = N H W below one pass of the block, no multiple
+    # of the unrolled pass, one exact multiple; ngroups 1, 2, 17, 1025 and more groups than rows
+    BnCase(5, 8, 1, 7, 1, 1, False, "nhwc", "nhwc", note="35 rows < 256 a pass"),
+    BnCase(3, 8, 7, 49, 1, 2, False, "nhwc", "nhwc", note="1029 rows"),
+    BnCase(2, 8, 32, 32, 1, 1, False, "nhwc", "nhwc", note="2048 rows = 2 unrolled passes"),
+    BnCase(3, 8, 7, 49, 1, 17, False, "nhwc", "nhwc", note="17 groups"),
+    BnCase(3, 8, 7, 49, 1, 1025, False, "nhwc", "nhwc", note="1025 groups: the fold's batched loop and its tail"),
+    BnCase(5, 8, 1, 7, 1, 1025, False, "nhwc", "nhwc", note="ngroups > rows: empty groups"),
+    BnCase(5, 16, 1, 7, 1, 2, False, "nhwc", "nhwc", py=False, note="35 rows < 128 a pass"),
+    BnCase(3, 16, 7, 49, 1, 17, False, "nhwc", "nhwc", note="1029 rows"),
+    BnCase(2, 16, 16, 32, 1, 1, False, "nhwc", "nhwc", note="1024 rows = 2 unrolled passes"),
+    BnCase(1, 64, 3, 5, 1, 1, False, "nhwc", "nhwc", note="15 rows < 32 a pass"),
+    BnCase(3, 64, 7, 49, 1, 2, False, "nhwc", "nhwc", note="1029 rows"),
+    BnCase(3, 64, 7, 49, 1, 17, False, "nhwc", "nhwc", note="17 groups"),
+    BnCase(2, 64, 8, 16, 1, 1, False, "nhwc", "nhwc", note="256 rows = 2 unrolled passes"),
+    BnCase(1, 512, 1, 3, 1, 1, False, "nhwc", "nhwc", note="a wave of octets: 3 rows < 4 a pass"),
+    BnCase(5, 512, 1, 7, 1, 2, False, "nhwc", "nhwc", note="35 rows"),
+    BnCase(5, 512, 1, 7, 1, 17, False, "nhwc", "nhwc", note="17 groups"),
+    BnCase(2, 512, 4, 4, 1, 1, False, "nhwc", "nhwc", note="32 rows = 2 unrolled passes"),
+    BnCase(1, 2048, 1, 3, 1, 1, False, "nhwc", "nhwc", note="one row a pass: 3 rows"),
+    BnCase(5, 2048, 1, 7, 1, 2, False, "nhwc", "nhwc", note="35 rows"),
+    BnCase(1, 2048, 1, 5, 1, 17, False, "nhwc", "nhwc", note="ngroups > rows"),
+    BnCase(2, 2048, 2, 2, 1, 1, False, "nhwc", "nhwc", note="8 rows = 2 unrolled passes"),
+]
+# (case note of the lower neighbour, of the upper neighbour, dtype, pass): the two sides of each bound of the rule
+BN_BOUNDARIES = [
+    ("cnt 1024: every register full", "cnt 1025, 41 vectors an image", BF16, BN_FWD),
+    ("cnt 1280: full", "cnt 1281, 61 vectors an image", BF16, BN_FWD),
+    ("cnt 2048 at ngroups 1: full", "cnt 2049 at ngroups 1: generic bf16", BF16, BN_BWD),
+    ("V 4, cnt 1024", "V 4, cnt 1025, 41 vectors an image", BF16, BN_FWD),
+    ("V 4, cnt 2048: full", "V 4, cnt 2049: generic bf16", BF16, BN_BWD),
+    ("6 vectors a thread: full", "1538 vectors: first of <8,8>", BF16, BN_FWD),
+    ("8 vectors a thread: full", "2050 vectors: past the registers", BF16, BN_BWD),
+    ("N / G = 2", "refused: N / G < 2", BF16, BN_FWD),
+    ("G = 64", "refused: G = 65", BF16, BN_FWD),
+    ("C G = 1024", "C G = 1026: forward two-pass", BF16, BN_FWD),
+    ("C G = 2304", "C G = 2306: both two-pass", BF16, BN_BWD),
+    ("N / G = 2", "refused: no workspace", BF16, BN_FWD),
+    ("N / G = 2", "refused: V 4", BF16, BN_BWD),
+]
+
+# act, residual, y: "y" = given; "null" = the forward without an apply pass / the ReLU backward recomputing y
+BnCombo = namedtuple("BnCombo", "act res y")
+BN_COMBOS_CLUSTER = [BnCombo(a, r, "y") for a in ("none", "swish", "relu") for r in (False, True)]
+BN_COMBOS_NCHW = [BnCombo("swish", False, "y"), BnCombo("relu", True, "y")]
+BN_COMBOS_NHWC = [BnCombo("swish", False, "y"), BnCombo("relu", True, "y"), BnCombo("relu", False, "y"),
+                  BnCombo("relu", False, "null")]
+
+
+def bn_combos(case, pas: int):
+    """The activation / residual combinations a case runs with. The backward of swish with a residual does not
+    exist (the kernels recompute the pre-activation from x alone): lss_bn_bwd2 refuses it."""
+    if case.layout == 1:
+        return BN_COMBOS_NHWC
+    if "cluster" in case.bf16 or (case.bwd and "cluster" in case.bwd[1]):
+        return [c for c in BN_COMBOS_CLUSTER if not (pas == BN_BWD and c.act == "swish" and c.res)]
+    return BN_COMBOS_NCHW
+
+
+def bn_case_arm(case, dtype, pas: int, act: str = "none") -> str:
+    name = (case.bwd if pas == BN_BWD and case.bwd else (case.f32, case.bf16))[0 if dtype == F32 else 1]
+    if pas == BN_BWD and act == "relu" and name.startswith("cluster"):
+        name = name[:-1] + ",relu>"
+    return name
+
+
+def bn_id(case) -> str:
+    return "%dx%dx%dx%d-%s-G%d%s" % (case.N, case.C, case.H, case.W, ("nchw", "nhwc")[case.layout], case.G,
+                                      "-sync" if case.sync else "")
+
+
+def bn_ranges(case):
+    """[(first, last)] element ranges along the reduced axis of the (C, N * HW) view, one per group."""
+    HW = case.H * case.W
+    M = case.N * HW
+    unit = 1 if case.layout == 1 else HW  # NHWC groups cut rows, NCHW groups cut images
+    n = M // unit
+    cuts = [n * q // case.G * unit for q in range(case.G + 1)]
+    return [(a, b - 1) for a, b in zip(cuts[:-1], cuts[1:]) if b > a]
+
+
+def bn_pinned(case) -> bool:
+    """Whether bn_inputs pins the ends of every group's range (at most a 16th of the elements: more of them
+    at one value would pull the channel's mean to it)."""
+    return 32 * len(bn_ranges(case)) <= case.N * case.H * case.W
+
+
+def bn_inputs(case, dtype, combo):
+    """x, residual, dy as (C, M) float64 arrays of values exact in dtype (M = N H W, image-major), and gamma,
+    beta, running mean / var (fp32 values, every channel its own). x = 2 randn + 3. Where bn_pinned, the first
+    and the last element of every group's range sit 2 standard deviations of the channel's draw above its mean,
+    the channel's very first element (always) 2 below ( at least one of the channel's, test_host.py asserts) with
+    dy >= 1 and a residual >= 0, so a kernel that drops a range's last element shows in the sums whatever the
+    activation."""
+    C, M = case.C, case.N * case.H * case.W
+    rng = np.random.default_rng(BN_SEED + case.N * 7919 + C * 131 + M + 17 * case.G + case.layout)
+    x = (2.0 * rng.standard_normal((C, M)) + 3.0).astype(np.float32)
+    res = rng.standard_normal((C, M)).astype(np.float32)
+    dy = rng.standard_normal((C, M)).astype(np.float32)
+    gamma = (0.5 + rng.random(C)).astype(np.float32)
+    beta = (0.1 * rng.standard_normal(C)).astype(np.float32)
+    rm = rng.standard_normal(C).astype(np.float32)
+    rv = (0.5 + rng.random(C)).astype(np.float32)
+    if bn_pinned(case):
+        ends = np.unique(np.array(bn_ranges(case)).reshape(-1))
+        x[:, ends] = (x.mean(axis=1) + 2.0 * x.std(axis=1))[:, None]
+        res[:, ends] = np.abs(res[:, ends])
+        dy[:, ends] = 1.0 + np.abs(dy[:, ends])  # (one sign: the groups' left-out ends cannot cancel)
+    # K, the shift of the kernels' sums: an element equal to it adds nothing to them
+    # (a multiple of 1/2: x - K then stays on x's own bf16 grid)
+    x[:, 0] = np.floor(2.0 * (x[:, 1:].mean(axis=1) - 2.0 * x[:, 1:].std(axis=1))) / 2.0 if M > 2 else 0.0
+    r64 = lambda a: rounded(a, dtype).double().numpy()
+    return dict(x=r64(x), res=r64(res) if combo.res else None, dy=r64(dy), gamma=gamma.astype(np.float64),
+                beta=beta.astype(np.float64), rm=rm.astype(np.float64), rv=rv.astype(np.float64))
+
+
+def _act_and_slope(z, act: str, ft):
+    if act == "relu":
+        return np.maximum(z, ft(0)), (z > 0).astype(z.dtype)
+    if act == "swish":
+        s = ft(1) / (ft(1) + np.exp(-z))
+        return z * s, s * (ft(1) + z * (ft(1) - s))
+    return z, np.ones_like(z)
+
+
+def _sum(a, order: str):
+    """Row sums of a (C, M) array: numpy's pairwise summation, or one element after the other."""
+    a = np.ascontiguousarray(a)  # (rows contiguous: what makes numpy's sum pairwise)
+    return a.sum(axis=1) if order == "pairwise" else np.cumsum(a, axis=1)[:, -1]
+
+
+def bn_reference(ins, combo, dtype, ft=np.float64, order="pairwise", drop=None, fed=None):
+    """Training batch norm + activation, forward and backward, restated in numpy (ft = float64: the reference;
+    float32 in either summation order: what test_host.py measures the bars' room with).
+      forward  mean, biased var, rstd = (var + eps)^-1/2, scale = gamma rstd, shift = beta - mean scale;
+               running <- (1 - m) running + m (mean | var n / (n - 1)); y = act(x scale + shift [+ r])
+      backward from y ROUNDED to dtype and the statistics rounded to fp32 (what the kernels are handed):
+               g = dy act'(.), dbeta = sum g, dgamma = sum g xhat, dx = scale (g - mean g - xhat mean(g xhat)),
+               dres = g
+    The sums are taken as the kernels document them: of x - K and (x - K)^2 with K the channel's first element.
+    drop: element indices left out of every sum (n unchanged): the reference of a kernel that skips them.
+    fed: a reference whose y and statistics the backward takes instead of this evaluation's own forward's (what
+    the GPU tests hand the backward kernels: the fp64 reference's).
+    Returns the outputs and, per sum, the sum of |summands| (the per-channel bars are made of those)."""
+    x, dy, res = ins["x"].astype(ft), ins["dy"].astype(ft), ins["res"]
+    gamma, beta = ins["gamma"].astype(ft), ins["beta"].astype(ft)
+    C, M = x.shape
+    n = ft(M)
+    keep = np.ones(M, dtype=bool)
+    if drop is not None:
+        keep[drop] = False
+    kk = x[:, :1]
+    d = (x - kk)[:, keep]
+    s1, s2 = _sum(d, order) / n, _sum(d * d, order) / n
+    mean = kk[:, 0] + s1
+    var = np.maximum(s2 - s1 * s1, ft(0))
+    rstd = ft(1) / np.sqrt(var + ft(BN_EPS))
+    scale = gamma * rstd
+    shift = beta - mean * scale
+    unb = var * n / (n - ft(1)) if M > 1 else var
+    run_mean = ft(1 - BN_MOM) * ins["rm"].astype(ft) + ft(BN_MOM) * mean
+    run_var = ft(1 - BN_MOM) * ins["rv"].astype(ft) + ft(BN_MOM) * unb
+    z = x * scale[:, None] + shift[:, None]
+    if res is not None:
+        z = z + res.astype(ft)
+    y, _ = _act_and_slope(z, combo.act, ft)
+    out = dict(mean=mean, var=var, rstd=rstd, scale=scale, shift=shift, run_mean=run_mean, run_var=run_var, y=y, z=z,
+               abs_mean=np.abs(x[:, keep]).sum(axis=1) / n,
+               abs_var=(d * d).sum(axis=1) / n + s1 * s1 + var)
+    # the backward's inputs: the reference's y and statistics as stored
+    if fed is not None:
+        stats, y_in = fed["stats_in"].astype(ft), fed["y_in"].astype(ft)
+    else:
+        stats = np.stack([mean, rstd, scale, shift]).astype(np.float32).astype(ft)
+        y_in = rounded(y.astype(np.float64), dtype).double().numpy().astype(ft)
+    m_, r_, sc_, sh_ = stats
+    xhat = (x - m_[:, None]) * r_[:, None]
+    if combo.act == "relu":
+        slope = (y_in > 0).astype(ft)
+    else:
+        slope = _act_and_slope(x * sc_[:, None] + sh_[:, None], combo.act, ft)[1]
+    g = dy * slope
+    gx = g * xhat
+    dbeta, dgamma = _sum(g[:, keep], order), _sum(gx[:, keep], order)
+    dx = sc_[:, None] * (g - (dbeta / n)[:, None] - xhat * (dgamma / n)[:, None])
+    out.update(stats_in=stats, y_in=y_in, dbeta=dbeta, dgamma=dgamma, dx=dx, dres=g,
+               abs_dbeta=np.abs(g[:, keep]).sum(axis=1), abs_dgamma=np.abs(gx[:, keep]).sum(axis=1))
+    return out
+
+
+# Bars. Maps: fp32 the project's rtol = atol = 1e-4; bf16 one bf16 ulp of the reference on top (the kernels compute
+# in fp32 and round once). Per-channel fp32 outputs: k 2^-23 (sum |summands| + |want|), the summands from the fp64
+# reference, carried through rstd / scale / shift / the running update by their derivatives.
+# k: the smallest power of two that leaves a plain fp32 numpy evaluation of bn_reference, in the worse of two
+# summation orders (numpy's pairwise, one element after the other), at most 1/4 of the bar at the largest case of
+# each family (test_host.py::test_arm_references_fp32_margins asserts both that it does and that k / 2 does not).
+# One element after the other loses n 2^-24 of a sum of n squares and about sqrt(n) 2^-24 of a sum of signed
+# terms, so there are two: BN_K for the plain sums (save_mean, running mean, dbeta, dgamma) and BN_K_SQ for what
+# hangs on the sum of squares (rstd, scale, shift, running var). The measured ratios are in the comment block at
+# the top of this file. (The backward of that evaluation is handed the fp64 reference's statistics, as the kernels
+# are. With BN_K / 2 save_mean takes 0.29 of its bar, with BN_K_SQ / 2 rstd 0.44.)
+BN_K = 64
+BN_K_SQ = 512
+U23 = 2.0 ** -23
+BN_RECOMPUTE_EPS = 1e-4  # NHWC ReLU with y = NULL: pre-activations this close to 0 may flip the recomputed mask
+BN_RECOMPUTE_CAP = 1e-3  # ... and at most this fraction of a case's elements may be that close
+
+
+def bn_map_bar(want, dtype):
+    want = np.abs(want)
+    return F32_TOL["atol"] + F32_TOL["rtol"] * want + (2.0 ** -8 * want if dtype == BF16 else 0.0)
+
+
+def bn_fwd_bars(ref, ins, k=BN_K, k_sq=BN_K_SQ):
+    """Per-channel bars of save_mean, rstd, scale, shift, running mean and running var."""
+    e, e2 = k * U23, k_sq * U23
+    a = lambda v: np.abs(v)
+    mean = e * (ref["abs_mean"] + a(ref["mean"]))
+    var = e2 * (ref["abs_var"] + a(ref["var"])) + 2 * a(ref["mean"] - ins["x"][:, 0]) * mean
+    rstd = 0.5 * ref["rstd"] / (ref["var"] + BN_EPS) * var + e * ref["rstd"]
+    scale = a(ins["gamma"]) * rstd + e * a(ref["scale"])
+    shift = a(ref["mean"]) * scale + a(ref["scale"]) * mean + e * (a(ins["beta"]) + a(ref["mean"] * ref["scale"]))
+    M = ins["x"].shape[1]
+    unb = M / (M - 1.0) if M > 1 else 1.0
+    run_mean = BN_MOM * mean + e * ((1 - BN_MOM) * a(ins["rm"]) + BN_MOM * a(ref["mean"]) + a(ref["run_mean"]))
+    run_var = BN_MOM * unb * var + e * ((1 - BN_MOM) * a(ins["rv"]) + BN_MOM * unb * ref["var"] + a(ref["run_var"]))
+    return dict(mean=mean, rstd=rstd, scale=scale, shift=shift, run_mean=run_mean, run_var=run_var)
+
+
+def bn_near_zero(ref, combo):
+    """(C, M) mask of the elements whose ReLU mask the recomputing backward may legitimately flip."""
+    if combo.act == "relu" and combo.y == "null":
+        return np.abs(ref["z"]) < BN_RECOMPUTE_EPS
+    return np.zeros(ref["z"].shape, dtype=bool)
+
+
+def bn_bwd_bars(ref, ins, combo, k=BN_K):
+    """Per-channel bars of dbeta and dgamma (with the summands of the elements bn_near_zero leaves out)."""
+    e = k * U23
+    near = bn_near_zero(ref, combo)
+    xhat = (ins["x"] - ref["stats_in"][0][:, None]) * ref["stats_in"][1][:, None]
+    extra_b = (np.abs(ins["dy"]) * near).sum(axis=1)
+    extra_g = (np.abs(ins["dy"] * xhat) * near).sum(axis=1)
+    return dict(dbeta=e * (ref["abs_dbeta"] + np.abs(ref["dbeta"])) + extra_b,
+                dgamma=e * (ref["abs_dgamma"] + np.abs(ref["dgamma"])) + extra_g)

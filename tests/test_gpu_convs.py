@@ -83,12 +83,14 @@ BN_CASES = [  # (N, C, H, W, layout)
     (4, 96, 8, 22, "nchw"),
     (5, 40, 4, 11, "nchw"),
     (2, 16, 5, 7, "nchw"),     # one group per channel (the fused single-launch kernels), V = 1
-    (48, 8, 8, 22, "nchw"),    # the trunk's 8 x 22 maps at B*N = 48: one group, V = 8, 8 vectors a thread
+    (48, 8, 8, 22, "nchw"),    # the trunk's 8 x 22 maps at B*N = 48: one group, V = 8, 1,056 vectors: 5 a thread
     (96, 8, 4, 11, "nchw"),    # 4 x 11 maps: one group, V = 4, 8 vectors a thread (register-resident)
     (2, 64, 100, 100, "nhwc"),
     (2, 256, 25, 25, "nhwc"),
-    (3, 24, 7, 9, "nhwc"),
+    (3, 24, 7, 9, "nhwc"),     # 256 % (24 / 8) != 0: not a channel count the kernels take -- the stock op
+    (3, 16, 7, 9, "nhwc"),     # ... and its sibling on the kernels
 ]
+BN_STOCK = {(3, 24, 7, 9, "nhwc")}
 
 
 def _bn_reference(x, w, b, rm, rv, eps, mom, act, res, dy):
@@ -108,7 +110,10 @@ def _bn_reference(x, w, b, rm, rv, eps, mom, act, res, dy):
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("act,with_res", [("none", False), ("swish", False), ("relu", False), ("relu", True)])
 @pytest.mark.parametrize("N,C,H,W,layout", BN_CASES)
-def test_bn_act_vs_fp64(N, C, H, W, layout, act, with_res, dtype):
+def test_bn_act_vs_fp64(N, C, H, W, layout, act, with_res, dtype, monkeypatch):
+    launched = []
+    real = Nm._lib.check
+    monkeypatch.setattr(Nm._lib, "check", lambda code, what: (launched.append(what), real(code, what))[1])
     g = torch.Generator().manual_seed(N * 1000 + C + H)
     x = (torch.randn(N, C, H, W, generator=g) * 2 + 3).to(dtype)  # offset mean: exercises the shifted sums
     res = torch.randn(N, C, H, W, generator=g).to(dtype) if with_res else None
@@ -126,6 +131,8 @@ def test_bn_act_vs_fp64(N, C, H, W, layout, act, with_res, dtype):
     assert y.dtype == dtype and y.is_contiguous(memory_format=mf)
     dy = torch.randn(y.shape, generator=g).to(dtype)
     y.backward(dy.to(DEV).contiguous(memory_format=mf))
+    # the kernels, not the stock fallback (but for the one case that says so)
+    assert launched == ([] if (N, C, H, W, layout) in BN_STOCK else ["lss_bn_fwd2", "lss_bn_bwd2"])
     ref = _bn_reference(x, bn.weight, bn.bias, rm0, rv0, bn.eps, bn.momentum, act, res, dy)
     tol = dict(rtol=1e-4, atol=1e-4) if dtype == torch.float32 else dict(rtol=2e-2, atol=3e-2)
     torch.testing.assert_close(y.detach().cpu().double(), ref[0], **tol)
@@ -493,7 +500,9 @@ def _bn_run(x, res, act, dy, seed):
 
 @pytest.mark.parametrize("spin", [0, 1])
 @pytest.mark.parametrize("act,with_res", [("swish", False), ("none", True), ("relu", False)])
-@pytest.mark.parametrize("N,C,H,W", [(48, 144, 32, 88), (48, 24, 32, 88), (48, 80, 16, 44), (16, 16, 33, 40)])
+@pytest.mark.parametrize("N,C,H,W", [(48, 144, 32, 88), (48, 24, 32, 88), (48, 80, 16, 44), (16, 16, 33, 40),
+                                     (5, 3, 48, 96),    # groups of 2 and 3 images, 7 vectors a thread: <8, 8>
+                                     (7, 3, 40, 88)])   # groups of 2, 2 and 3 images, 1,320 vectors: <8, 6>
 def test_bn_cluster_kernels_bit_identical(N, C, H, W, act, with_res, spin):
     """NCHW bf16 with several groups per channel: the one-launch cluster kernels (lss_bn_fwd2 / lss_bn_bwd2
     with a sync workspace) against the two-launch statistics + apply kernels, bit for bit -- outputs,

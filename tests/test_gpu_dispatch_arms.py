@@ -36,7 +36,9 @@ def _within(got: torch.Tensor, want: np.ndarray, bar: np.ndarray, what: str = ""
     g = got.float().cpu().numpy().astype(np.float64)
     assert g.shape == want.shape, (g.shape, want.shape)
     assert np.isfinite(g).all(), f"{what}: {np.count_nonzero(~np.isfinite(g))} elements not written or not finite"
-    over = np.abs(g - want) / bar
+    diff = np.abs(g - want)
+    with np.errstate(divide="ignore"):  # (an exact result meets any bar, a zero bar included; anything else over it is inf)
+        over = np.divide(diff, bar, out=np.zeros_like(diff), where=diff > 0)
     i = np.unravel_index(np.argmax(over), over.shape)
     assert over[i] <= 1.0, f"{what}: at {i} got {g[i]}, want {want[i]}, bar {bar[i]}"
 

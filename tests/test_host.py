@@ -570,5 +570,206 @@ def test_arm_references_fp32_margins():
         tol, wtol = A.dw_tols(A.F32)
         rooms[name] = max(_room(outs[0][0], outs[1][0], **tol), _room(outs[0][1], outs[1][1], **tol))
         rooms[name + "_dw"] = _room(outs[0][2], outs[1][2], **wtol)
+    # batch norm: the largest case of each family, bf16-exact inputs (the register and cluster kernels' dtype),
+    # fp32 arithmetic in numpy's pairwise order and one element after the other, against every bar
+    half = {"k": 0.0, "k_sq": 0.0}
+    for fam, cases in _bn_families().items():
+        c = max(cases, key=lambda c: c.N * c.H * c.W)
+        combo = A.BnCombo("swish", False, "y")
+        ins = A.bn_inputs(c, A.BF16, combo)
+        want = A.bn_reference(ins, combo, A.BF16)
+        for order in ("pairwise", "sequential"):
+            got = A.bn_reference(ins, combo, A.BF16, ft=np.float32, order=order, fed=want)
+            r = _bn_rooms(got, want, ins, combo)
+            print("bn", fam, c.N * c.H * c.W, order, {n: round(v, 3) for n, v in r.items()})
+            # the maps' bars are the project's, not chosen here: 4x room in numpy's order; y through statistics
+            # summed one element after the other over 32,800 elements still meets its bar (0.87 of it)
+            maps = max(r.pop(n) for n in ("y", "dx", "dres"))
+            assert maps <= (0.25 if order == "pairwise" else 1.0), (fam, order, maps)
+            rooms["bn_%s_%s" % (fam, order)] = max(r.values())
+            r = _bn_rooms(got, want, ins, combo, k=A.BN_K // 2)
+            half["k"] = max([half["k"]] + [r[n] for n in ("mean", "run_mean", "dbeta", "dgamma")])
+            r = _bn_rooms(got, want, ins, combo, k_sq=A.BN_K_SQ // 2)
+            half["k_sq"] = max([half["k_sq"]] + [r[n] for n in ("rstd", "scale", "shift", "run_var")])
+    assert min(half.values()) > 0.25, half  # BN_K and BN_K_SQ are the smallest powers of two that do
     print({k: round(v, 4) for k, v in rooms.items()})
     assert all(v <= 0.25 for v in rooms.values()), rooms
+
+
+# ---- batch norm (tests/arm_cases.py's BN section; tests/test_gpu_bn_arms.py runs it on the GPU)
+def _bn_families():
+    fams = {}
+    for c in A.BN_CASES:
+        for name in {c.f32, c.bf16} | set(c.bwd or ()):
+            fams.setdefault(name.split("<")[0], []).append(c)
+    return fams
+
+
+def _bn_rooms(got, want, ins, combo, k=A.BN_K, k_sq=A.BN_K_SQ):
+    """Largest |got - want| / bar of each per-channel output and each fp32 map of one evaluation."""
+    bars = dict(A.bn_fwd_bars(want, ins, k, k_sq), **A.bn_bwd_bars(want, ins, combo, k))
+    bars.update({n: A.bn_map_bar(want[n], A.F32) for n in ("y", "dx", "dres")})
+    return {n: float((np.abs(got[n].astype(np.float64) - want[n]) / bars[n]).max()) for n in bars}
+
+
+def _bn_arm(lib, pas, dtype, c, act="none"):
+    a = _lib.BnArm()
+    assert lib.lss_bn_arm(pas, dtype, c.layout, c.N, c.C, c.H * c.W, A.ACT[act], c.G, int(c.sync),
+                          ctypes.byref(a)) == 0, c
+    assert a.launches == {"nhwc": 3, "two_pass": 2}.get(A.BN_FAMILIES[a.family], 1), c
+    assert a.blocks == (c.G if c.layout == 1 else c.C * c.G) and a.chunks == 0, c
+    return A.bn_arm_name(a.family, a.v, a.it, a.relu)
+
+
+def test_arm_table_covers_every_batch_norm_arm():
+    lib = _lib.load()
+    for pas in (A.BN_FWD, A.BN_BWD):
+        for code, dt in ((_lib.F32, A.F32), (_lib.BF16, A.BF16)):
+            hit = set()
+            for c in A.BN_CASES:
+                for combo in A.bn_combos(c, pas):
+                    got = _bn_arm(lib, pas, code, c, combo.act)
+                    assert got == A.bn_case_arm(c, dt, pas, combo.act), (c, pas, dt, got)
+                    hit.add(got)
+            assert hit == A.bn_arms(pas, dt), (pas, dt, hit ^ A.bn_arms(pas, dt))
+    assert lib.lss_bn_arm(0, 0, 0, 2, 3, 8, 0, 1, 0, None) == _EINVAL and _lib.BnArm().family == 0
+    assert len(A.BN_FAMILIES) == 7  # LSS_BN_ARM_FAMILIES
+    # each bound of the rule: its two neighbours are in the table and land on different arms
+    notes = [c.note for c in A.BN_CASES]
+    for lo, hi, dt, pas in A.BN_BOUNDARIES:
+        a, b = (next(c for c in A.BN_CASES if c.note == n and c.layout == 0) for n in (lo, hi))
+        assert lo in notes and hi in notes
+        assert A.bn_case_arm(a, dt, pas) != A.bn_case_arm(b, dt, pas), (lo, hi)
+    one = [c for c in A.BN_CASES if c.layout == 0 and c.G == 1]
+    cnt = lambda c: c.N * c.H * c.W // (8 if c.H * c.W % 8 == 0 else 4)  # noqa: E731
+    assert {1023, 1024, 1025, 1280, 1281, 2047, 2048, 2049} <= {cnt(c) for c in one if c.H * c.W % 8 == 0}
+    assert {1023, 1024, 1025, 2048, 2049} <= {cnt(c) for c in one if c.H * c.W % 8 == 4}
+    # every register instantiation has a case whose vectors per image (>= 3) do not divide the block
+    for arm in ("fused_reg<8,4>", "fused_reg<8,5>", "fused_reg<8,8>", "fused_reg<4,4>", "fused_reg<4,8>"):
+        per = [c.H * c.W // int(arm[10]) for c in one if c.bf16 == arm]
+        assert any(p >= 3 and 256 % p for p in per), (arm, per)
+    # the cluster's backward families differ from the forward's between 1024 and 2304 blocks
+    assert any(c.bwd and c.bwd[1] != c.bf16 for c in A.BN_CASES)
+    # two-pass: every V with uneven groups and one image a group, the second lap of the fold, an empty group
+    for v in (8, 4, 1):
+        tp = [c for c in A.BN_CASES if c.bf16 == "two_pass<%d>" % v and c.f32 == c.bf16 and not c.sync]
+        assert any(c.N % c.G for c in tp) and any(c.G == c.N for c in tp), v
+    assert any(c.G > 64 and c.layout == 0 for c in A.BN_CASES) and any(c.G > c.N and c.layout == 0 for c in A.BN_CASES)
+    # NHWC: octets a row below, at and above a wave; rows below a pass, off and on the unrolled pass; group counts
+    nh = [c for c in A.BN_CASES if c.layout == 1]
+    assert {c.C for c in nh} == {8, 16, 64, 512, 2048} and {1, 2, 17, 1025} == {c.G for c in nh}
+    for C in (8, 16, 64, 512, 2048):
+        step, rows = 256 // (C // 8), {c.N * c.H * c.W for c in nh if c.C == C}
+        assert any(m % (4 * step) for m in rows) and any(m % (4 * step) == 0 for m in rows), C
+        assert step == 1 or any(m < step for m in rows), C
+    assert any(c.G > c.N * c.H * c.W for c in nh)
+    # bad pass, dtype, layout, sizes, activation, group counts
+    a = ctypes.byref(_lib.BnArm())
+    good = (0, 1, 0, 4, 3, 8, 0, 2, 1)
+    assert lib.lss_bn_arm(*good, a) == 0
+    for i, bad in ((0, 3), (0, -1), (1, 2), (2, 2), (3, 0), (4, 0), (5, 0), (5, -8), (6, 3), (7, 0)):
+        args = list(good)
+        args[i] = bad
+        assert lib.lss_bn_arm(*args, a) == _EINVAL, (i, bad)
+    assert lib.lss_bn_arm(0, 1, 0, 1 << 15, 1 << 10, 1 << 6, 0, 1, 0, a) == _EINVAL  # N C HW >= 2^31
+    assert lib.lss_bn_arm(0, 1, 1, 2, 24, 8, 0, 1, 0, a) == _EINVAL   # NHWC: 256 % (C / 8) != 0
+    assert lib.lss_bn_arm(0, 1, 1, 2, 16, 8, 0, 4096, 0, a) == 0
+    assert lib.lss_bn_arm(1, 1, 1, 2, 16, 8, 0, 4097, 0, a) == _EINVAL  # NHWC: at most 4096 groups
+    assert lib.lss_bn_arm(2, 1, 1, 2, 16, 8, 0, 0, 0, a) == 0  # eval does not read ngroups
+    x, y, dy, dx = _fake(0), _fake(1), _fake(12), _fake(13)
+    st = _fake(8)
+    # the entry points agree on 4097 groups (made-up addresses: refused before any launch)
+    assert lib.lss_bn_fwd2(x, None, 1, 1, 2, 16, 8, _fake(2), _fake(3), 1e-5, 0.1, None, None, None, 0, 4097, _fake(7),
+                           st, st + 64, st + 128, st + 192, y, None, None) == _EINVAL
+    assert lib.lss_bn_bwd2(dy, x, y, 1, 1, 2, 16, 8, st + 128, st + 192, st, st + 64, 0, 4097, _fake(7), _fake(9), None,
+                           None, dx, None, None, None) == _EINVAL
+    # the backward of swish with a residual does not exist: refused, not computed without the residual
+    assert lib.lss_bn_bwd2(dy, x, y, 1, 0, 2, 3, 8, st + 24, st + 36, st, st + 12, 2, 1, _fake(7), _fake(9), None, None,
+                           dx, _fake(14), None, None) == _EINVAL
+    # lss_bn_groups' choice is what the through-Python cases assume
+    for c in A.BN_CASES:
+        if c.py:
+            assert lib.lss_bn_groups(c.N, c.C, c.H * c.W, c.layout) == c.G, c
+    assert lib.lss_bn_groups(2, 3, 64 * 128, 0) == 2 and lib.lss_bn_groups(3, 3, 8 * 683, 0) == 2  # ngroups 1: ABI only
+
+
+def test_bn_eval_cases_cover_every_eval_arm():
+    """tests/test_gpu_bn_eval.py's CASES (read from its source: the module needs a GPU to import) reach V in
+    {8, 4, 1} x dtype for NCHW, NHWC, several chunks a channel and more units than the 1,024 blocks."""
+    import ast
+    src = open(os.path.join(REPO, "tests", "test_gpu_bn_eval.py")).read()
+    node = next(n for n in ast.parse(src).body if isinstance(n, ast.Assign) and getattr(n.targets[0], "id", "") == "CASES")
+    cases = ast.literal_eval(node.value)
+    lib, hit, over = _lib.load(), set(), set()
+    for layout, (N, C, H, W) in cases:
+        for code in (_lib.F32, _lib.BF16):
+            a = _lib.BnArm()
+            assert lib.lss_bn_arm(A.BN_EVAL, code, int(layout == "nhwc"), N, C, H * W, 0, 1, 0, ctypes.byref(a)) == 0
+            assert a.launches == 1 and a.it == 0 and a.relu == 0
+            hit.add((A.bn_arm_name(a.family, a.v, 0, 0), code))
+            if a.family == A.BN_FAMILIES.index("eval_nchw") and C * a.chunks > a.blocks:
+                over.add("nchw")
+            if a.family == A.BN_FAMILIES.index("eval_nhwc") and a.blocks == 1024:
+                over.add("nhwc")
+            if a.chunks > 1:
+                over.add("chunks")
+    want = {("eval_nchw<%d>" % v, code) for v in (4, 1) for code in (_lib.F32, _lib.BF16)}
+    want |= {("eval_nchw<8>", _lib.BF16), ("eval_nhwc", _lib.F32), ("eval_nhwc", _lib.BF16)}  # fp32 never takes V 8
+    assert hit == want, hit ^ want
+    assert over == {"nchw", "nhwc", "chunks"}
+
+
+def test_bn_reference_is_batch_norm():
+    """arm_cases.bn_reference against F.batch_norm + autograd in fp64, on cases of every layout and activation."""
+    import torch.nn.functional as Fn
+    picks = [c for c in A.BN_CASES if c.note in ("V 1", "groups of 1, 2, 2", "15 rows < 32 a pass")]
+    assert len(picks) >= 3
+    for c in picks:
+        for combo in (A.BnCombo("none", True, "y"), A.BnCombo("swish", False, "y"), A.BnCombo("relu", True, "y")):
+            ins = A.bn_inputs(c, A.F32, combo)
+            ref = A.bn_reference(ins, combo, A.F32)
+            t = lambda a: torch.from_numpy(a.reshape(c.C, c.N, -1).transpose(1, 0, 2).copy())  # noqa: E731
+            x = t(ins["x"]).requires_grad_(True)
+            w, b = (torch.from_numpy(ins[k]).requires_grad_(True) for k in ("gamma", "beta"))
+            r = t(ins["res"]).requires_grad_(True) if combo.res else None
+            rm, rv = torch.from_numpy(ins["rm"].copy()), torch.from_numpy(ins["rv"].copy())
+            z = Fn.batch_norm(x, rm, rv, w, b, training=True, momentum=A.BN_MOM, eps=A.BN_EPS)
+            z = z + r if combo.res else z
+            y = {"none": z, "relu": Fn.relu(z), "swish": Fn.silu(z)}[combo.act]
+            y.backward(t(ins["dy"]))
+            back = lambda g: g.detach().numpy().transpose(1, 0, 2).reshape(c.C, -1)  # noqa: E731
+            # (the reference's backward starts from fp32-rounded statistics: 2^-24 relative)
+            for got, want, tol in ((ref["y"], back(y), 1e-12), (ref["run_mean"], rm.numpy(), 1e-12),
+                                   (ref["run_var"], rv.numpy(), 1e-12), (ref["dx"], back(x.grad), 1e-5),
+                                   (ref["dbeta"], b.grad.numpy(), 1e-5), (ref["dgamma"], w.grad.numpy(), 1e-5)):
+                np.testing.assert_allclose(got, want, rtol=tol, atol=tol)
+            if combo.res:
+                np.testing.assert_allclose(ref["dres"], back(r.grad), rtol=1e-12, atol=1e-12)
+
+
+def test_bn_bars_notice_a_left_out_element_and_the_recompute_cap_holds():
+    """For every case, dtype and combination: a reference that leaves the last element of each (channel, group)
+    range out of its sums misses the bar on save_mean and on dbeta or dgamma: in every channel where the builder
+    pinned the range ends; on save_mean in 99 % of the channels and on dbeta or dgamma in some channel otherwise. The pinned ends are at least one standard
+    deviation off their channel's mean. And the elements the ReLU recompute arm may leave out of dx stay under
+    the cap."""
+    for c in A.BN_CASES:
+        lasts = [b for _, b in A.bn_ranges(c)]
+        for dt in (A.F32, A.BF16):
+            for combo in A.bn_combos(c, A.BN_BWD):
+                ins = A.bn_inputs(c, dt, combo)
+                ref = A.bn_reference(ins, combo, dt)
+                cut = A.bn_reference(ins, combo, dt, drop=lasts)
+                fb, bb = A.bn_fwd_bars(ref, ins), A.bn_bwd_bars(ref, ins, combo)
+                seen = np.abs(cut["mean"] - ref["mean"]) > fb["mean"]
+                # (unpinned: a last element that happens to equal K, the sums' shift, adds nothing to them)
+                assert seen.all() if A.bn_pinned(c) else seen.mean() >= 0.99, (c, dt, combo)
+                miss = (np.abs(cut["dbeta"] - ref["dbeta"]) > bb["dbeta"]) | (np.abs(cut["dgamma"] - ref["dgamma"]) > bb["dgamma"])
+                assert miss.all() if A.bn_pinned(c) else miss.any(), (c, dt, combo, miss)
+                if A.bn_pinned(c):
+                    ends = np.unique(np.array(A.bn_ranges(c)).reshape(-1))
+                    off = np.abs(ins["x"][:, ends] - ref["mean"][:, None]) * ref["rstd"][:, None]
+                    assert off.min() >= 1.0 and np.abs(ins["dy"][:, ends]).min() >= 1.0, (c, off.min())
+                near = A.bn_near_zero(ref, combo)
+                assert near.sum() <= A.BN_RECOMPUTE_CAP * near.size, (c, dt, int(near.sum()))
+                assert combo.y == "null" or not near.any()

@@ -47,6 +47,33 @@ int lss_resample_coeffs(int32_t in_size, int32_t out_size, int32_t* table);
 int lss_simbev_images(const uint8_t* src, int32_t n, int32_t src_h, int32_t src_w, const lss_img_aug_t* aug,
                       const int32_t* tables, int32_t out_h, int32_t out_w, float* out, void* stream);
 
+/* (ABI 36) One camera image's photometric augmentation: colour jitter as an affine map of (R, G, B) and sensor
+ * noise. 64 bytes, one per image, parallel to lss_img_aug_t[n]. */
+typedef struct lss_img_photo {
+    float    m[9];                 /* row-major 3x3 colour matrix on (R, G, B) in 0..255 units */
+    float    t[3];                 /* offset, same units */
+    float    noise;                /* noise amplitude sigma, 0..255 units; 0 = none (no RNG work) */
+    uint32_t seed[2];              /* Philox key of this image's noise */
+    uint32_t pad;
+} lss_img_photo_t;
+
+/* lss_simbev_images with the photometric augmentation photo[n] (DEVICE memory) applied to the resampled integer
+ * (r, g, b) of each output pixel, before the normalisation. A pixel is "inside" when it passed the rotation's
+ * inside test and the crop-inside-the-resized-image test; a fill pixel stays the reference's black (the
+ * normalisation of 0), bit for bit as lss_simbev_images writes it. For an inside pixel pix = y * out_w + x of
+ * image img, every product and sum one correctly rounded fp32 operation in this order (no FMA):
+ *   v[c] = ((m[3c] r + m[3c+1] g) + m[3c+2] b) + t[c]
+ *   if noise != 0:  w = philox4x32_10(key = seed, counter = (pix, img, 0, 0)); s_c = the sum of the four bytes of
+ *                   word c of w (0..1020); z_c = (float)(s_c - 510) * 0.006765875f (Irwin-Hall, n = 4: mean 0,
+ *                   variance 1, |z| <= 3.46); v[c] = v[c] + noise * z_c
+ *   v[c] = fminf(fmaxf(v[c], 0), 255)                       the one clamp
+ *   out = ((v[c] / 255) - mean[c]) / std[c]                 as lss_simbev_images
+ * The neutral record (m = I, t = 0, noise = 0) gives lss_simbev_images' output bit for bit. Same checks and codes
+ * as lss_simbev_images (-1 bad argument, -2 n > 65535), and -1 for a NULL photo. */
+int lss_simbev_images_photo(const uint8_t* src, int32_t n, int32_t src_h, int32_t src_w, const lss_img_aug_t* aug,
+                            const lss_img_photo_t* photo, const int32_t* tables, int32_t out_h, int32_t out_w,
+                            float* out, void* stream);
+
 /* BEV labels: bev (n, n_classes, X, Y) uint8 (any value > 0 = set) -> out (n, 1, X, Y) fp32 =
  * flipud((bev[1] > 0) | (bev[2] > 0) | (bev[3] > 0)). n_classes >= 4. */
 int lss_simbev_vehicle_mask(const uint8_t* bev, int32_t n, int32_t n_classes, int32_t X, int32_t Y, float* out,

@@ -18,7 +18,7 @@ _LAZY = {
     "get_val_info": "tools", "val_accumulate": "tools",
     "FocalLoss": "tools", "seg_metrics_accumulate": "tools", "seg_metrics_summary": "tools",
     "SoftmaxLoss": "tools", "confusion_accumulate": "tools", "confusion_summary": "tools", "argmax_classes": "tools",
-    "Predictor": "predict", "LRSchedule": "optim",
+    "Predictor": "predict", "LRSchedule": "optim", "photo_matrix": "simbev",
     "train": "trainer", "BatchStager": "staging", "EvalStep": "train_step", "QuickCumsum": "tools", "cumsum_trick": "tools",
 }
 

@@ -18,7 +18,7 @@ DEBUG_LIB_PATH = os.path.join(_HERE, "liblss_hip_debug.so")  # LSS_DEBUG=1: devi
 
 F32, BF16 = 0, 1
 NCHW, NHWC = 0, 1
-ABI_VERSION = 35
+ABI_VERSION = 36
 
 
 class Dims(ctypes.Structure):
@@ -32,6 +32,12 @@ class ImgAug(ctypes.Structure):
                 ("rs_h", ctypes.c_int32), ("crop", ctypes.c_int32 * 4), ("flip", ctypes.c_int32),
                 ("rot_mode", ctypes.c_int32), ("affine", ctypes.c_int32 * 6), ("h_off", ctypes.c_int32),
                 ("h_ksize", ctypes.c_int32), ("v_off", ctypes.c_int32), ("v_ksize", ctypes.c_int32)]
+
+
+class ImgPhoto(ctypes.Structure):
+    """lss_img_photo_t of include/lss_simbev.h (64 bytes: 16 words, the layout of a sample's (N, 16) fp32 rows)."""
+    _fields_ = [("m", ctypes.c_float * 9), ("t", ctypes.c_float * 3), ("noise", ctypes.c_float),
+                ("seed", ctypes.c_uint32 * 2), ("pad", ctypes.c_uint32)]
 
 
 class BnArm(ctypes.Structure):
@@ -98,6 +104,7 @@ SIGNATURES = {
     "lss_resample_ksize": (ctypes.c_int, [_i32, _i32]),
     "lss_resample_coeffs": (ctypes.c_int, [_i32, _i32, _p]),
     "lss_simbev_images": (ctypes.c_int, [_p, _i32, _i32, _i32, _p, _p, _i32, _i32, _p, _p]),
+    "lss_simbev_images_photo": (ctypes.c_int, [_p, _i32, _i32, _i32, _p, _p, _p, _i32, _i32, _p, _p]),
     "lss_simbev_vehicle_mask": (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _p, _p]),
     "lss_simbev_class_masks": (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _p, _i32, _p, _p]),
     "lss_simbev_class_masks_warp": (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _p, _i32, _p, _p, _p]),

@@ -127,6 +127,21 @@ __device__ __forceinline__ uint4 keep_if(bool c, uint4 v) {
 }
 __device__ __forceinline__ float keep_if(bool c, float v) { return __uint_as_float(__float_as_uint(v) & keep_mask(c)); }
 
+// ---- Philox4x32-10 (Salmon et al., SC'11): 10 rounds of the two multiplies and key bumps; a pure function of
+// (key, counter). Integer only: the same words under either contraction setting. The dropout kernels
+// (lss_elementwise.hip) and the image kernel's sensor noise (lss_simbev.hip) share it.
+__device__ __forceinline__ uint4 philox4x32(uint2 key, uint4 c) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned lo0 = 0xD2511F53u * c.x, hi0 = __umulhi(0xD2511F53u, c.x);
+        const unsigned lo1 = 0xCD9E8D57u * c.z, hi1 = __umulhi(0xCD9E8D57u, c.z);
+        c = make_uint4(hi1 ^ c.y ^ key.x, lo1, hi0 ^ c.w ^ key.y, lo0);
+        key.x += 0x9E3779B9u;
+        key.y += 0xBB67AE85u;
+    }
+    return c;
+}
+
 // values handed from block to block inside a launch: write-through stores, L1-bypassing loads
 __device__ __forceinline__ unsigned long long ld_agent(const unsigned long long* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

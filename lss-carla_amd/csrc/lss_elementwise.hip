@@ -47,19 +47,8 @@ __global__ __launch_bounds__(kBlock) void k_scale_add(const uint4* __restrict__ 
 
 
 // ---- dropout (CamEncode.dropout, src/models.py:44, 53) on a counter-based RNG, laid out for the next kernel
-// Philox4x32-10 (Salmon et al., SC'11): 10 rounds of the two multiplies and key bumps; a pure function of
-// (key, counter), so the backward regenerates the forward's mask from the same seed.
-__device__ __forceinline__ uint4 philox4x32(uint2 key, uint4 c) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned lo0 = 0xD2511F53u * c.x, hi0 = __umulhi(0xD2511F53u, c.x);
-        const unsigned lo1 = 0xCD9E8D57u * c.z, hi1 = __umulhi(0xCD9E8D57u, c.z);
-        c = make_uint4(hi1 ^ c.y ^ key.x, lo1, hi0 ^ c.w ^ key.y, lo0);
-        key.x += 0x9E3779B9u;
-        key.y += 0xBB67AE85u;
-    }
-    return c;
-}
+// philox4x32 (lss_device.h) is a pure function of (key, counter), so the backward regenerates the forward's
+// mask from the same seed.
 
 // Elements of 16-B vector v (8 bf16 or 4 fp32) kept: bit j = element j; uniform u = top 24 bits / 2^24,
 // kept when u < keep (P = keep). Counter (v, 0, 0, 0): 4 draws, a second block (v, 0, 1, 0) for bf16.

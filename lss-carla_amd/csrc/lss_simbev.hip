@@ -9,6 +9,7 @@
 //   resize   Resample.c's two passes evaluated at that one pixel: for each vertical tap (source row),
 //            the horizontal pass's value at that row, clipped to uint8 as Pillow's intermediate image
 //            stores it, then the vertical accumulation, clipped again;
+//   photo    (lss_simbev_images_photo only) colour matrix + offset, sensor noise, one clamp to [0, 255], fp32;
 //   normalize ToTensor (/255) and Normalize((x - mean) / std), fp32, IEEE division.
 // The horizontal values are recomputed per output row (<= ksize_v times each): a few hundred integer
 // MACs per pixel, against reading a 322 KB image -- the kernel is bound by its fp32 output writes.
@@ -54,10 +55,45 @@ __device__ __forceinline__ void hpass(const uint8_t* __restrict__ img, int src_w
     rgb[2] = clip8(a2);
 }
 
+// Photometric augmentation (ABI 36), on the pixel's integer rgb while it is in registers: the colour matrix and
+// offset of the image's lss_img_photo_t, the sensor noise, one clamp, then the normalisation below. Only for a
+// pixel that came from the source image ("lit": inside the rotation and inside the resized image); a fill pixel
+// stays the reference's black. Every product and sum is one correctly rounded fp32 operation in the order written
+// (the numpy restatement of the tests does the same roundings). The record is uniform over the block (blockIdx.y).
+constexpr float kNoiseInvStd = 0.006765875f;  // (float)(1 / sqrt(4 * (256^2 - 1) / 12)): four bytes summed, variance 1
+
+__device__ __forceinline__ int byte_sum(unsigned w) {
+    return (int)((w & 255u) + ((w >> 8) & 255u) + ((w >> 16) & 255u) + (w >> 24));
+}
+
+__device__ __forceinline__ void photo_apply(const lss_img_photo_t* __restrict__ q, int pix, int img, float* v) {
+    const float r = v[0], g = v[1], b = v[2];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+        v[c] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(q->m[3 * c], r), __fmul_rn(q->m[3 * c + 1], g)),
+                                   __fmul_rn(q->m[3 * c + 2], b)),
+                         q->t[c]);
+    const float sigma = q->noise;
+    if (sigma != 0.0f) {
+        const uint4 w = philox4x32(make_uint2(q->seed[0], q->seed[1]), make_uint4((unsigned)pix, (unsigned)img, 0u, 0u));
+        const unsigned word[3] = {w.x, w.y, w.z};
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float z = __fmul_rn((float)(byte_sum(word[c]) - 510), kNoiseInvStd);
+            v[c] = __fadd_rn(v[c], __fmul_rn(sigma, z));
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = fminf(fmaxf(v[c], 0.0f), 255.0f);
+}
+
+// kPhoto false: lss_simbev_images, `photo` not read. true: lss_simbev_images_photo.
+template <bool kPhoto>
 __global__ __launch_bounds__(kThreads) void k_simbev_images(const uint8_t* __restrict__ src, int src_h, int src_w,
                                                             const lss_img_aug_t* __restrict__ augs,
                                                             const int32_t* __restrict__ tables, int out_h,
-                                                            int out_w, float* __restrict__ out) {
+                                                            int out_w, float* __restrict__ out,
+                                                            const lss_img_photo_t* __restrict__ photo) {
     const int img = blockIdx.y;
     const int pix = blockIdx.x * kThreads + threadIdx.x;
     if (pix >= out_h * out_w) return;
@@ -66,6 +102,7 @@ __global__ __launch_bounds__(kThreads) void k_simbev_images(const uint8_t* __res
     int rgb[3] = {0, 0, 0};
     int xs = x, ys = y;
     bool inside = true;
+    [[maybe_unused]] bool lit = false;  // the pixel comes from the source image (kPhoto)
     if (p.rot_mode == 1) {  // ROTATE_180
         xs = out_w - 1 - x;
         ys = out_h - 1 - y;
@@ -87,6 +124,7 @@ __global__ __launch_bounds__(kThreads) void k_simbev_images(const uint8_t* __res
         if (p.flip) xs = out_w - 1 - xs;
         const int xr = xs + p.crop[0], yr = ys + p.crop[1];
         if (xr >= 0 && xr < p.rs_w && yr >= 0 && yr < p.rs_h) {
+            lit = true;
             const uint8_t* im = src + (size_t)img * src_h * src_w * 3;
             const int32_t* th = tables + p.h_off;
             if (p.v_ksize == 0) {
@@ -113,10 +151,20 @@ __global__ __launch_bounds__(kThreads) void k_simbev_images(const uint8_t* __res
     const float mean[3] = {0.485f, 0.456f, 0.406f};
     const float stdv[3] = {0.229f, 0.224f, 0.225f};
     float* o = out + (size_t)img * 3 * out_h * out_w + pix;
+    if constexpr (kPhoto) {
+        float val[3] = {(float)rgb[0], (float)rgb[1], (float)rgb[2]};
+        if (lit) photo_apply(photo + img, pix, img, val);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float v = __fdiv_rn((float)rgb[c], 255.0f);
-        o[(size_t)c * out_h * out_w] = __fdiv_rn(__fsub_rn(v, mean[c]), stdv[c]);
+        for (int c = 0; c < 3; ++c) {
+            const float v = __fdiv_rn(val[c], 255.0f);
+            o[(size_t)c * out_h * out_w] = __fdiv_rn(__fsub_rn(v, mean[c]), stdv[c]);
+        }
+    } else {  // (the statements lss_simbev_images has always compiled from: its instruction stream is unchanged)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float v = __fdiv_rn((float)rgb[c], 255.0f);
+            o[(size_t)c * out_h * out_w] = __fdiv_rn(__fsub_rn(v, mean[c]), stdv[c]);
+        }
     }
 }
 
@@ -384,8 +432,20 @@ int lss_simbev_images(const uint8_t* src, int32_t n, int32_t src_h, int32_t src_
     if (!src || !aug || !tables || !out || n <= 0 || src_h <= 0 || src_w <= 0 || out_h <= 0 || out_w <= 0) return -1;
     if (n > 65535) return -2;
     const dim3 grid((unsigned)((out_h * out_w + kThreads - 1) / kThreads), (unsigned)n);
-    hipLaunchKernelGGL(k_simbev_images, grid, dim3(kThreads), 0, (hipStream_t)stream, src, src_h, src_w, aug, tables,
-                       out_h, out_w, out);
+    hipLaunchKernelGGL(k_simbev_images<false>, grid, dim3(kThreads), 0, (hipStream_t)stream, src, src_h, src_w, aug,
+                       tables, out_h, out_w, out, (const lss_img_photo_t*)nullptr);
+    return launch_status();
+}
+
+int lss_simbev_images_photo(const uint8_t* src, int32_t n, int32_t src_h, int32_t src_w, const lss_img_aug_t* aug,
+                            const lss_img_photo_t* photo, const int32_t* tables, int32_t out_h, int32_t out_w,
+                            float* out, void* stream) {
+    if (!src || !aug || !photo || !tables || !out || n <= 0 || src_h <= 0 || src_w <= 0 || out_h <= 0 || out_w <= 0)
+        return -1;
+    if (n > 65535) return -2;
+    const dim3 grid((unsigned)((out_h * out_w + kThreads - 1) / kThreads), (unsigned)n);
+    hipLaunchKernelGGL(k_simbev_images<true>, grid, dim3(kThreads), 0, (hipStream_t)stream, src, src_h, src_w, aug,
+                       tables, out_h, out_w, out, photo);
     return launch_status();
 }
 

@@ -42,6 +42,7 @@ state_dict): build it on a model no training step is bound to. The hot path has 
                                     [--weights auto|ema|model] [--valid_mask none|grid|fov] [--fov_z 0.0[,1.5,...]]
                                     [--drop_cams front,back_left] [--drop_each 0|1]
                                     [--exclusive 0|1] [--class_weight w0,...,wK]
+                                    [--photo "brightness=-40,contrast=0.8,noise=8"]
 
 runs the val split through ``BatchStager`` and the Predictor and writes one uint8 mask array per sample
 (``DIR/<index>.npy``, (K, X, Y)) and ``DIR/metrics.json``: loss, IoU and per-class IoU from get_val_info's
@@ -63,6 +64,10 @@ model of exclusive classes: the labels are the painted class map (simbev.class_i
 ``drop_each`` entry -- carries ``tools.confusion_summary``'s keys (loss, iou over the foreground classes, iou_per_class,
 miou_all, pixel_acc, precision / recall per class, confusion) from ``lss_confusion_accum``. ``--threshold``,
 ``--pos_weight``, ``--loss focal``, ``--focal_*`` and ``--iou_thresholds`` with it are errors before anything is built.
+``--photo "brightness=-40,contrast=0.8,noise=8"`` (entries: brightness, contrast, saturation, hue, noise, seed) runs the
+split with that one photometric shift applied to every image by the staging stream's image kernel
+(``lss_simbev_images_photo``; the loader's ``photo_fixed``): how the metrics move at dusk, or with a noisy sensor.
+``metrics.json`` gains ``photo`` (the parsed dict); without the flag nothing changes.
 """
 from __future__ import annotations
 
@@ -386,6 +391,34 @@ def parse_drop_cams(text) -> list:
     return sorted(out)
 
 
+def parse_photo(text):
+    """``--photo "brightness=-40,contrast=0.8,noise=8"`` -> {"brightness": -40.0, "contrast": 0.8, "noise": 8.0}: the
+    loader's ``photo_fixed`` dict (entries brightness, contrast, saturation, hue, noise: numbers; seed: an integer).
+    None or empty: None. A dict passes through the same checks. ValueError for an unknown entry or a bad value."""
+    from .simbev import photo_fixed_record
+    if text is None or (isinstance(text, str) and not text.strip()):
+        return None
+    if isinstance(text, dict):
+        out = dict(text)
+    else:
+        out = {}
+        for part in str(text).split(","):
+            if not part.strip():
+                continue
+            name, eq, value = part.partition("=")
+            name = name.strip()
+            if not eq or not value.strip() or name in out:
+                raise ValueError(f"--photo {text!r}: name=value entries, each once, comma separated")
+            try:
+                out[name] = int(value) if name == "seed" else float(value)
+            except ValueError:
+                raise ValueError(f"--photo {text!r}: {name}={value.strip()!r} is not a number") from None
+    if not out:
+        return None
+    photo_fixed_record({"photo_fixed": out})  # (unknown entries and bad values fail here)
+    return out
+
+
 def parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="python -m lss_carla_amd.predict",
                                 description="Run a trained LSS over a SimBEV val split on the MI355X: masks and metrics")
@@ -421,6 +454,8 @@ def parser() -> argparse.ArgumentParser:
                    help="1: exclusive classes (argmax class maps in DIR/preds/, confusion-matrix metrics); needs --label_groups")
     p.add_argument("--class_weight", type=str, default=None,
                    help="--exclusive 1: the loss's weight per class, the background first: w0,...,wK (default all 1)")
+    p.add_argument("--photo", type=str, default=None,
+                   help='one photometric shift for every image: "brightness=-40,contrast=0.8,saturation=1,hue=0,noise=8,seed=0"')
     p.add_argument("--gpuid", type=int, default=0)
     p.add_argument("--nworkers", type=int, default=4)
     p.add_argument("--H", type=int, default=224)
@@ -459,6 +494,7 @@ def predict(a, grid_conf=None, data_aug_conf=None, model: Optional[torch.nn.Modu
             getattr(a, "focal_alpha", None), getattr(a, "iou_thresholds", None) or None)
     elif getattr(a, "class_weight", None) is not None:
         raise ValueError("--class_weight needs --exclusive 1")
+    photo = parse_photo(getattr(a, "photo", None))  # (a bad entry fails before anything is built)
     if a.gpuid < 0:
         raise RuntimeError("lss_carla_amd.predict: needs an MI355X (the hot path has no CPU fallback)")
     dev = _require_gpu(f"cuda:{a.gpuid}")
@@ -475,6 +511,8 @@ def predict(a, grid_conf=None, data_aug_conf=None, model: Optional[torch.nn.Modu
     torch.backends.cudnn.benchmark = bool(a.miopen_find)
     gc, dac = confs(a)
     grid_conf, data_aug_conf = grid_conf or gc, data_aug_conf or dac
+    if photo is not None:  # the validation loader then emits that record for every image (simbev.photo_fixed_records)
+        data_aug_conf = {**data_aug_conf, "photo_fixed": photo}
     loss_kind = getattr(a, "loss", "bce")
     pw_arg = getattr(a, "pos_weight", None)
     pos_weight, focal = _loss_setup(loss_kind, None if pw_arg is None else parse_per_class(pw_arg, "--pos_weight"),
@@ -508,7 +546,8 @@ def predict(a, grid_conf=None, data_aug_conf=None, model: Optional[torch.nn.Modu
     stager = BatchStager(data_aug_conf["final_dim"], a.bsz, len(simbev.CAMERA_ORDER),
                          (data_aug_conf["H"], data_aug_conf["W"]), grid_conf, dev, label_groups=groups,
                          **({} if mask_mode is None else {"valid_mask": mask_mode, "fov_z": fov_z}),
-                         **({"exclusive": True} if exclusive else {}))
+                         **({"exclusive": True} if exclusive else {}),
+                         **({"photo": True} if simbev.photo_enabled(data_aug_conf) else {}))
     p = Predictor(model, a.bsz, dev, amp_dtype=amp_dtype, threshold=threshold, graph=bool(a.graph), stager=stager,
                   **({"camera_mask": True} if use_mask else {}), **({"exclusive": True} if exclusive else {}))
     if K > 1 or not tools.is_scalar_weight(pos_weight):
@@ -635,6 +674,8 @@ def predict(a, grid_conf=None, data_aug_conf=None, model: Optional[torch.nn.Modu
                 "frames_per_s": frames / elapsed if frames and elapsed > 0 else None}
     if mask_mode is not None:
         info.update({"valid_mask": mask_mode, "fov_z": list(fov_z), "valid_fraction": valid_fraction})
+    if photo is not None:
+        info["photo"] = photo
     if use_mask:
         info["dropped_cams"] = [simbev.CAMERA_ORDER[c] for c in dropped]
     if drop_each:

@@ -10,7 +10,9 @@ Where the work runs:
                              (``sample_augmentation``, np.random, src/data_simbev.py:119-145) and the
                              post-homography arithmetic (torch, src/tools.py:130-142), the BEV npz read
   device (main process)      ``lss_simbev_images``: Image.resize (bicubic) -> crop -> flip -> rotate
-                             -> ToTensor -> Normalize per camera, bit for bit with Pillow / torchvision;
+                             -> ToTensor -> Normalize per camera, bit for bit with Pillow / torchvision
+                             (``lss_simbev_images_photo``: the same with colour jitter and sensor noise on the
+                             resampled pixel, for a conf with ``photo_*`` keys);
                              ``lss_simbev_vehicle_mask``: classes 1-3 merged + np.flipud (or, with
                              ``label_groups``, ``lss_simbev_class_masks``: one label channel per group)
 So a training step at hundreds of frames/s is not bound by PIL's per-camera resampling on the CPU:
@@ -175,6 +177,140 @@ def label_index_matrix(A, grid_conf: dict) -> np.ndarray:
     return out.astype(np.float32)
 
 
+# ----------------------------------------------------------------------------- photometric augmentation (host)
+# Per image, an affine map of (R, G, B) in 0..255 units -- brightness, contrast, saturation, hue composed into one
+# 3 x 3 matrix and one offset -- plus a noise amplitude and the Philox key of the image's noise: the 16 words of
+# lss_img_photo_t (include/lss_simbev.h). ``lss_simbev_images_photo`` applies it to the resampled integer pixel in
+# registers and clamps once, at the end.
+PHOTO_NEUTRAL = (0.0, 1.0, 1.0, 0.0, 0.0, 0, 0)  # brightness, contrast, saturation, hue (deg), noise sigma, seed words
+PHOTO_WORDS = 16                                  # sizeof(lss_img_photo_t) / 4
+_LUMA = (0.299, 0.587, 0.114)
+_YIQ = ((0.299, 0.587, 0.114), (0.595716, -0.274453, -0.321263), (0.211456, -0.522591, 0.311135))
+_PHOTO_LIMS = (("photo_brightness_lim", (0.0, 0.0)), ("photo_contrast_lim", (1.0, 1.0)),
+               ("photo_saturation_lim", (1.0, 1.0)), ("photo_hue_lim", (0.0, 0.0)), ("photo_noise_lim", (0.0, 0.0)))
+_PHOTO_FIXED_KEYS = ("brightness", "contrast", "saturation", "hue", "noise", "seed")
+
+
+def photo_matrix(brightness=0.0, contrast=1.0, saturation=1.0, hue_deg=0.0):
+    """(M (3, 3), t (3,)) fp32 of the colour map v = M (r, g, b) + t in 0..255 units: composed in float64 in the fixed
+    order brightness, contrast, saturation, hue, rounded to fp32 once. An op at its neutral value (0, 1, 1, 0) is
+    skipped, not multiplied in, so the neutral record is exactly (I, 0).
+      brightness d   t += d
+      contrast a     about mid-grey: M <- a M, t <- a (t - 127.5) + 127.5
+      saturation s   S = s I + (1 - s) 1 L^T, L = (0.299, 0.587, 0.114): M <- S M, t <- S t
+      hue h degrees  H = T^-1 R(h) T, T the RGB -> YIQ matrix, R(h) the rotation of the I/Q plane: M <- H M, t <- H t
+    There is no clamp between the ops: the kernel clamps once, after the noise."""
+    vals = [float(v) for v in (brightness, contrast, saturation, hue_deg)]
+    if not all(math.isfinite(v) for v in vals):
+        raise ValueError(f"photo_matrix: finite values, got {vals!r}")
+    b, a, s, h = vals
+    M, t = np.eye(3, dtype=np.float64), np.zeros(3, dtype=np.float64)
+    if b != 0.0:
+        t = t + b
+    if a != 1.0:
+        M, t = a * M, a * (t - 127.5) + 127.5
+    if s != 1.0:
+        S = s * np.eye(3) + (1.0 - s) * np.outer(np.ones(3), np.array(_LUMA, dtype=np.float64))
+        M, t = S @ M, S @ t
+    if h != 0.0:
+        T = np.array(_YIQ, dtype=np.float64)
+        c, sn = math.cos(math.radians(h)), math.sin(math.radians(h))
+        R = np.array([[1.0, 0.0, 0.0], [0.0, c, -sn], [0.0, sn, c]], dtype=np.float64)
+        H = np.linalg.inv(T) @ R @ T
+        M, t = H @ M, H @ t
+    return M.astype(np.float32), t.astype(np.float32)
+
+
+def _photo_lims(conf: dict):
+    """(the five (lo, hi) limits in _PHOTO_LIMS' order, photo_prob, photo_per_camera) of a data_aug_conf, absent keys
+    neutral; ValueError for a pair that is not finite and ascending, a negative contrast, saturation or sigma, or a
+    probability outside [0, 1]."""
+    lims = []
+    for name, neutral in _PHOTO_LIMS:
+        lim = tuple(float(v) for v in conf.get(name, neutral))
+        if len(lim) != 2 or not all(math.isfinite(v) for v in lim) or lim[0] > lim[1]:
+            raise ValueError(f"{name} {lim!r}: a finite (lo, hi) with lo <= hi")
+        if name in ("photo_contrast_lim", "photo_saturation_lim", "photo_noise_lim") and lim[0] < 0.0:
+            raise ValueError(f"{name} {lim!r}: not negative")
+        lims.append(lim)
+    prob = float(conf.get("photo_prob", 0.5))
+    if not 0.0 <= prob <= 1.0:
+        raise ValueError(f"photo_prob {prob!r}: a probability")
+    return tuple(lims), prob, bool(int(conf.get("photo_per_camera", 1)))
+
+
+def photo_fixed_record(conf: dict):
+    """The ``photo_fixed`` dict of a data_aug_conf as (brightness, contrast, saturation, hue, noise, seed), absent
+    entries neutral (seed 0); None when the conf has none. ValueError for an unknown entry, a value that is not finite,
+    a negative contrast, saturation or noise, or a seed outside 0..2^64-1."""
+    fixed = conf.get("photo_fixed")
+    if fixed is None:
+        return None
+    unknown = sorted(set(fixed) - set(_PHOTO_FIXED_KEYS))
+    if unknown:
+        raise ValueError(f"photo_fixed: unknown entries {unknown} (one of {', '.join(_PHOTO_FIXED_KEYS)})")
+    vals = [float(fixed.get(k, d)) for k, d in zip(_PHOTO_FIXED_KEYS[:5], PHOTO_NEUTRAL[:5])]
+    if not all(math.isfinite(v) for v in vals) or vals[1] < 0.0 or vals[2] < 0.0 or vals[4] < 0.0:
+        raise ValueError(f"photo_fixed {fixed!r}: finite values; contrast, saturation and noise not negative")
+    seed = int(fixed.get("seed", 0))
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"photo_fixed: seed {seed!r} outside 0..2^64-1")
+    return (*vals, seed)
+
+
+def photo_draws(conf: dict) -> bool:
+    """Whether training samples of a data_aug_conf draw a photometric augmentation: some photo_*_lim present and not
+    neutral ((0, 0) for brightness, hue and noise, (1, 1) for contrast and saturation)."""
+    lims, _, _ = _photo_lims(conf)
+    return any(lim != neutral for lim, (_, neutral) in zip(lims, _PHOTO_LIMS))
+
+
+def photo_enabled(conf: dict) -> bool:
+    """Whether a data_aug_conf asks for the photometric augmentation: a photo_*_lim that is not neutral (photo_draws)
+    or a ``photo_fixed`` record. The training and the validation samples of such a conf carry the (N, 16) photo
+    records (SimBEVDataset.__getitem__), and this is the flag their consumers are given. A bad limit raises here."""
+    return photo_draws(conf) or photo_fixed_record(conf) is not None
+
+
+def draw_photo_augmentation(conf: dict, train: bool):
+    """One unit's photometric augmentation (brightness, contrast, saturation, hue_deg, sigma, seed0, seed1) -- a unit
+    is a camera, or a whole sample with photo_per_camera 0. Off -- validation, or a conf without a photo_*_lim -- it is
+    PHOTO_NEUTRAL and draws nothing. On, it draws from np.random, after the sample's other draws, always the same
+    number of values: for each of the four colour ops a coin U(0, 1) < photo_prob and then a value U(lim), drawn
+    even when the coin fails (the op is then neutral); sigma ~ U(photo_noise_lim); two uint32 seed words."""
+    if not train or not photo_draws(conf):
+        return PHOTO_NEUTRAL
+    lims, prob, _ = _photo_lims(conf)
+    rnd = np.random
+    ops = []
+    for lim, neutral in zip(lims[:4], PHOTO_NEUTRAL[:4]):
+        coin = rnd.uniform(0.0, 1.0) < prob
+        value = float(rnd.uniform(*lim))
+        ops.append(value if coin else neutral)
+    sigma = float(rnd.uniform(*lims[4]))
+    seed0 = int(rnd.randint(0, 1 << 32, dtype=np.uint32))
+    seed1 = int(rnd.randint(0, 1 << 32, dtype=np.uint32))
+    return (*ops, sigma, seed0, seed1)
+
+
+def photo_record(brightness=0.0, contrast=1.0, saturation=1.0, hue_deg=0.0, noise=0.0, seed0=0, seed1=0) -> np.ndarray:
+    """The 16 fp32 words of one lss_img_photo_t: photo_matrix's M (9) and t (3), sigma, the two seed words bit-cast,
+    a zero pad. (Seed words are bits, not numbers: move a record by copies only.)"""
+    M, t = photo_matrix(brightness, contrast, saturation, hue_deg)
+    rec = np.zeros(PHOTO_WORDS, dtype=np.float32)
+    rec[:9], rec[9:12], rec[12] = M.reshape(9), t, np.float32(noise)
+    rec.view(np.uint32)[13:15] = (int(seed0) & 0xFFFFFFFF, int(seed1) & 0xFFFFFFFF)
+    return rec
+
+
+def photo_fixed_records(fixed, n: int) -> np.ndarray:
+    """(n, 16) records of one fixed shift (photo_fixed_record's tuple) for the images 0..n-1 of a sample: the same
+    matrix, offset and sigma, and per image the key (seed's low word + image index mod 2^32, seed's high word)."""
+    b, a, s, h, noise, seed = fixed
+    return np.stack([photo_record(b, a, s, h, noise, (seed + i) & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
+                     for i in range(n)])
+
+
 def rotation_mode(angle: float, w: int, h: int) -> Tuple[int, Tuple[int, ...]]:
     """(rot_mode, 16.16 affine coefficients) for Image.rotate(angle) of a w x h image (NEAREST,
     expand=False): the fast paths of Image.rotate, else its inverse matrix (Python doubles, as
@@ -241,13 +377,16 @@ def _to_device_pinned(buf: bytes, dev: torch.device) -> torch.Tensor:
 
 # ----------------------------------------------------------------------------- device kernels
 def augment_images(imgs_u8: torch.Tensor, augs: Sequence[dict], final_dim: Sequence[int], out=None,
-                   keep=None) -> torch.Tensor:
+                   keep=None, photo=None) -> torch.Tensor:
     """(n, H, W, 3) uint8 device images + one aug dict per image (resize_dims, crop, flip, rotate) ->
     (n, 3, fH, fW) fp32 = normalize_img(img_transform(img)) (src/tools.py:120-128, 167-171).
 
     out: a contiguous fp32 device tensor of n * 3 * fH * fW elements to write instead of a new one.
     keep: a list that receives the device tensors allocated here (the parameter block, the table
-    concatenation, the source) -- a caller running this on a side stream holds them until its event."""
+    concatenation, the source) -- a caller running this on a side stream holds them until its event.
+    photo: None (``lss_simbev_images``), or the (n, 16) fp32 HOST tensor of the images' photometric records
+    (photo_record: the byte layout of lss_img_photo_t), uploaded pinned on the current stream and applied by
+    ``lss_simbev_images_photo``; neutral records give the same output bit for bit."""
     if not imgs_u8.is_cuda:
         raise RuntimeError("lss_carla_amd.simbev: images must be on the MI355X (no CPU fallback)")
     if imgs_u8.dtype != torch.uint8 or imgs_u8.dim() != 4 or imgs_u8.shape[-1] != 3:
@@ -295,6 +434,13 @@ def augment_images(imgs_u8: torch.Tensor, augs: Sequence[dict], final_dim: Seque
     tab_d = (tables[0] if len(tables) == 1 else torch.cat(tables)) if tables else \
         torch.zeros(1, device=dev, dtype=torch.int32)
     par_d = _to_device_pinned(bytes(params), dev)
+    photo_d = None
+    if photo is not None:
+        ph = torch.as_tensor(photo)
+        if ph.is_cuda or ph.dtype != torch.float32 or tuple(ph.shape) != (n, PHOTO_WORDS):
+            raise RuntimeError(f"photo= must be a host fp32 tensor of {(n, PHOTO_WORDS)}, got {ph.device} {ph.dtype} "
+                               f"{tuple(ph.shape)}")
+        photo_d = _to_device_pinned(ph.contiguous().numpy().tobytes(), dev)
     src = imgs_u8.contiguous()
     if out is None:
         out = torch.empty(n, 3, fH, fW, device=dev, dtype=torch.float32)
@@ -302,7 +448,12 @@ def augment_images(imgs_u8: torch.Tensor, augs: Sequence[dict], final_dim: Seque
               and out.numel() == n * 3 * fH * fW):
         raise RuntimeError(f"out= must be a contiguous fp32 device tensor of {(n, 3, fH, fW)}")
     if keep is not None:
-        keep.extend([par_d, tab_d, src])
+        keep.extend([par_d, tab_d, src] if photo_d is None else [par_d, tab_d, src, photo_d])
+    if photo_d is not None:
+        _lib.check(lib.lss_simbev_images_photo(_lib.ptr(src), n, H, W, _lib.ptr(par_d), _lib.ptr(photo_d),
+                                               _lib.ptr(tab_d), fH, fW, _lib.ptr(out), _lib.stream_handle(dev)),
+                   "lss_simbev_images_photo")
+        return out
     _lib.check(lib.lss_simbev_images(_lib.ptr(src), n, H, W, _lib.ptr(par_d), _lib.ptr(tab_d), fH, fW,
                                      _lib.ptr(out), _lib.stream_handle(dev)), "lss_simbev_images")
     return out
@@ -616,6 +767,11 @@ class SimBEVDataset(torch.utils.data.Dataset):
         # the conf asks for the BEV-space augmentation: every sample (validation's too, with the identity) then
         # carries its label index matrix directly before the BEV map
         self.bev_aug = bev_aug_enabled(data_aug_conf)
+        # the conf asks for the photometric augmentation: every sample (validation's with the neutral record, or the
+        # ``photo_fixed`` one) then carries its (N, 16) photo records before the label index matrix / the BEV map
+        self.photo = photo_enabled(data_aug_conf)
+        self.photo_fixed = photo_fixed_record(data_aug_conf) if self.photo else None
+        self.photo_per_camera = _photo_lims(data_aug_conf)[2] if self.photo else True
         print(self)
 
     def _load_all_samples(self):
@@ -655,16 +811,30 @@ class SimBEVDataset(torch.utils.data.Dataset):
         after sample_augmentation's values; the identity, and no draw, for validation or a conf without it."""
         return draw_bev_augmentation(self.data_aug_conf, self.is_train)
 
+    def sample_photo_augmentation(self, n_cams: int) -> np.ndarray:
+        """The (n_cams, 16) photo records of one sample: training draws one per camera (one per sample with
+        photo_per_camera 0) after the sample's other draws (draw_photo_augmentation); validation draws nothing and
+        carries the neutral record, or the conf's ``photo_fixed`` one (which training ignores)."""
+        if not self.is_train:
+            if self.photo_fixed is not None:
+                return photo_fixed_records(self.photo_fixed, n_cams)
+            return np.stack([photo_record()] * n_cams)
+        if self.photo_per_camera:
+            return np.stack([photo_record(*draw_photo_augmentation(self.data_aug_conf, True)) for _ in range(n_cams)])
+        return np.stack([photo_record(*draw_photo_augmentation(self.data_aug_conf, True))] * n_cams)
+
     def get_image_data(self, sample, cam_indices):
         """Decoded images and calibration (src/data_simbev.py:147-218 without the pixel work); with the BEV-space
         augmentation on, rots / trans are the composed ones (compose_rig)."""
         return self._image_data(sample, cam_indices)[0]
 
     def _image_data(self, sample, cam_indices):
-        """(get_image_data's tuple, the sample's label index matrix (2, 3) or None without the BEV augmentation)."""
+        """(get_image_data's tuple, the sample's label index matrix (2, 3) or None without the BEV augmentation,
+        the sample's (N, 16) photo records or None without the photometric augmentation)."""
         from PIL import Image
         resize, resize_dims, crop, flip, rotate = self.sample_augmentation()
         bev_aug = self.sample_bev_augmentation() if self.bev_aug else None
+        photo = torch.from_numpy(self.sample_photo_augmentation(len(cam_indices))) if self.photo else None
         imgs, rots, trans, intrins, post_rots, post_trans = [], [], [], [], [], []
         for cam_idx in cam_indices:
             img = Image.open(self.dataroot / sample["images"][cam_idx]).convert("RGB")
@@ -685,18 +855,19 @@ class SimBEVDataset(torch.utils.data.Dataset):
                 rots, trans = compose_rig(A, rots, trans)
             index_mat = torch.from_numpy(label_index_matrix(A, self.grid_conf))
         return (torch.stack(imgs), rots, trans, torch.stack(intrins), torch.stack(post_rots), torch.stack(post_trans),
-                aug, torch.tensor(float(rotate), dtype=torch.float64)), index_mat
+                aug, torch.tensor(float(rotate), dtype=torch.float64)), index_mat, photo
 
     def get_bev_raw(self, sample):
         """The BEV npz's (n_classes, X, Y) map as uint8 (value > 0 kept), src/data_simbev.py:227-232."""
         bev = np.load(sample["meta_dir"] / sample["bev"])["bev"]
         return torch.from_numpy((bev > 0).astype(np.uint8) if bev.dtype != np.uint8 else bev.copy())
 
-    def _labels(self, sample, index_mat):
-        """The sample's tail: the BEV map, last, and directly before it the label index matrix when the conf asks
-        for the BEV-space augmentation."""
+    def _labels(self, sample, index_mat, photo=None):
+        """The sample's tail: the BEV map, last; directly before it the label index matrix when the conf asks
+        for the BEV-space augmentation; before those the photo records when it asks for the photometric one."""
         bev = self.get_bev_raw(sample)
-        return (bev,) if index_mat is None else (index_mat, bev)
+        tail = (bev,) if index_mat is None else (index_mat, bev)
+        return tail if photo is None else (photo,) + tail
 
     def choose_cams(self):
         all_cams = list(range(len(CAMERA_ORDER)))
@@ -716,22 +887,23 @@ class SimBEVDataset(torch.utils.data.Dataset):
 class VizData(SimBEVDataset):
     def __getitem__(self, index):
         sample = self.samples[index]
-        raw, index_mat = self._image_data(sample, self.choose_cams())
-        return raw + (torch.empty(3, 0),) + self._labels(sample, index_mat)
+        raw, index_mat, photo = self._image_data(sample, self.choose_cams())
+        return raw + (torch.empty(3, 0),) + self._labels(sample, index_mat, photo)
 
 
 class SegmentationData(SimBEVDataset):
     def __getitem__(self, index):
         sample = self.samples[index]
-        raw, index_mat = self._image_data(sample, self.choose_cams())
-        return raw + self._labels(sample, index_mat)
+        raw, index_mat, photo = self._image_data(sample, self.choose_cams())
+        return raw + self._labels(sample, index_mat, photo)
 
 
 def worker_rnd_init(x):
     np.random.seed(13 + x)  # src/data_simbev.py:310-312
 
 
-def finish_batch(batch, final_dim, device, label_groups=None, bev_aug=False, valid_mask_conf=None, exclusive=False):
+def finish_batch(batch, final_dim, device, label_groups=None, bev_aug=False, valid_mask_conf=None, exclusive=False,
+                 photo=False):
     """A collated raw batch -> the reference's (imgs, rots, trans, intrins, post_rots, post_trans,
     [lidar,] binimgs) on `device`, the pixel work done by the HIP kernels. label_groups: K lists of BEV
     channels -> binimgs (B, K, X, Y) (class_masks); None: the reference's vehicle mask, (B, 1, X, Y).
@@ -739,7 +911,10 @@ def finish_batch(batch, final_dim, device, label_groups=None, bev_aug=False, val
     the BEV maps is the (B, 2, 3) label index matrices, which warp the labels; the rig is already composed.
     valid_mask_conf: None (the tuple is as above), or (mode, grid_conf, heights) -- the finished batch then carries,
     after the labels, the (B, X, Y) uint8 valid-cell mask of ``valid_mask`` on the batch's host rig.
-    exclusive: binimgs is the (B, X, Y) uint8 exclusive class map of the groups (class_index) instead."""
+    exclusive: binimgs is the (B, X, Y) uint8 exclusive class map of the groups (class_index) instead.
+    photo: the batch comes from a conf with the photometric augmentation (photo_enabled): the element before the label
+    index matrices (before the BEV maps without bev_aug) is the (B, N, 16) photo records, which the image kernel
+    applies (augment_images, photo=); the finished tuple does not change."""
     if exclusive and label_groups is None:
         raise ValueError("exclusive classes need label_groups")
     imgs_u8, rots, trans, intrins, post_rots, post_trans, aug, rot = batch[:8]
@@ -747,6 +922,9 @@ def finish_batch(batch, final_dim, device, label_groups=None, bev_aug=False, val
     index_mats = None
     if bev_aug:
         index_mats, rest = rest[-2], tuple(rest[:-2]) + tuple(rest[-1:])
+    records = None
+    if photo:
+        records, rest = rest[-2], tuple(rest[:-2]) + tuple(rest[-1:])
     B, N = imgs_u8.shape[:2]
     src = imgs_u8.reshape(B * N, *imgs_u8.shape[2:]).to(device, non_blocking=True)
     augs = []
@@ -754,7 +932,11 @@ def finish_batch(batch, final_dim, device, label_groups=None, bev_aug=False, val
         a = aug[b].tolist()
         rec = {"resize_dims": (a[0], a[1]), "crop": tuple(a[2:6]), "flip": bool(a[6]), "rotate": float(rot[b])}
         augs.extend([rec] * N)
-    imgs = augment_images(src, augs, final_dim).view(B, N, 3, int(final_dim[0]), int(final_dim[1]))
+    if records is None:
+        imgs = augment_images(src, augs, final_dim)
+    else:
+        imgs = augment_images(src, augs, final_dim, photo=records.reshape(B * N, PHOTO_WORDS))
+    imgs = imgs.view(B, N, 3, int(final_dim[0]), int(final_dim[1]))
     out = [imgs] + [t.to(device, non_blocking=True) for t in (rots, trans, intrins, post_rots, post_trans)]
     # the host copies ride along: the model's host torch.inverse (src/models.py:180,186) reads them
     # instead of copying the device tensors back (ops.camera_inverses), so no batch syncs the host
@@ -780,11 +962,12 @@ class DeviceLoader:
     """Iterates a DataLoader of raw samples and yields finished device batches (finish_batch)."""
 
     def __init__(self, loader, final_dim, device, label_groups=None, bev_aug=False, valid_mask_conf=None,
-                 exclusive=False):
+                 exclusive=False, photo=False):
         self.loader, self.final_dim, self.device = loader, final_dim, torch.device(device)
         self.label_groups, self.bev_aug = label_groups, bool(bev_aug)
         self.exclusive = bool(exclusive)  # the labels are the (B, X, Y) uint8 class map (class_index)
         self.valid_mask_conf = valid_mask_conf  # None, or (mode, grid_conf, heights): finish_batch appends the mask
+        self.photo = bool(photo)  # the raw batches hold the (B, N, 16) photo records (photo_enabled)
         self.dataset = loader.dataset
         self.batch_size = loader.batch_size
 
@@ -793,7 +976,10 @@ class DeviceLoader:
 
     def __iter__(self):
         for batch in self.loader:
-            if self.exclusive:
+            if self.photo:
+                yield finish_batch(batch, self.final_dim, self.device, self.label_groups, self.bev_aug,
+                                   self.valid_mask_conf, exclusive=self.exclusive, photo=True)
+            elif self.exclusive:
                 yield finish_batch(batch, self.final_dim, self.device, self.label_groups, self.bev_aug,
                                    self.valid_mask_conf, exclusive=True)
             elif self.valid_mask_conf is None:
@@ -812,8 +998,15 @@ def compile_data(version, dataroot, data_aug_conf, grid_conf, bsz, nworkers, par
     carry the flag (``bev_aug``) that says their raw batches hold the label index matrices. A data_aug_conf with
     ``valid_mask`` "grid" or "fov" (valid_mask_mode; heights ``fov_z``) makes both loaders' finished batches carry the
     valid-cell mask after the labels -- validation's too: that is the point of a masked metric. exclusive: the labels
-    of both loaders are the (B, X, Y) uint8 exclusive class map of the 1..7 label_groups (class_index)."""
+    of both loaders are the (B, X, Y) uint8 exclusive class map of the 1..7 label_groups (class_index).
+    A data_aug_conf with a photo_*_lim (photo_brightness_lim, photo_contrast_lim, photo_saturation_lim, photo_hue_lim,
+    photo_noise_lim; photo_prob, photo_per_camera) adds the photometric augmentation to the training loader's images --
+    drawn per camera on the host, applied by ``lss_simbev_images_photo`` -- and never to the validation loader, whose
+    records are neutral unless ``photo_fixed`` (a dict of brightness, contrast, saturation, hue, noise, seed) names one
+    shift for every validation image; both loaders carry the flag (``photo``) that says their raw batches hold the
+    records. Without any of these keys the loaders draw, return and launch exactly what they did before."""
     bev_aug = bev_aug_enabled(data_aug_conf)  # (a bad limit fails here)
+    photo = photo_enabled(data_aug_conf)
     mask_mode = valid_mask_mode(data_aug_conf)
     mask_conf = None if mask_mode is None else (mask_mode, grid_conf, fov_heights(data_aug_conf))
     if label_groups is not None:
@@ -830,6 +1023,9 @@ def compile_data(version, dataroot, data_aug_conf, grid_conf, bsz, nworkers, par
     valloader = torch.utils.data.DataLoader(valdata, batch_size=bsz, shuffle=False, num_workers=nworkers,
                                             pin_memory=True)
     fd = data_aug_conf["final_dim"]
+    if photo:
+        return (DeviceLoader(trainloader, fd, device, label_groups, bev_aug, mask_conf, exclusive=exclusive, photo=True),
+                DeviceLoader(valloader, fd, device, label_groups, bev_aug, mask_conf, exclusive=exclusive, photo=True))
     if exclusive:
         return (DeviceLoader(trainloader, fd, device, label_groups, bev_aug, mask_conf, exclusive=True),
                 DeviceLoader(valloader, fd, device, label_groups, bev_aug, mask_conf, exclusive=True))

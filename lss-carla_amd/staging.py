@@ -9,7 +9,8 @@ are valid. ``BatchStager`` owns those tensors and fills them from the raw batche
                ``lss_simbev_images`` and ``lss_simbev_vehicle_mask`` (``lss_simbev_class_masks`` with
                ``label_groups``; ``lss_simbev_class_masks_warp`` with ``bev_aug``: the batch's label index
                matrices, uploaded on the same stream; with ``valid_mask``, ``lss_simbev_valid_mask`` into
-               the slot's mask) straight into the next of two slots;
+               the slot's mask; with ``photo``, ``lss_simbev_images_photo`` in ``lss_simbev_images``' place, on
+               the batch's photo records uploaded on the same stream) straight into the next of two slots;
                an event marks the slot ready. Batch k+1 is staged while step k runs.
   commit()     on the current stream: wait for the oldest staged slot's event, copy slot -> static tensors
                (device to device), ``HostInverses.update`` with the slot's host post_rots / intrins, set
@@ -61,7 +62,8 @@ class BatchStager:
     RIG = ("rots", "trans", "intrins", "post_rots", "post_trans")
 
     def __init__(self, final_dim: Sequence[int], B: int, N: int, src_hw: Sequence[int], grid: dict, device,
-                 label_groups=None, bev_aug=False, valid_mask=None, fov_z=(0.0,), dbound=None, exclusive=False):
+                 label_groups=None, bev_aug=False, valid_mask=None, fov_z=(0.0,), dbound=None, exclusive=False,
+                 photo=False):
         """label_groups: K lists of BEV channels, one label channel each (simbev.class_masks): ``binimgs`` and
         both slots are (B, K, X, Y); None: the reference's vehicle mask, K = 1. bev_aug: the raw batches come from a
         conf with the BEV-space augmentation (simbev.bev_aug_enabled): the element before the BEV maps is the
@@ -76,7 +78,11 @@ class BatchStager:
         or an (N,) / (B, N) host mask) further blanks dead cameras' blocks (simbev.fov_cameras(alive=)).
         exclusive: ``binimgs`` and both slots are the (B, X, Y) uint8 exclusive class map of the 1..7 label_groups
         (0 the background, k + 1 group k, a later group wins), written by ``lss_simbev_class_index`` on the staging
-        stream in ``lss_simbev_class_masks``' place; nothing else differs."""
+        stream in ``lss_simbev_class_masks``' place; nothing else differs.
+        photo: the raw batches come from a conf with the photometric augmentation (simbev.photo_enabled): the element
+        before the label index matrices (before the BEV maps without bev_aug) is the (b, N, 16) photo records, which
+        the image kernel applies on the staging stream (simbev.augment_images, photo=); slots, events and partial
+        batches are as without it, and only ``imgs`` differs."""
         dev = torch.device(device)
         if dev.type != "cuda":
             raise RuntimeError("BatchStager: the static tensors live on the MI355X (no CPU fallback)")
@@ -93,6 +99,7 @@ class BatchStager:
             simbev.group_bits(label_groups)
         self.label_groups = None if label_groups is None else [list(g) for g in label_groups]
         self.bev_aug = bool(bev_aug)
+        self.photo = bool(photo)
         K = 1 if label_groups is None else len(self.label_groups)
         self.exclusive = bool(exclusive)
         if self.exclusive:
@@ -141,6 +148,7 @@ class BatchStager:
         imgs_u8, rots, trans, intrins, post_rots, post_trans, aug, rot = raw_batch[:8]
         bev = raw_batch[-1]
         index_mats = raw_batch[-2] if self.bev_aug else None
+        records = raw_batch[-3 if self.bev_aug else -2] if self.photo else None
         b, N = int(imgs_u8.shape[0]), int(imgs_u8.shape[1])
         slot = self._slots[self._next]
         if not 0 < b <= self.B or N != self.N or tuple(imgs_u8.shape[2:]) != tuple(slot.u8.shape[1:]):
@@ -155,6 +163,11 @@ class BatchStager:
             raise RuntimeError(f"BatchStager.stage: label index matrices {index_mats.dtype} "
                                f"{tuple(index_mats.shape)} for a batch of {b} (a raw batch without the BEV-space "
                                "augmentation?)")
+        if records is not None and (not torch.is_tensor(records) or records.dtype != torch.float32
+                                    or tuple(records.shape) != (b, N, simbev.PHOTO_WORDS)):
+            raise RuntimeError(f"BatchStager.stage: photo records {getattr(records, 'dtype', None)} "
+                               f"{tuple(getattr(records, 'shape', ()))} for a batch of {b} x {N} images (a raw batch "
+                               "without the photometric augmentation?)")
         self._next ^= 1
         self._retire(slot)
         augs = []
@@ -179,7 +192,11 @@ class BatchStager:
             slot.bev_u8[:b].copy_(bev, non_blocking=True)
             for name, t in zip(self.RIG, (rots, trans, intrins, post_rots, post_trans)):
                 getattr(slot, name)[:b].copy_(t, non_blocking=True)
-            simbev.augment_images(slot.u8[:b * N], augs, self.final_dim, out=slot.imgs[:b], keep=keep)
+            if records is None:
+                simbev.augment_images(slot.u8[:b * N], augs, self.final_dim, out=slot.imgs[:b], keep=keep)
+            else:
+                simbev.augment_images(slot.u8[:b * N], augs, self.final_dim, out=slot.imgs[:b], keep=keep,
+                                      photo=records.reshape(b * N, simbev.PHOTO_WORDS))
             if self.exclusive:
                 simbev.class_index(slot.bev_u8[:b], self.label_groups, out=slot.binimgs[:b], index_mats=index_mats,
                                    keep=keep)

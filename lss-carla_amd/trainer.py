@@ -147,6 +147,23 @@ def parse_pair(text, name="value"):
     return float(items[0]), float(items[1])
 
 
+def photo_conf(brightness=0.0, contrast=(1.0, 1.0), saturation=(1.0, 1.0), hue=0.0, noise=(0.0, 0.0), prob=0.5,
+               per_camera=True) -> dict:
+    """The loader's photo_* keys from the trainer's arguments: brightness (0..255 units) and hue (degrees) are
+    symmetric half-widths (32 -> (-32, 32)); contrast, saturation and the noise sigma are (lo, hi) ranges. ValueError
+    for a negative half-width or a limit simbev.photo_enabled refuses."""
+    from . import simbev
+    b, h = float(brightness), float(hue)
+    if not (b >= 0.0 and h >= 0.0):
+        raise ValueError(f"photo_brightness {brightness!r} / photo_hue {hue!r}: half-widths, not negative")
+    conf = {"photo_brightness_lim": (-b, b), "photo_contrast_lim": tuple(float(v) for v in contrast),
+            "photo_saturation_lim": tuple(float(v) for v in saturation), "photo_hue_lim": (-h, h),
+            "photo_noise_lim": tuple(float(v) for v in noise), "photo_prob": float(prob),
+            "photo_per_camera": int(bool(per_camera))}
+    simbev.photo_enabled(conf)
+    return conf
+
+
 def parse_thresholds(text):
     """``--iou_thresholds 0.35,0.4,0.45,0.5,0.55,0.6,0.65`` (or a sequence of numbers) -> the ladder as an ascending
     list of distinct probabilities, each strictly between 0 and 1, 15 at most (0.5 makes 16); None or empty: None."""
@@ -286,7 +303,9 @@ def build_step(grid_conf, data_aug_conf, bsz, device, *, dtype="bf16", lr=1e-3, 
     exclusive: the K label_groups are painted into one (B, X, Y) uint8 class map (simbev.class_index: 0 the
     background, k + 1 group k, a later group wins), the model has outC = K + 1, the loss is
     tools.SoftmaxLoss(K + 1, class_weight) and the EvalStep accumulates a confusion matrix; pos_weight, loss and
-    iou_thresholds are not used."""
+    iou_thresholds are not used.
+    A data_aug_conf that asks for the photometric augmentation (simbev.photo_enabled) makes both stagers expect the
+    photo records in their raw batches and run ``lss_simbev_images_photo``; the captured steps do not change."""
     import lss_carla_amd as L
     from . import parallel, simbev, tools
     from .flat_params import FlatParamGroups, lss_backward_groups
@@ -310,6 +329,8 @@ def build_step(grid_conf, data_aug_conf, bsz, device, *, dtype="bf16", lr=1e-3, 
     opt = torch.optim.Adam(masters, lr=lr, weight_decay=weight_decay, fused=True, capturable=True)
     mask_mode = simbev.valid_mask_mode(data_aug_conf)
     mask_args = {} if mask_mode is None else {"valid_mask": mask_mode, "fov_z": simbev.fov_heights(data_aug_conf)}
+    if simbev.photo_enabled(data_aug_conf):  # both stagers: validation's raw batches carry (neutral) records too
+        excl_args = {**excl_args, "photo": True}
     stager = BatchStager(data_aug_conf["final_dim"], bsz, ncams,
                          (data_aug_conf["H"], data_aug_conf["W"]), grid_conf, device, label_groups=label_groups,
                          bev_aug=simbev.bev_aug_enabled(data_aug_conf), **mask_args, **excl_args)
@@ -411,6 +432,13 @@ def train(
     fov_z=(0.0,),
     exclusive=False,
     class_weight=None,
+    photo_brightness=0.0,
+    photo_contrast=(1.0, 1.0),
+    photo_saturation=(1.0, 1.0),
+    photo_hue=0.0,
+    photo_noise=(0.0, 0.0),
+    photo_prob=0.5,
+    photo_per_camera=True,
 ):
     """Train LiftSplatShoot on a SimBEV tree; the reference's arguments (train_simbev.py:23-98) plus:
 
@@ -463,6 +491,13 @@ def train(
     focal_gamma / focal_alpha and iou_thresholds with it raise ValueError before anything is built. The ``config``
     event records ``exclusive`` and ``class_weight``. Works with the BEV-space augmentation, the valid-cell mask,
     ncams, the schedules, the EMA and resume as the sigmoid mode does.
+    photo_brightness (+-, 0..255 units), photo_contrast (lo, hi), photo_saturation (lo, hi), photo_hue (+- degrees),
+    photo_noise (sigma lo, hi; 0..255 units): the photometric augmentation of the training images -- per camera
+    (photo_per_camera False: per sample), each colour op applied with probability photo_prob at a value drawn from its
+    range, the noise always at a drawn sigma, all drawn after the sample's other draws (simbev.draw_photo_augmentation)
+    and applied by the staging stream's image kernel (``lss_simbev_images_photo``) to the resampled pixel before the
+    normalisation. Validation is never augmented, the captured step and the checkpoints do not change, and the neutral
+    defaults leave the loader exactly as it was. When on, the ``config`` event carries the seven values.
     Returns a summary dict (counter, epoch, best_val_iou, skipped, frames_per_s of the training steps)."""
     from . import checkpoint, simbev, tools
 
@@ -485,6 +520,9 @@ def train(
     bev_aug_conf = {"bev_rot_lim": tuple(float(v) for v in bev_rot_lim),
                     "bev_scale_lim": tuple(float(v) for v in bev_scale_lim), "bev_flip": bool(bev_flip)}
     bev_on = simbev.bev_aug_enabled(bev_aug_conf)
+    photo_aug_conf = photo_conf(photo_brightness, photo_contrast, photo_saturation, photo_hue, photo_noise, photo_prob,
+                                photo_per_camera)
+    photo_on = simbev.photo_draws(photo_aug_conf)
     mask_conf = {"valid_mask": valid_mask, "fov_z": parse_heights(fov_z, "fov_z")}
     mask_mode = simbev.valid_mask_mode(mask_conf)
     if gpuid < 0 or not torch.cuda.is_available():
@@ -501,6 +539,8 @@ def train(
         data_aug_conf.update(bev_aug_conf)
     if mask_mode is not None:
         data_aug_conf.update({"valid_mask": mask_mode, "fov_z": mask_conf["fov_z"]})
+    if photo_on:
+        data_aug_conf.update(photo_aug_conf)
     config = {"dataroot": str(dataroot), "nepochs": nepochs, "batch_size": bsz, "learning_rate": lr,
               "weight_decay": weight_decay, "num_workers": nworkers, "num_cameras": ncams, "image_H": H, "image_W": W,
               "final_dim": list(final_dim), "max_grad_norm": max_grad_norm, "pos_weight": pos_weight,
@@ -526,9 +566,14 @@ def train(
         config.update({"valid_mask": mask_mode, "fov_z": list(mask_conf["fov_z"])})
     if exclusive:
         config.update({"exclusive": True, "class_weight": class_weight, "pos_weight": None})
+    if photo_on:
+        config.update({"photo_brightness": float(photo_brightness), "photo_contrast": list(photo_aug_conf["photo_contrast_lim"]),
+                       "photo_saturation": list(photo_aug_conf["photo_saturation_lim"]), "photo_hue": float(photo_hue),
+                       "photo_noise": list(photo_aug_conf["photo_noise_lim"]), "photo_prob": float(photo_prob),
+                       "photo_per_camera": bool(photo_per_camera)})
     log = _Log(logdir, use_wandb, {"project": wandb_project, "name": wandb_name, "entity": wandb_entity}, config)
 
-    if ("loss" in config or bev_on or mask_mode is not None or exclusive) and not (sched_on or ema_on):
+    if ("loss" in config or bev_on or mask_mode is not None or exclusive or photo_on) and not (sched_on or ema_on):
         log.event("config", 0, **config)
 
     device = torch.device(f"cuda:{gpuid}")
@@ -807,6 +852,18 @@ def main(argv=None):
                         "softmax cross-entropy, confusion-matrix mIoU; needs --label_groups")
     p.add_argument("--class_weight", type=str, default=None,
                    help="--exclusive 1: one weight per class, the background first: w0,...,wK (default all 1)")
+    p.add_argument("--photo_brightness", type=float, default=0.0,
+                   help="photometric augmentation: brightness shift, +- this many 0..255 units (e.g. 32)")
+    p.add_argument("--photo_contrast", type=str, default="1,1",
+                   help="photometric augmentation: contrast about mid-grey, lo,hi (e.g. 0.5,1.5)")
+    p.add_argument("--photo_saturation", type=str, default="1,1",
+                   help="photometric augmentation: saturation, lo,hi (e.g. 0.5,1.5)")
+    p.add_argument("--photo_hue", type=float, default=0.0, help="photometric augmentation: hue rotation, +- degrees (e.g. 18)")
+    p.add_argument("--photo_noise", type=str, default="0,0",
+                   help="photometric augmentation: sensor noise sigma in 0..255 units, lo,hi (e.g. 0,8)")
+    p.add_argument("--photo_prob", type=float, default=0.5, help="the probability of each colour op")
+    p.add_argument("--photo_per_camera", type=int, default=1, choices=[0, 1],
+                   help="1: one draw per camera; 0: one per sample, shared by its cameras")
     a = p.parse_args(argv)
     if a.exclusive:  # the sigmoid mode's flags are errors here, before anything is built
         _exclusive_setup(parse_label_groups(a.label_groups),
@@ -834,6 +891,10 @@ def main(argv=None):
                  bev_rot_lim=parse_pair(a.bev_rot_lim, "--bev_rot_lim"),
                  bev_scale_lim=parse_pair(a.bev_scale_lim, "--bev_scale_lim"), bev_flip=bool(a.bev_flip),
                  valid_mask=a.valid_mask, fov_z=parse_heights(a.fov_z),
+                 photo_brightness=a.photo_brightness, photo_contrast=parse_pair(a.photo_contrast, "--photo_contrast"),
+                 photo_saturation=parse_pair(a.photo_saturation, "--photo_saturation"), photo_hue=a.photo_hue,
+                 photo_noise=parse_pair(a.photo_noise, "--photo_noise"), photo_prob=a.photo_prob,
+                 photo_per_camera=bool(a.photo_per_camera),
                  **({"exclusive": True, "class_weight": None if a.class_weight is None else _weights_list(a.class_weight)}
                     if a.exclusive else {}))
 

@@ -27,6 +27,11 @@ Steps:
   train_loop_bev[:steps[:runs]]       the same tree and the same two loops with the BEV-space augmentation off and on
                                       (--bev-rot-lim=-22.5,22.5 --bev-scale-lim 0.9,1.1 --bev-flip 1) alternately, RUNS (3)
                                       fresh processes each: train_loop_bev.json
+  photo[:steps[:runs[:PARENT_LIB]]]   the photometric augmentation: scripts/photo_bench.py (lss_simbev_images against
+                                      lss_simbev_images_photo at the staging shape, neutral / colour / colour + noise records,
+                                      graph replays; PARENT_LIB: the parent commit's library, its plain kernel as the base):
+                                      photo_kernel.json; then the same tree and the two loops of train_loop_bev with
+                                      --photo 0 and --photo 1 alternately, RUNS (3) fresh processes each: train_loop_photo.json
   infer[:PARENT_DIR]                  the eval-mode forward with and without the lss_bn_eval path: bench.py --config c2
                                       on a checkout of the parent commit (PARENT_DIR, library built there) and on this
                                       tree alternately, three runs each, and --hip-bn 0 here; scripts/infer_ab.py (the
@@ -288,6 +293,55 @@ def step_train_loop_bev(out, spec):
     return 0
 
 
+def step_photo(out, spec):
+    import json
+    import tempfile
+    parts = spec.split(":") if spec else []
+    steps, runs = int(parts[0]) if parts and parts[0] else 200, int(parts[1]) if len(parts) > 1 and parts[1] else 3
+    parent_lib = os.path.abspath(parts[2]) if len(parts) > 2 and parts[2] else None
+    log = os.path.join(out, "photo_kernel.log")
+    rc = run([PY, "-u", os.path.join("scripts", "photo_bench.py")] + (["--parent-lib", parent_lib] if parent_lib else []),
+             log, 300)
+    last = tail(log, 1).strip()
+    if rc != 0 or not last.startswith("{"):
+        print(tail(log, 15), flush=True)
+        return rc or 1
+    with open(os.path.join(out, "photo_kernel.json"), "w") as fh:
+        json.dump(json.loads(last), fh, indent=1)
+        fh.write("\n")
+    print(last, flush=True)
+    if steps <= 0:
+        return 0
+    script = os.path.join("scripts", "train_loop.py")
+    loops = (("loop_14_workers", ["--nworkers", "14"]), ("loop_predecoded", ["--nworkers", "0", "--cycle-batches", "4"]))
+    result = {"steps": steps, "bsz": 8, "runs": runs, **{k: {"off": [], "on": []} for k, _ in loops}}
+    with tempfile.TemporaryDirectory(prefix="lss_simbev_") as root:
+        samples = int(steps * 8 / 0.8) + 40
+        rc = run([PY, "-u", script, "--make", root, "--samples", str(samples)], os.path.join(out, "tree.log"), 900)
+        if rc != 0:
+            return rc
+        for key, extra in loops:
+            for i in range(1, runs + 1):
+                for side, aug in (("off", []), ("on", ["--photo", "1"])):
+                    log = os.path.join(out, f"train_loop_photo_{key}_{side}_{i}.log")
+                    rc = run([PY, "-u", script, "--dataroot", root, "--steps", str(steps)] + extra + aug, log, 600)
+                    last = tail(log, 1).strip()
+                    if rc != 0 or not last.startswith("{"):
+                        print(tail(log, 15), flush=True)
+                        return rc or 1
+                    got = json.loads(last)
+                    if got["skipped"]:
+                        print(f"  {key} {side} {i}: {got['skipped']} skipped steps", flush=True)
+                        return 1
+                    result[key][side].append(got["frames_per_s"])
+                    print(f"  {key} {side} {i}: {got['frames_per_s']:.1f} frames/s", flush=True)
+    with open(os.path.join(out, "train_loop_photo.json"), "w") as fh:
+        json.dump(result, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(result), flush=True)
+    return 0
+
+
 def _bench_value(cmd, log, cwd, limit=600):
     import json
     rc = run(cmd, log, limit, cwd=cwd)
@@ -424,7 +478,8 @@ def main():
     os.makedirs(out, exist_ok=True)
     os.chdir(REPO)
     fns = {"tests": step_tests, "smoke": step_smoke, "bench": step_bench, "trace": step_trace, "pmc": step_pmc,
-           "kbench": step_kbench, "py": step_py, "train_loop": step_train_loop, "train_loop_bev": step_train_loop_bev, "infer": step_infer, "bench_ab": step_bench_ab}
+           "kbench": step_kbench, "py": step_py, "train_loop": step_train_loop, "train_loop_bev": step_train_loop_bev, "infer": step_infer, "bench_ab": step_bench_ab,
+           "photo": step_photo}
     for s in a.steps:
         kind, _, spec = s.partition(":")
         print(f"== {s}", flush=True)

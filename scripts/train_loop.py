@@ -13,6 +13,9 @@ train_loop step): one JSON line {"frames_per_s", "steps", "nworkers", "cycle_bat
   python scripts/train_loop.py --dataroot DIR --valid-mask fov [--fov-z 0.0,1.5]   the valid-cell mask (none | grid | fov)
   python scripts/train_loop.py --dataroot DIR --label-groups "0;1,2;3" --exclusive 1 [--class-weight 1,1,2,4]
                                                                                     exclusive classes (softmax loss)
+  python scripts/train_loop.py --dataroot DIR --photo 1                            the photometric augmentation, every
+                                                                                    op on (+-32, 0.5-1.5, 0.5-1.5, +-18 deg,
+                                                                                    sigma 0-8, per camera)
 """
 from __future__ import annotations
 
@@ -50,6 +53,8 @@ def main():
     ap.add_argument("--ncams", type=int, default=6, help="trainer --ncams: cameras per training sample")
     ap.add_argument("--exclusive", type=int, default=0, help="trainer --exclusive (needs --label-groups)")
     ap.add_argument("--class-weight", default="", help="trainer --class_weight: one weight per class, background first")
+    ap.add_argument("--photo", type=int, default=0, help="1: trainer --photo_brightness 32 --photo_contrast 0.5,1.5 "
+                    "--photo_saturation 0.5,1.5 --photo_hue 18 --photo_noise 0,8")
     a = ap.parse_args()
     from lss_carla_amd import miopen_db
     miopen_db.use_committed()  # before torch starts
@@ -72,6 +77,8 @@ def main():
                             bev_scale_lim=trainer.parse_pair(a.bev_scale_lim, "--bev-scale-lim"),
                             bev_flip=bool(a.bev_flip), valid_mask=a.valid_mask,
                             fov_z=trainer.parse_heights(a.fov_z), ncams=a.ncams,
+                            **({"photo_brightness": 32.0, "photo_contrast": (0.5, 1.5), "photo_saturation": (0.5, 1.5),
+                                "photo_hue": 18.0, "photo_noise": (0.0, 8.0)} if a.photo else {}),
                             **({"exclusive": True, "class_weight": [float(v) for v in a.class_weight.split(",")]
                                 if a.class_weight else None} if a.exclusive else {}))
     print(json.dumps({"frames_per_s": out["frames_per_s"], "steps": out["counter"], "bsz": a.bsz,
@@ -79,7 +86,7 @@ def main():
                       "skipped": out["skipped"], "loss": out["loss"], "label_groups": a.label_groups or None,
                       "loss_kind": a.loss, "bev_rot_lim": a.bev_rot_lim, "bev_scale_lim": a.bev_scale_lim,
                       "bev_flip": a.bev_flip, "valid_mask": a.valid_mask, "fov_z": a.fov_z, "ncams": a.ncams,
-                      "exclusive": a.exclusive}))
+                      "exclusive": a.exclusive, "photo": a.photo}))
 
 
 if __name__ == "__main__":

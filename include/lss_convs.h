@@ -575,6 +575,44 @@ int lss_se_wgrad(const float* de, const float* h, const float* dr, const float* 
 #define LSS_SE_TAIL_MAX_IMAGES 4096
 int lss_se_tails(int on);
 
+/* What lss_se_fwd / lss_se_bwd launch for a shape under the current lss_se_tails setting (ABI 37; host only: no HIP
+ * call, no allocation -- both entry points read the same rule, so it reports what this build launches). pass: the
+ * entry point; N, C, HW, sq as that entry point's. Returns 0, or LSS_CONV_EINVAL where the entry point would for these
+ * sizes (and for an unknown pass or arm == NULL). The report:
+ *   tails       1: the reduction with the per-image MLP tail, then scale / dx (launches = 2); 0: the sequence of four
+ *   grid        blocks of each launch in order (zero past `launches`)
+ *   bpi, cpb    tails: blocks per image and channels per block (cpb % 16 == 0; bpi = 1 once N > 512); sequence: 0
+ *   planes_max, planes_min   the most and the fewest planes one wave of one block takes. Tails: a block of nch
+ *               channels gives wave w ceil((nch - w) / 16) of them, the mean loading them four at a time and the dot
+ *               two at a time; sequence: 1, or 0 for the idle waves of a last block (N * C % 4 != 0)
+ *   w2_chunks   forward: pieces W2 goes through LDS in -- tails ceil(C / min(1024, 16384 / (sq + 1))), sequence
+ *               ceil(C / 256); backward: 0
+ *   chunks64    backward: ceil(C / 64), the 64-channel chunks (four 16-channel units each); forward: 0
+ * and the classes these form -- every combination below that the sizes admit is a distinct path through the kernels:
+ *   planes_class  min(planes_max, 5): 1 one plane a wave (the unbatched body); 2, 3, 4 one batch of the mean with that
+ *               many live planes (the dot: 2; 2 + 1; 2 + 2); LSS_SE_PLANES_MANY = 5 several batches. Sequence: 1.
+ *   ragged      planes_min < planes_max: a block whose waves do not all take the same number of planes
+ *   chunk_class forward  LSS_SE_FWD_ONE_CHUNK   W2 staged once
+ *                        LSS_SE_FWD_CHUNKS      several chunks, C <= 1024
+ *                        LSS_SE_FWD_TWO_PASSES  tails only: C > 1024, so also a second pass of the block over the means
+ *               backward LSS_SE_BWD_ONE_CHUNK   C <= 64
+ *                        LSS_SE_BWD_UNIT_A_WAVE 2 to 4 chunks: each wave of the tail takes at most one unit
+ *                        LSS_SE_BWD_UNITS_A_WAVE 5 to 16 chunks: a wave of the tail takes several units
+ *                        LSS_SE_BWD_TWO_PASSES  C > 1024: also a second pass of the tail's block over t / de / dm
+ *               (the sequence runs one block per chunk and sums as many partials, so the classes bound it as well)
+ * The finite set: tails in {0, 1}; with the tails planes_class x ragged in {1..5} x {0, 1} and bpi = 1 or more, the
+ * forward's three and the backward's four chunk classes; in the sequence ragged in {0, 1}, the forward's first two
+ * and the backward's four chunk classes. */
+enum { LSS_SE_FWD = 0, LSS_SE_BWD = 1 };
+enum { LSS_SE_PLANES_MANY = 5 };
+enum { LSS_SE_FWD_ONE_CHUNK = 0, LSS_SE_FWD_CHUNKS = 1, LSS_SE_FWD_TWO_PASSES = 2 };
+enum { LSS_SE_BWD_ONE_CHUNK = 0, LSS_SE_BWD_UNIT_A_WAVE = 1, LSS_SE_BWD_UNITS_A_WAVE = 2, LSS_SE_BWD_TWO_PASSES = 3 };
+typedef struct lss_se_arm {
+    int32_t tails, launches, grid[4], bpi, cpb, planes_max, planes_min, w2_chunks, chunks64;
+    int32_t planes_class, ragged, chunk_class;
+} lss_se_arm_t;
+int lss_se_arm(int32_t pass, int32_t N, int32_t C, int32_t HW, int32_t sq, lss_se_arm_t* arm);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,7 @@ DEBUG_LIB_PATH = os.path.join(_HERE, "liblss_hip_debug.so")  # LSS_DEBUG=1: devi
 
 F32, BF16 = 0, 1
 NCHW, NHWC = 0, 1
-ABI_VERSION = 36
+ABI_VERSION = 37
 
 
 class Dims(ctypes.Structure):
@@ -43,6 +43,13 @@ class ImgPhoto(ctypes.Structure):
 class BnArm(ctypes.Structure):
     """lss_bn_arm_t of include/lss_convs.h: the kernels lss_bn_arm reports for a batch-norm entry point."""
     _fields_ = [(n, ctypes.c_int32) for n in ("family", "v", "it", "relu", "launches", "chunks", "blocks")]
+
+
+class SeArm(ctypes.Structure):
+    """lss_se_arm_t of include/lss_convs.h: what lss_se_arm reports for a squeeze-excite entry point."""
+    _fields_ = [("tails", ctypes.c_int32), ("launches", ctypes.c_int32), ("grid", ctypes.c_int32 * 4)] + \
+        [(n, ctypes.c_int32) for n in ("bpi", "cpb", "planes_max", "planes_min", "w2_chunks", "chunks64",
+                                       "planes_class", "ragged", "chunk_class")]
 
 
 class DwArm(ctypes.Structure):
@@ -189,6 +196,7 @@ SIGNATURES = {
     "lss_se_bwd": (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "lss_se_wgrad": (ctypes.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p]),
     "lss_se_tails": (ctypes.c_int, [ctypes.c_int]),
+    "lss_se_arm": (ctypes.c_int, [_i32] * 5 + [ctypes.POINTER(SeArm)]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -701,31 +701,73 @@ inline void se_tail_grid(int N, int C, int* bpi, int* cpb) {
 }
 inline int se_next_bank() { return (int)(g_se_bank.fetch_add(1u, std::memory_order_relaxed) % kSeBanks); }
 
+// Everything a launch of lss_se_fwd / lss_se_bwd depends on, decided once: both launchers read it and lss_se_arm
+// reports it (include/lss_convs.h), so the query cannot differ from what this build launches.
+inline int se_arm(int pass, int N, int C, int HW, int sq, lss_se_arm_t* a) {
+    if (!a || (pass != LSS_SE_FWD && pass != LSS_SE_BWD) || !se_ok(N, C, HW, sq)) return LSS_CONV_EINVAL;
+    const bool bwd = pass == LSS_SE_BWD;
+    const int planes = N * C, n4 = planes * HW / 4;
+    *a = lss_se_arm_t{};
+    a->tails = se_tails(N, C, sq, HW, bwd) ? 1 : 0;
+    if (a->tails) {
+        se_tail_grid(N, C, &a->bpi, &a->cpb);
+        a->launches = 2;
+        a->grid[0] = N * a->bpi;
+        a->grid[1] = grid_blocks(n4, kBlock);
+        // a block of nch channels: wave w takes the planes w, w + 16, ...
+        a->planes_max = grid_blocks(std::min(a->cpb, C), kTailWaves);
+        a->planes_min = (C - (a->bpi - 1) * a->cpb) / kTailWaves;
+        a->w2_chunks = bwd ? 0 : grid_blocks(C, std::min(kTail, kTailW / (sq + 1)));
+    } else {
+        a->launches = 4;
+        a->grid[0] = grid_blocks(planes, kBlock / kWave);
+        a->grid[1] = bwd ? N * grid_blocks(C, kMlpbC) : N * grid_blocks(sq, 4);
+        a->grid[2] = N * grid_blocks(C, bwd ? kMlpbC : kMlpC);
+        a->grid[3] = grid_blocks(n4, kBlock);
+        a->planes_max = 1;
+        a->planes_min = planes % (kBlock / kWave) ? 0 : 1;  // the last block's idle waves
+        a->w2_chunks = bwd ? 0 : grid_blocks(C, kMlpC);
+    }
+    a->chunks64 = bwd ? grid_blocks(C, kMlpbC) : 0;
+    a->planes_class = std::min(a->planes_max, (int)LSS_SE_PLANES_MANY);
+    a->ragged = a->planes_min < a->planes_max;
+    if (bwd)
+        a->chunk_class = C <= kMlpbC ? LSS_SE_BWD_ONE_CHUNK
+                         : 4 * a->chunks64 <= kTailWaves ? LSS_SE_BWD_UNIT_A_WAVE
+                         : C <= kTail ? LSS_SE_BWD_UNITS_A_WAVE : LSS_SE_BWD_TWO_PASSES;
+    else
+        a->chunk_class = a->w2_chunks == 1 ? LSS_SE_FWD_ONE_CHUNK
+                         : a->tails && C > kTail ? LSS_SE_FWD_TWO_PASSES : LSS_SE_FWD_CHUNKS;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
 
 int lss_se_tails(int on) { return g_se_tails.exchange(on <= 0 ? 0 : on >= 2 ? 2 : 1, std::memory_order_relaxed); }
 
+int lss_se_arm(int32_t pass, int32_t N, int32_t C, int32_t HW, int32_t sq, lss_se_arm_t* arm) {
+    return se_arm(pass, N, C, HW, sq, arm);
+}
+
 int lss_se_fwd(const void* x, int32_t N, int32_t C, int32_t HW, const float* w1, const float* b1, const float* w2,
                const float* b2, int32_t sq, float* m, float* r, float* h, float* sig, void* y, void* stream) {
     if (!x || !w1 || !b1 || !w2 || !b2 || !m || !r || !h || !sig || !y || !se_ok(N, C, HW, sq)) return LSS_CONV_EINVAL;
     if (!se_aligned(x, y)) return LSS_CONV_EINVAL;
     hipStream_t s = (hipStream_t)stream;
+    lss_se_arm_t a;
+    if (se_arm(LSS_SE_FWD, N, C, HW, sq, &a) != 0) return LSS_CONV_EINVAL;
     const int planes = N * C, n4 = planes * HW / 4;
-    if (se_tails(N, C, sq, HW, false)) {
-        int bpi, cpb;
-        se_tail_grid(N, C, &bpi, &cpb);
-        hipLaunchKernelGGL(k_se_mean_tail, dim3(N * bpi), dim3(kTail), 0, s, (const unsigned short*)x, C, HW, bpi, cpb,
-                           se_next_bank(), w1, b1, w2, b2, sq, m, r, h, sig);
+    if (a.tails) {
+        hipLaunchKernelGGL(k_se_mean_tail, dim3(a.grid[0]), dim3(kTail), 0, s, (const unsigned short*)x, C, HW, a.bpi,
+                           a.cpb, se_next_bank(), w1, b1, w2, b2, sq, m, r, h, sig);
     } else {
-        hipLaunchKernelGGL(k_se_mean, dim3(grid_blocks(planes, kBlock / kWave)), dim3(kBlock), 0, s,
-                           (const unsigned short*)x, planes, HW, m);
-        const int nchunk = (C + kMlpC - 1) / kMlpC;
-        hipLaunchKernelGGL(k_se_mlp1, dim3(N * ((sq + 3) / 4)), dim3(kBlock), 0, s, m, w1, b1, C, sq, r, h);
-        hipLaunchKernelGGL(k_se_mlp2, dim3(N * nchunk), dim3(kBlock), 0, s, h, w2, b2, C, sq, sig);
+        hipLaunchKernelGGL(k_se_mean, dim3(a.grid[0]), dim3(kBlock), 0, s, (const unsigned short*)x, planes, HW, m);
+        hipLaunchKernelGGL(k_se_mlp1, dim3(a.grid[1]), dim3(kBlock), 0, s, m, w1, b1, C, sq, r, h);
+        hipLaunchKernelGGL(k_se_mlp2, dim3(a.grid[2]), dim3(kBlock), 0, s, h, w2, b2, C, sq, sig);
     }
-    hipLaunchKernelGGL(k_se_scale, dim3(grid_blocks(n4, kBlock)), dim3(kBlock), 0, s, (const unsigned short*)x, sig, HW, n4,
+    hipLaunchKernelGGL(k_se_scale, dim3(a.grid[a.launches - 1]), dim3(kBlock), 0, s, (const unsigned short*)x, sig, HW, n4,
                        (unsigned short*)y);
     return launch_status();
 }
@@ -737,21 +779,20 @@ int lss_se_bwd(const void* dy, const void* x, int32_t N, int32_t C, int32_t HW, 
         return LSS_CONV_EINVAL;
     if (!se_aligned(dy, x, dx)) return LSS_CONV_EINVAL;
     hipStream_t s = (hipStream_t)stream;
+    lss_se_arm_t a;
+    if (se_arm(LSS_SE_BWD, N, C, HW, sq, &a) != 0) return LSS_CONV_EINVAL;
     const int planes = N * C, n4 = planes * HW / 4;
-    if (se_tails(N, C, sq, HW, true)) {  // the chunk partials stay in LDS: dh_part is not touched
-        int bpi, cpb;
-        se_tail_grid(N, C, &bpi, &cpb);
-        hipLaunchKernelGGL(k_se_dot_tail, dim3(N * bpi), dim3(kTail), 0, s, (const unsigned short*)dy,
-                           (const unsigned short*)x, C, HW, bpi, cpb, se_next_bank(), sig, r, w1, w2, sq, t, de, dr,
+    if (a.tails) {  // the chunk partials stay in LDS: dh_part is not touched
+        hipLaunchKernelGGL(k_se_dot_tail, dim3(a.grid[0]), dim3(kTail), 0, s, (const unsigned short*)dy,
+                           (const unsigned short*)x, C, HW, a.bpi, a.cpb, se_next_bank(), sig, r, w1, w2, sq, t, de, dr,
                            dm);
     } else {
-        hipLaunchKernelGGL(k_se_dot, dim3(grid_blocks(planes, kBlock / kWave)), dim3(kBlock), 0, s,
-                           (const unsigned short*)dy, (const unsigned short*)x, planes, HW, t);
-        const int nchunk = (C + kMlpbC - 1) / kMlpbC;
-        hipLaunchKernelGGL(k_se_mlpb1, dim3(N * nchunk), dim3(kBlock), 0, s, t, sig, w2, C, sq, de, dh_part);
-        hipLaunchKernelGGL(k_se_mlpb2, dim3(N * nchunk), dim3(kBlock), 0, s, dh_part, r, w1, C, sq, dr, dm);
+        hipLaunchKernelGGL(k_se_dot, dim3(a.grid[0]), dim3(kBlock), 0, s, (const unsigned short*)dy,
+                           (const unsigned short*)x, planes, HW, t);
+        hipLaunchKernelGGL(k_se_mlpb1, dim3(a.grid[1]), dim3(kBlock), 0, s, t, sig, w2, C, sq, de, dh_part);
+        hipLaunchKernelGGL(k_se_mlpb2, dim3(a.grid[2]), dim3(kBlock), 0, s, dh_part, r, w1, C, sq, dr, dm);
     }
-    hipLaunchKernelGGL(k_se_dx, dim3(grid_blocks(n4, kBlock)), dim3(kBlock), 0, s, (const unsigned short*)dy, sig, dm, HW,
+    hipLaunchKernelGGL(k_se_dx, dim3(a.grid[a.launches - 1]), dim3(kBlock), 0, s, (const unsigned short*)dy, sig, dm, HW,
                        n4, (unsigned short*)dx);
     return launch_status();
 }

@@ -666,3 +666,369 @@ def bn_bwd_bars(ref, ins, combo, k=BN_K):
     extra_g = (np.abs(ins["dy"] * xhat) * near).sum(axis=1)
     return dict(dbeta=e * (ref["abs_dbeta"] + np.abs(ref["dbeta"])) + extra_b,
                 dgamma=e * (ref["abs_dgamma"] + np.abs(ref["dgamma"])) + extra_g)
+
+
+# ----------------------------------------------------------------------------- squeeze-excite
+# lss_se_arm's passes, settings and classes (include/lss_convs.h)
+SE_FWD, SE_BWD = 0, 1
+SE_OFF, SE_DEFAULT, SE_FORCED = 0, 1, 2  # lss_se_tails
+SE_FWD_CHUNKS = ("one_chunk", "chunks", "two_passes")
+SE_BWD_CHUNKS = ("one_chunk", "unit_a_wave", "units_a_wave", "two_passes")
+SE_BANK_IMAGES = 4096  # LSS_SE_TAIL_MAX_IMAGES
+SE_SEED = 180000  # (committed with the draws: test_host.py's left-out-term proofs hold for this one)
+
+# N, C, HW, sq; setting: SE_DEFAULT marks a routing case (it runs under all three settings, the others under 0 and 2)
+SeCase = namedtuple("SeCase", "N C HW sq setting note")
+_R, _T = SE_DEFAULT, SE_FORCED
+SE_CASES = [
+    # ---- routing under the default setting: C * sq against 1024 (forward) and 4096 (backward); N against the bank
+    SeCase(2, 256, 4, 4, _R, "C sq 1024: forward tail; one plane a wave, full blocks; C 256"),
+    SeCase(2, 41, 4, 25, _R, "C sq 1025: forward sequence"),
+    SeCase(2, 64, 8, 64, _R, "C sq 4096: backward tail; C 64, sq 64"),
+    SeCase(2, 241, 4, 17, _R, "C sq 4097: backward sequence; sq 17"),
+    SeCase(4096, 4, 4, 1, _R, "N 4096: the last image of the bank"),
+    SeCase(4097, 4, 4, 1, _R, "N 4097: past the bank, the sequence under every setting"),
+    # ---- tail grid: planes a wave 1 .. 5, each with full and with ragged blocks
+    SeCase(3, 6, 4, 1, _T, "one plane, ragged: a block must not straddle images"),
+    SeCase(64, 256, 4, 2, _T, "two planes a wave, full"),
+    SeCase(48, 240, 8, 10, _T, "two planes a wave, a last block of one"),
+    SeCase(64, 384, 4, 2, _T, "three planes a wave, full"),
+    SeCase(64, 376, 4, 2, _T, "three planes a wave, ragged"),
+    SeCase(64, 512, 4, 2, _T, "four planes a wave, full"),
+    SeCase(64, 500, 4, 2, _T, "four planes a wave, ragged"),
+    SeCase(128, 320, 4, 5, _T, "five planes a wave, full: mean 4 + 1, dot 2 + 2 + 1"),
+    SeCase(128, 310, 4, 5, _T, "five planes a wave, ragged"),
+    SeCase(600, 40, 4, 2, _T, "N 600: one block an image"),
+    SeCase(256, 20, 4, 1, _T, "N 256: the last count with two slots an image"),
+    SeCase(257, 20, 4, 1, _T, "N 257: one block an image from here on"),
+    SeCase(64, 1152, 4, 48, _T, "144 channels a block: mean 4 + 4 + 1, dot 2 + 2 + 2 + 2 + 1"),
+    SeCase(40, 600, 12, 25, _T, "64 channels a block, 24 in the last; HW 12"),
+    # ---- reduce conv: C around the wave (64), the four-way unrolled loop (193) and the expand chunk (256); sq with
+    # rows past the last in the tail's four-row batches
+    SeCase(2, 63, 4, 1, _T, "C 63, sq 1"),
+    SeCase(2, 64, 4, 3, _T, "C 64, sq 3"),
+    SeCase(2, 65, 4, 5, _T, "C 65, sq 5"),
+    SeCase(2, 192, 4, 16, _T, "C 192, sq 16"),
+    SeCase(2, 193, 4, 17, _T, "C 193, sq 17"),
+    SeCase(2, 257, 4, 63, _T, "C 257, sq 63"),
+    SeCase(2, 72, 12, 3, _T, "C 72: a second 64-channel chunk of 8 channels"),
+    SeCase(2, 320, 8, 5, _T, "C 320: two expand chunks of the sequence, five backward chunks"),
+    # ---- expand conv in the tail: the chunk is min(1024, 16384 / (sq + 1)) channels
+    SeCase(1, 1025, 4, 15, _T, "sq 15, C 1025: two chunks, the second of one channel"),
+    SeCase(1, 963, 4, 16, _T, "sq 16, C 963: one chunk of 963"),
+    SeCase(1, 964, 4, 16, _T, "sq 16, C 964: a second chunk of one channel"),
+    SeCase(1, 1024, 4, 15, _T, "sq 15, C 1024: one chunk, one pass"),
+    SeCase(1, 2048, 4, 64, _T, "the ABI's limits: nine chunks, 128 units"),
+    SeCase(5, 1152, 44, 48, _T, "the widest trunk block at its real plane"),
+    # ---- planes: a lane's second trip (HW > 256) and a trip that stops mid-wave
+    SeCase(2, 5, 252, 2, _T, "HW 252: the last lane idle"),
+    SeCase(3, 4, 256, 1, _T, "HW 256: one full trip"),
+    SeCase(2, 7, 260, 3, _T, "HW 260: lane 0 makes a second trip"),
+    SeCase(2, 3, 516, 2, _T, "HW 516: a third trip"),
+    SeCase(48, 8, 4, 2, _T, "the workload's image count"),
+    SeCase(1, 4, 4, 1, _T, "one block is the whole image"),
+]
+# (note below, note above, pass, setting): the two sides of each bound; they fall in different classes
+SE_BOUNDARIES = [
+    ("C sq 1024: forward tail; one plane a wave, full blocks; C 256", "C sq 1025: forward sequence", SE_FWD, SE_DEFAULT),
+    ("C sq 4096: backward tail; C 64, sq 64", "C sq 4097: backward sequence; sq 17", SE_BWD, SE_DEFAULT),
+    ("N 4096: the last image of the bank", "N 4097: past the bank, the sequence under every setting", SE_FWD, SE_FORCED),
+    ("N 4096: the last image of the bank", "N 4097: past the bank, the sequence under every setting", SE_BWD, SE_DEFAULT),
+    ("N 256: the last count with two slots an image", "N 257: one block an image from here on", SE_FWD, SE_FORCED),
+    ("sq 16, C 963: one chunk of 963", "sq 16, C 964: a second chunk of one channel", SE_FWD, SE_FORCED),
+    ("sq 15, C 1024: one chunk, one pass", "sq 15, C 1025: two chunks, the second of one channel", SE_FWD, SE_FORCED),
+    ("sq 15, C 1024: one chunk, one pass", "sq 15, C 1025: two chunks, the second of one channel", SE_BWD, SE_FORCED),
+    ("C sq 1024: forward tail; one plane a wave, full blocks; C 256", "C 257, sq 63", SE_FWD, SE_OFF),
+    ("C sq 1024: forward tail; one plane a wave, full blocks; C 256", "C 257, sq 63", SE_BWD, SE_FORCED),
+    ("C 64, sq 3", "C 65, sq 5", SE_BWD, SE_OFF),
+    ("C 64, sq 3", "C 65, sq 5", SE_BWD, SE_FORCED),
+    ("two planes a wave, full", "three planes a wave, full", SE_FWD, SE_FORCED),
+    ("three planes a wave, full", "four planes a wave, full", SE_BWD, SE_FORCED),
+    ("four planes a wave, full", "five planes a wave, full: mean 4 + 1, dot 2 + 2 + 1", SE_FWD, SE_FORCED),
+    ("three planes a wave, full", "three planes a wave, ragged", SE_FWD, SE_FORCED),
+]
+# lss_se_wgrad, (N, C, sq): N on either side of the unroll of 16 images; 2 C sq + sq + C no multiple of 256, and with
+# C sq = 15 one wave holds all four branches (dw2, dw1, db1, db2)
+SE_WGRAD_CASES = [(1, 5, 3), (15, 5, 3), (16, 5, 3), (17, 100, 7), (33, 5, 3), (33, 100, 7)]
+SE_AUTOGRAD = ("C 72: a second 64-channel chunk of 8 channels", "two planes a wave, a last block of one",
+               "HW 260: lane 0 makes a second trip")
+
+
+def se_id(c) -> str:
+    return "%dx%dx%d-sq%d" % (c.N, c.C, c.HW, c.sq)
+
+
+def se_case(note: str):
+    return next(c for c in SE_CASES if c.note == note)
+
+
+def se_settings(c):
+    return (SE_OFF, SE_DEFAULT, SE_FORCED) if c.setting == SE_DEFAULT else (SE_OFF, SE_FORCED)
+
+
+def se_class(pas: int, a) -> tuple:
+    """lss_se_arm_t as a class: (path, planes a wave, ragged, one block an image, chunk class)."""
+    chunk = (SE_BWD_CHUNKS if pas == SE_BWD else SE_FWD_CHUNKS)[a.chunk_class]
+    return ("tails" if a.tails else "sequence", a.planes_class, bool(a.ragged), a.tails == 1 and a.bpi == 1, chunk)
+
+
+def se_classes(pas: int, tails: bool) -> dict:
+    """What include/lss_convs.h enumerates for a pass and path, axis by axis."""
+    chunks = set(SE_BWD_CHUNKS) if pas == SE_BWD else set(SE_FWD_CHUNKS[:3 if tails else 2])
+    if tails:
+        return dict(planes={(p, r) for p in (1, 2, 3, 4, 5) for r in (False, True)}, one_block={False, True}, chunks=chunks)
+    return dict(planes={(1, False), (1, True)}, one_block={False}, chunks=chunks)
+
+
+def rbf(v):
+    """v rounded to the nearest bf16 value, ties to even, as float64 (from float64 directly: no double rounding)."""
+    v = np.asarray(v, dtype=np.float64)
+    e = np.frexp(v)[1] - 1  # |v| in [2^e, 2^(e + 1))
+    return np.where(v == 0, 0.0, np.ldexp(np.rint(np.ldexp(v, 7 - e)), e - 7))
+
+
+def bf16_half(got, exact):
+    """Half the distance from the bf16 value got to its bf16 neighbour on exact's side."""
+    got, exact = np.asarray(got, dtype=np.float64), np.asarray(exact, dtype=np.float64)
+    f, e = np.frexp(got)
+    half = np.ldexp(1.0, e - 1 - 8)
+    inward = (np.abs(exact) < np.abs(got)) | (np.sign(exact) != np.sign(got))
+    return np.where(got == 0, 0.0, np.where(inward & (np.abs(f) == 0.5), half / 2, half))
+
+
+def se_inputs(N: int, C: int, HW: int, sq: int):
+    """x, dy (N, C, HW): bf16 values with |v| in [0.5, 2] and a random sign (no term of a plane's sum is negligible);
+    w1 (sq, C), b1, w2 (C, sq), b2: fp32 masters scaled as test_gpu_se_tails._inputs scales them. All float64 arrays."""
+    rng = np.random.default_rng(SE_SEED + 7919 * N + 131 * C + 17 * HW + sq)
+
+    def away(shape):
+        v = (0.5 + 1.5 * rng.random(shape)) * np.where(rng.random(shape) < 0.5, -1.0, 1.0)
+        return rounded(v, BF16).double().numpy()
+    f32 = lambda a: a.astype(np.float32).astype(np.float64)  # noqa: E731
+    return dict(x=away((N, C, HW)), dy=away((N, C, HW)),
+                w1=f32(rng.standard_normal((sq, C)) / C ** 0.5), b1=f32(rng.standard_normal(sq)),
+                w2=f32(rng.standard_normal((C, sq)) / sq ** 0.5), b2=f32(rng.standard_normal(C)))
+
+
+# Bars. Every stage is recomputed in fp64 from the buffers that feed it, so a bar has to cover one stage's fp32
+# arithmetic only. With u = 2^-24 (half an fp32 ulp, the relative error of one rounding) a stage whose every term
+# passes through at most d roundings errs by at most d u sum |terms| (first order; d u < 2^-17 throughout). d is read
+# from the summation order written in lss_se.hip, and the bar is SE_ROOM d u sum |terms|: the 4x room the batch-norm
+# bars are held to, so that a re-associated kernel of the same depth, and test_host.py's fp32 evaluation, still pass.
+# Products of two bf16 values are exact in fp32, and an fma rounds once.
+#   m     se_plane_mean: per lane and trip (v0 + v1) + (v2 + v3) then s +=: 3 a trip, ceil(HW / 256) trips; the
+#         six-step wave tree; the division by HW
+#   r     se_fc1_dots: a lane has at most ceil(C / 64) channels, its four partial sums take a quarter of them (rounded
+#         down) in the unrolled loop, partial 0 up to 3 more in the remainder loop; (a0 + a1) + (a2 + a3): 2; the wave tree: 6; + b1: 1
+#   sigmoid(z) = 1 / (1 + __expf(-z)), __expf(x) = exp2(x log2(e)): the product's rounding and the constant's move the
+#         result by |x| u each, the hardware exp2 is good to 1 ulp = 2 u; so exp errs by (2 |z| + 2) u, which 1 + . damps
+#         and rounds (1), and the correctly rounded division rounds (1): relative error (2 |z| + 4) u
+#   h     r sigmoid(r): the sigmoid's and one product
+#   e     se_fc2: sq fmas in sequence (the first onto zero), + b2: sq of them
+#   t     se_plane_dot: 4 fmas a trip in one chain, ceil(HW / 256) trips; the wave tree: 6
+#   de    t s (1 - s): 1 - s, two products: 3
+#   dh_part  se_dh16: a product each (1), 16 added in sequence (15); sum4 of the four waves: 2
+#   dr    dh: the above and the chunks' partials added in sequence, ceil(C / 64) more; then dh s (1 + r (1 - s)) with
+#         s = sigmoid(r): written out at se_bwd_stages
+#   dm    se_dm_range: at most 16 fmas in sequence; sum4: 2
+#   dx    fma(g, sig, dm / HW): the division's rounding of dm / HW and the fma's of the sum
+#   dw1, db1, dw2, db2   k_se_wgrad: N fmas (or adds) in image order
+SE_ROOM = 4
+U24 = 2.0 ** -24
+SE_D_DE, SE_D_DHP, SE_D_DM = 3, 18, 18
+
+
+def se_d_m(HW): return 3 * -(-HW // 256) + 6 + 1
+def se_d_r(C): return -(-C // 64) // 4 + 3 + 2 + 6 + 1
+def se_d_sigmoid(z): return 2 * np.abs(z) + 4
+def se_d_e(sq): return sq
+def se_d_t(HW): return 4 * -(-HW // 256) + 6
+def se_d_dh(C): return SE_D_DHP + -(-C // 64)
+
+
+def _sigmoid(z):
+    return 1 / (1 + np.exp(-z))
+
+
+def _dot(a, b, order: str):
+    """sum_k a[..., k] b[..., k] over the last axis: numpy's pairwise sum of the products, or one after the other."""
+    p = np.ascontiguousarray(a * b)
+    return p.sum(axis=-1) if order == "pairwise" else np.cumsum(p, axis=-1)[..., -1]
+
+
+def se_weights(ins):
+    """The weights and biases as the kernels use them: rounded to bf16."""
+    return rbf(ins["w1"]), rbf(ins["b1"]), rbf(ins["w2"]), rbf(ins["b2"])
+
+
+def se_reference(ins, ft=np.float64, order="pairwise", fed=None):
+    """include/lss_convs.h's squeeze-excite contract restated in numpy, every buffer of the C ABI, with bf16 rounding
+    (nearest even) where the header says autocast rounds; pre_*: the value before that rounding. ft = float64: the
+    reference. ft = float32 in either order: the evaluation test_host.py measures the bars' room with (it chains its
+    own rounded buffers, as the kernels do). fed: the reference whose r, sig the backward and whose de, h, dr, m the
+    weight gradients take (what the GPU tests hand lss_se_bwd and lss_se_wgrad); default: this evaluation's own."""
+    c = lambda a: np.asarray(a).astype(ft)  # noqa: E731
+    x, dy = c(ins["x"]), c(ins["dy"])
+    w1, b1, w2, b2 = (c(w) for w in se_weights(ins))
+    N, C, HW = x.shape
+    o = {}
+    o["pre_m"] = _dot(x, np.ones_like(x), order) / ft(HW)
+    o["m"] = c(rbf(o["pre_m"]))
+    o["pre_r"] = _dot(o["m"][:, None, :], w1[None], order) + b1
+    o["r"] = c(rbf(o["pre_r"]))
+    o["pre_h"] = o["r"] * _sigmoid(o["r"])
+    o["h"] = c(rbf(o["pre_h"]))
+    o["pre_e"] = _dot(o["h"][:, None, :], w2[None], order) + b2
+    o["e"] = c(rbf(o["pre_e"]))
+    o["pre_sig"] = _sigmoid(o["e"])
+    o["sig"] = c(rbf(o["pre_sig"]))
+    o["y"] = rbf(o["sig"][..., None].astype(np.float64) * ins["x"])
+    src = o if fed is None else fed
+    r, sig = c(src["r"]), c(src["sig"])
+    o["t"] = _dot(dy, x, order)
+    o["de"] = o["t"] * sig * (1 - sig)
+    nchunk = -(-C // 64)
+    pad = np.zeros((N, nchunk * 64 - C), dtype=ft)
+    dec = np.concatenate([o["de"], pad], axis=1).reshape(N, nchunk, 64)
+    w2c = np.concatenate([w2, np.zeros((nchunk * 64 - C, w2.shape[1]), dtype=ft)]).reshape(nchunk, 64, -1)
+    o["dh_part"] = _dot(dec[:, :, None, :], w2c.transpose(0, 2, 1)[None], order)  # (N, nchunk, sq)
+    dh = _dot(o["dh_part"].transpose(0, 2, 1), np.ones((1, 1, nchunk), dtype=ft), order)
+    s = _sigmoid(r)
+    o["dr"] = dh * s * (1 + r * (1 - s))
+    o["dm"] = _dot(o["dr"][:, None, :], w1.T[None], order)
+    o["pre_dx"] = dy * sig[..., None] + (o["dm"] / ft(HW))[..., None]
+    o["dx"] = rbf(o["pre_dx"])
+    src = o if fed is None else fed
+    de, h, dr, m = (c(np.asarray(src[k]).astype(np.float32)) for k in ("de", "h", "dr", "m"))
+    o.update(se_wgrad_reference(de, h, dr, m, ft, order))
+    return o
+
+
+def se_wgrad_reference(de, h, dr, m, ft=np.float64, order="pairwise"):
+    c = lambda a: np.asarray(a).astype(ft)  # noqa: E731
+    de, h, dr, m = c(de), c(h), c(dr), c(m)
+    one = np.ones((1, de.shape[0]), dtype=ft)
+    return dict(dw1=_dot(dr.T[:, None, :], m.T[None], order), db1=_dot(dr.T, one, order),
+                dw2=_dot(de.T[:, None, :], h.T[None], order), db2=_dot(de.T, one, order))
+
+
+def se_fwd_stages(ins, buf):
+    """name -> (exact, slack) of the forward's stages, each from the buffer before it in buf (m, r, h as the kernel
+    or an evaluation stored them): exact in fp64, slack the fp32 part of the bar. e: the hidden bf16(W2 h + b2)."""
+    x = ins["x"]
+    w1, b1, w2, b2 = se_weights(ins)
+    N, C, HW = x.shape
+    sq = w1.shape[0]
+    k = SE_ROOM * U24
+    m, r, h = (np.asarray(buf[n], dtype=np.float64) for n in ("m", "r", "h"))
+    out = {"m": (x.mean(axis=-1), k * se_d_m(HW) * np.abs(x).mean(axis=-1))}
+    out["r"] = (m @ w1.T + b1, k * se_d_r(C) * (np.abs(m) @ np.abs(w1).T + np.abs(b1)))
+    hx = r * _sigmoid(r)
+    out["h"] = (hx, k * (se_d_sigmoid(r) + 1) * np.abs(hx))
+    out["e"] = (h @ w2.T + b2, k * se_d_e(sq) * (np.abs(h) @ np.abs(w2).T + np.abs(b2)))
+    return out
+
+
+def se_sig_stage(e):
+    """(exact, slack) of sig given the bf16 value e."""
+    s = _sigmoid(np.asarray(e, dtype=np.float64))
+    return s, SE_ROOM * U24 * se_d_sigmoid(e) * s
+
+
+def se_ratio(got, exact, slack, bf16: bool, beyond: bool = False):
+    """|got - exact| over the bar, per element: the bar is slack, plus for a value stored rounded to bf16 half the
+    distance to got's bf16 neighbour on exact's side (either neighbour of a near-tie is admitted, nothing else).
+    beyond: what the error exceeds that half step by, over slack alone (the fp32 arithmetic's share of the bar: a
+    correctly rounded value sits at up to 1.0 of the whole bar, and at 0 of this)."""
+    got = np.asarray(got, dtype=np.float64)
+    half = bf16_half(got, exact) if bf16 else 0.0
+    err = np.abs(got - exact)
+    if beyond:
+        return np.maximum(err - half, 0.0) / np.maximum(slack, 1e-300)
+    return np.where(err == 0, 0.0, err / np.maximum(slack + half, 1e-300))
+
+
+def se_sig_ratio(got, e_exact, e_slack, beyond: bool = False):
+    """sig is admissible if it is for some bf16 e within its bar of the exact e: the candidates are the roundings of
+    the two ends of [e_exact - slack, e_exact + slack] (the slack is far below a bf16 step)."""
+    ratios = [se_ratio(got, *se_sig_stage(rbf(e_exact + d)), True, beyond) for d in (-e_slack, e_slack)]
+    return np.minimum(*ratios)
+
+
+def se_bwd_stages(ins, fed, buf):
+    """The backward's stages, chained like the forward's: t from dy and x; de from buf's t; dh_part and dr from its
+    de; dm from its dr; dx from its dm. fed: the reference whose r and sig lss_se_bwd was handed."""
+    x, dy = ins["x"], ins["dy"]
+    w1, _, w2, _ = se_weights(ins)
+    N, C, HW = x.shape
+    sq = w1.shape[0]
+    k = SE_ROOM * U24
+    r, sig = fed["r"].astype(np.float64), fed["sig"].astype(np.float64)
+    t, de, dr, dm = (np.asarray(buf[n], dtype=np.float64) for n in ("t", "de", "dr", "dm"))
+    out = {"t": ((dy * x).sum(axis=-1), k * se_d_t(HW) * np.abs(dy * x).sum(axis=-1))}
+    dex = t * sig * (1 - sig)
+    out["de"] = (dex, k * SE_D_DE * np.abs(dex))
+    nchunk = -(-C // 64)
+    dec = np.concatenate([de, np.zeros((N, nchunk * 64 - C))], axis=1).reshape(N, nchunk, 64)
+    w2c = np.concatenate([w2, np.zeros((nchunk * 64 - C, sq))]).reshape(nchunk, 64, sq)
+    out["dh_part"] = (np.einsum("nqc,qcj->nqj", dec, w2c), k * SE_D_DHP * np.einsum("nqc,qcj->nqj", np.abs(dec), np.abs(w2c)))
+    # dr = dh s F, F = 1 + r (1 - s), s = sigmoid(r) computed with relative error es = se_d_sigmoid(r) u:
+    # 1 - s errs by s es + u (1 - s) <= s es + u, the fma r (1 - s) + 1 adds u |F|, the two products 2 u:
+    # |d dr| <= |dh| (s |F| (es + 3 u) + s |r| (s es + u)), and dh's own error passes through |s F|
+    dh, dh_abs = de @ w2, np.abs(de) @ np.abs(w2)
+    s = _sigmoid(r)
+    F = 1 + r * (1 - s)
+    es = se_d_sigmoid(r)
+    out["dr"] = (dh * s * F, k * (se_d_dh(C) * dh_abs * np.abs(s * F)
+                                   + np.abs(dh) * (s * np.abs(F) * (es + 3) + s * np.abs(r) * (s * es + 1))))
+    out["dm"] = (dr @ w1, k * SE_D_DM * (np.abs(dr) @ np.abs(w1)))
+    b = dm / HW
+    dxx = dy * sig[..., None] + b[..., None]
+    out["dx"] = (dxx, k * (np.abs(b)[..., None] + np.abs(dxx)))
+    return out
+
+
+def se_wgrad_stages(de, h, dr, m):
+    """The four gradients from the fp32 de, h, dr, m lss_se_wgrad was handed."""
+    de, h, dr, m = (np.asarray(a, dtype=np.float64) for a in (de, h, dr, m))
+    k = SE_ROOM * U24 * de.shape[0]
+    return {"dw1": (dr.T @ m, k * (np.abs(dr).T @ np.abs(m))), "db1": (dr.sum(axis=0), k * np.abs(dr).sum(axis=0)),
+            "dw2": (de.T @ h, k * (np.abs(de).T @ np.abs(h))), "db2": (de.sum(axis=0), k * np.abs(de).sum(axis=0))}
+
+
+SE_FWD_BF16 = ("m", "r", "h")  # fp32 buffers that hold a bf16 value (and sig, checked through e)
+
+
+def se_rooms(ins, buf, fed, dh_part: bool = True):
+    """Largest |error| / bar of every buffer of one run (buf: name -> array; y and dx as fp64 of their bf16): under 1
+    everywhere is the test. y must equal bf16(x sig) of buf's own sig exactly: inf if any element differs."""
+    rooms = {}
+    f = se_fwd_stages(ins, buf)
+    for n in SE_FWD_BF16:
+        rooms[n] = float(se_ratio(buf[n], *f[n], True).max())
+    rooms["sig"] = float(se_sig_ratio(buf["sig"], *f["e"]).max())
+    y = rbf(np.asarray(buf["sig"], dtype=np.float64)[..., None] * ins["x"])
+    rooms["y"] = 0.0 if np.array_equal(y, np.asarray(buf["y"], dtype=np.float64)) else np.inf
+    b = se_bwd_stages(ins, fed, buf)
+    for n in ("t", "de", "dr", "dm") + (("dh_part",) if dh_part else ()):
+        rooms[n] = float(se_ratio(buf[n], *b[n], False).max())
+    rooms["dx"] = float(se_ratio(buf["dx"], *b["dx"], True).max())
+    # the bf16-valued buffers again, the half step taken off: the fp32 arithmetic's share (reported, implied by the above)
+    for n in SE_FWD_BF16:
+        rooms[n + ">half"] = float(se_ratio(buf[n], *f[n], True, beyond=True).max())
+    rooms["sig>half"] = float(se_sig_ratio(buf["sig"], *f["e"], beyond=True).max())
+    rooms["dx>half"] = float(se_ratio(buf["dx"], *b["dx"], True, beyond=True).max())
+    return rooms
+
+
+def se_wgrad_rooms(fed4, got):
+    st = se_wgrad_stages(*fed4)
+    return {n: float(se_ratio(got[n], *st[n], False).max()) for n in st}
+
+
+def se_wgrad_inputs(N: int, C: int, sq: int):
+    """de (N, C), h (N, sq), dr (N, sq), m (N, C) for lss_se_wgrad's own cases: fp32 values, h and m bf16 ones."""
+    rng = np.random.default_rng(SE_SEED + 31 * N + 7 * C + sq)
+    f32 = lambda a: a.astype(np.float32).astype(np.float64)  # noqa: E731
+    return (f32(rng.standard_normal((N, C))), rbf(rng.standard_normal((N, sq))), f32(rng.standard_normal((N, sq))),
+            rbf(rng.standard_normal((N, C))))

@@ -773,3 +773,172 @@ def test_bn_bars_notice_a_left_out_element_and_the_recompute_cap_holds():
                 near = A.bn_near_zero(ref, combo)
                 assert near.sum() <= A.BN_RECOMPUTE_CAP * near.size, (c, dt, int(near.sum()))
                 assert combo.y == "null" or not near.any()
+
+
+# ---- squeeze-excite (tests/arm_cases.py's SE section; tests/test_gpu_se_arms.py runs it on the GPU)
+def _se_arm(lib, pas, c, setting):
+    prev = lib.lss_se_tails(setting)
+    try:
+        a = _lib.SeArm()
+        assert lib.lss_se_arm(pas, c.N, c.C, c.HW, c.sq, ctypes.byref(a)) == 0, c
+    finally:
+        lib.lss_se_tails(prev)
+    return a
+
+
+def test_arm_table_covers_every_squeeze_excite_class():
+    lib = _lib.load()
+    up = lambda n, d: -(-n // d)  # noqa: E731
+    for pas in (A.SE_FWD, A.SE_BWD):
+        for setting in (A.SE_OFF, A.SE_DEFAULT, A.SE_FORCED):
+            hit = {}
+            for c in A.SE_CASES:
+                a = _se_arm(lib, pas, c, setting)
+                path, planes, ragged, one, chunk = A.se_class(pas, a)
+                axes = hit.setdefault(path, dict(planes=set(), one_block=set(), chunks=set()))
+                axes["planes"].add((planes, ragged))
+                axes["one_block"].add(one)
+                axes["chunks"].add(chunk)
+                # the report against the rule restated: the routing, the grids, the planes a wave, the chunks
+                limit = 4096 if pas == A.SE_BWD else 1024
+                tails = setting != A.SE_OFF and c.N <= A.SE_BANK_IMAGES and (setting == A.SE_FORCED or c.C * c.sq <= limit)
+                assert a.tails == int(tails) and a.launches == (2 if tails else 4), (c, pas, setting)
+                n4 = up(c.N * c.C * c.HW // 4, 256)
+                if tails:
+                    assert a.cpb % 16 == 0 and a.bpi == up(c.C, a.cpb) and a.bpi <= max(1, 512 // c.N), c
+                    assert (a.bpi - 1) * a.cpb < c.C and list(a.grid) == [c.N * a.bpi, n4, 0, 0], c
+                    last = c.C - (a.bpi - 1) * a.cpb
+                    assert (a.planes_max, a.planes_min) == (up(min(a.cpb, c.C), 16), last // 16), c
+                    assert a.w2_chunks == (0 if pas else up(c.C, min(1024, 16384 // (c.sq + 1)))), c
+                else:
+                    mid = [c.N * up(c.C, 64)] * 2 if pas else [c.N * up(c.sq, 4), c.N * up(c.C, 256)]
+                    assert list(a.grid) == [up(c.N * c.C, 4)] + mid + [n4] and (a.bpi, a.cpb) == (0, 0), c
+                    assert a.w2_chunks == (0 if pas else up(c.C, 256)), c
+                assert a.chunks64 == (up(c.C, 64) if pas else 0), c
+            if setting == A.SE_DEFAULT:  # either path, each within what the header enumerates
+                assert set(hit) == {"tails", "sequence"}
+                for path, axes in hit.items():
+                    want = A.se_classes(pas, path == "tails")
+                    assert all(axes[k] <= want[k] for k in want), (pas, path, axes)
+            else:  # one path (past the bank: the sequence), every class of it
+                path = "tails" if setting else "sequence"
+                want = A.se_classes(pas, setting != A.SE_OFF)
+                assert hit[path] == want, (pas, setting, {k: hit[path][k] ^ want[k] for k in want})
+                assert set(hit) == ({"tails", "sequence"} if setting else {"sequence"})
+    # each bound of the rule: its two neighbours are in the table and fall in different classes
+    for lo, hi, pas, setting in A.SE_BOUNDARIES:
+        a, b = (A.se_class(pas, _se_arm(lib, pas, A.se_case(n), setting)) for n in (lo, hi))
+        assert a != b, (lo, hi, a)
+    by = lambda f: {f(c) for c in A.SE_CASES}  # noqa: E731
+    assert {63, 64, 65, 192, 193, 256, 257, 1025, 2048} <= by(lambda c: c.C)
+    assert {1, 2, 3, 4, 5, 15, 16, 17, 63, 64} <= by(lambda c: c.sq)
+    assert {4, 8, 12, 252, 256, 260, 516} <= by(lambda c: c.HW) and max(by(lambda c: c.HW)) <= 516
+    assert any(c.C % 16 for c in A.SE_CASES) and {1, 15, 16, 17, 33} == {n for n, _, _ in A.SE_WGRAD_CASES}
+    for N, C, sq in A.SE_WGRAD_CASES:
+        assert (2 * C * sq + sq + C) % 256
+    assert any(2 * C * sq + sq + C <= 64 for _, C, sq in A.SE_WGRAD_CASES)  # one wave holds all four branches
+    assert all(A.se_case(n) for n in A.SE_AUTOGRAD) and len(A.SE_AUTOGRAD) == 3
+    # the query refuses what the entry points refuse
+    a = ctypes.byref(_lib.SeArm())
+    assert lib.lss_se_arm(0, 2, 8, 8, 2, a) == 0 and lib.lss_se_arm(1, 2, 2048, 4, 64, a) == 0
+    for bad in ((2, 2, 8, 8, 2), (-1, 2, 8, 8, 2), (0, 2, 8, 6, 2), (0, 2, 2049, 4, 2), (1, 2, 8, 8, 65), (0, 0, 8, 8, 2),
+                (1, 2, 8, 8, 0), (0, 2, 0, 8, 2), (0, 2, 8, 0, 2), (0, 1 << 15, 1 << 10, 1 << 6, 2)):
+        assert lib.lss_se_arm(*bad, a) == _EINVAL, bad
+    assert lib.lss_se_arm(0, 2, 8, 8, 2, None) == _EINVAL
+
+
+def _se_eval_rooms(ins, ref, got):
+    """|error| / bar of every stage of an evaluation that kept its values before the bf16 roundings: those are held
+    to the fp32 part of the bar alone."""
+    pre = lambda n, st: float((np.abs(got["pre_" + n].astype(np.float64) - st[0]) / st[1]).max())  # noqa: E731
+    f, b = A.se_fwd_stages(ins, got), A.se_bwd_stages(ins, ref, got)
+    r = {n: pre(n, f[n]) for n in ("m", "r", "h", "e")}
+    r["sig"] = pre("sig", A.se_sig_stage(got["e"]))
+    r.update({n: float(A.se_ratio(got[n], *b[n], False).max()) for n in ("t", "de", "dh_part", "dr", "dm")})
+    r["dx"] = pre("dx", b["dx"])
+    r.update(A.se_wgrad_rooms([ref[k].astype(np.float32) for k in ("de", "h", "dr", "m")], got))
+    return r
+
+
+def test_se_bars_leave_fp32_room_and_notice_a_left_out_term():
+    """On every case: (1) an fp32 numpy evaluation of the contract -- numpy's pairwise sums or one term after the
+    other, numpy's exp -- stays within a quarter of every bar, and passes the test the GPU buffers are put to; (2) the
+    fp64 reference itself passes it; (3) a value with one term left out does not: the last element of every plane in m
+    and t; per output the largest term of r (a channel), of e under sig (a j), of dh under dr (a channel), of dm (a j);
+    the image of the largest term in each of the four gradients."""
+    worst, shares = {}, []
+    for c in A.SE_CASES:
+        ins = A.se_inputs(c.N, c.C, c.HW, c.sq)
+        ref = A.se_reference(ins)
+        assert max(A.se_rooms(ins, ref, ref).values()) <= 1.0, c
+        for n in A.SE_FWD_BF16 + ("sig",):
+            assert np.array_equal(ref[n], ref[n].astype(np.float32)) and not (ref[n].astype(np.float32).view(np.uint32) & 0xFFFF).any()
+        for order in ("pairwise", "sequential"):
+            got = A.se_reference(ins, ft=np.float32, order=order, fed=ref)
+            for n, v in _se_eval_rooms(ins, ref, got).items():
+                worst[n] = max(worst.get(n, 0.0), v)
+                assert v <= 0.25, (c, order, n, v)
+            assert max(A.se_rooms(ins, got, ref).values()) <= 1.0, (c, order)
+        # ---- one term left out
+        x, dy = ins["x"], ins["dy"]
+        w1, b1, w2, b2 = A.se_weights(ins)
+        f, b = A.se_fwd_stages(ins, ref), A.se_bwd_stages(ins, ref, ref)
+        N, sq = c.N, c.sq
+        seen = lambda got, st, bf: A.se_ratio(got, *st, bf) > 1.0  # noqa: E731
+        assert seen(A.rbf(f["m"][0] - x[..., -1] / c.HW), f["m"], True).all(), (c, "m")
+        assert seen(b["t"][0] - (dy * x)[..., -1], b["t"], False).all(), (c, "t")
+        top = lambda terms: np.take_along_axis(terms, np.abs(terms).argmax(axis=-1)[..., None], -1)[..., 0]  # noqa: E731
+        assert seen(A.rbf(f["r"][0] - top(ref["m"][:, None, :] * w1[None])), f["r"], True).all(), (c, "r")
+        gone = top(ref["h"][:, None, :] * w2[None])
+        cut = A.rbf(A._sigmoid(A.rbf(f["e"][0] - gone)))
+        sig_seen = A.se_sig_ratio(cut, *f["e"]) > 1.0
+        # sig passes two bf16 roundings (e, then sig): a term shows for certain once it moves e by more than a bf16
+        # step of e and, through the sigmoid's smallest slope on the way, sig by more than a bf16 step of sig
+        ends = np.stack([f["e"][0], f["e"][0] - gone])
+        step_e = 4 * A.bf16_half(A.rbf(np.abs(ends).max(axis=0)), np.inf)
+        ends = np.concatenate([ends - step_e, ends + step_e])
+        sg = A._sigmoid(ends)
+        must = (sg * (1 - sg)).min(axis=0) * (np.abs(gone) - step_e) > 4 * A.bf16_half(A.rbf(sg.max(axis=0)), np.inf)
+        assert sig_seen[must].all() and must.mean() >= 0.5, (c, "sig", must.mean(), sig_seen.mean())
+        shares.append((A.se_id(c), round(float(must.mean()), 3), round(float(sig_seen.mean()), 3)))
+        s = A._sigmoid(ref["r"])
+        slope = s * (1 + ref["r"] * (1 - s))
+        assert seen(b["dr"][0] - top(ref["de"][:, None, :] * w2.T[None]) * slope, b["dr"], False).all(), (c, "dr")
+        assert seen(b["dm"][0] - top(ref["dr"][:, None, :] * w1.T[None]), b["dm"], False).all(), (c, "dm")
+        fed4 = [ref[k].astype(np.float32).astype(np.float64) for k in ("de", "h", "dr", "m")]
+        st = A.se_wgrad_stages(*fed4)
+        de, h, dr, m = fed4
+        terms = {"dw1": dr.T[:, None, :] * m.T[None], "db1": dr.T, "dw2": de.T[:, None, :] * h.T[None], "db2": de.T}
+        for n, term in terms.items():
+            # (a sum of N terms in sequence is allowed SE_ROOM N u of its summands: one of N equal terms shows while
+            # SE_ROOM N^2 u < 1, N < 2048. The two cases at the counter bank's limit cannot shrink below 4096.)
+            gone = top(term)  # (0 where a pooled mean of four is exactly 0: nothing to notice)
+            assert (seen(st[n][0] - gone, st[n], False) | (gone == 0)).all() or c.N >= A.SE_BANK_IMAGES, (c, n)
+    for N, C, sq in A.SE_WGRAD_CASES:
+        fed4 = A.se_wgrad_inputs(N, C, sq)
+        st = A.se_wgrad_stages(*fed4)
+        for order in ("pairwise", "sequential"):
+            got = A.se_wgrad_reference(*fed4, ft=np.float32, order=order)
+            for n in st:
+                assert float(A.se_ratio(got[n], *st[n], False).max()) <= 0.25, (N, C, sq, order, n)
+    print({k: round(v, 3) for k, v in worst.items()}, shares)
+
+
+def test_se_reference_is_squeeze_excite():
+    """arm_cases.se_reference against the stock ops + autograd in fp64: the bf16 roundings move values by up to
+    2^-8 relative, so this pins the formulas, not the bits."""
+    import torch.nn.functional as Fn
+    for note in A.SE_AUTOGRAD + ("C 65, sq 5",):
+        c = A.se_case(note)
+        ins = A.se_inputs(c.N, c.C, c.HW, c.sq)
+        ref = A.se_reference(ins)
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a))  # noqa: E731
+        x = t(ins["x"]).reshape(c.N, c.C, c.HW, 1).requires_grad_(True)
+        w1, b1, w2, b2 = (t(w).requires_grad_(True) for w in A.se_weights(ins))
+        hid = Fn.silu(Fn.conv2d(Fn.adaptive_avg_pool2d(x, 1), w1.reshape(c.sq, c.C, 1, 1), b1))
+        y = x * torch.sigmoid(Fn.conv2d(hid, w2.reshape(c.C, c.sq, 1, 1), b2))
+        y.backward(t(ins["dy"]).reshape(x.shape))
+        for got, want in ((ref["y"], y.detach().reshape(c.N, c.C, c.HW)), (ref["dx"], x.grad.reshape(c.N, c.C, c.HW)),
+                          (ref["dw1"], w1.grad), (ref["db1"], b1.grad), (ref["dw2"], w2.grad), (ref["db2"], b2.grad)):
+            want = want.numpy()
+            assert np.abs(got - want).max() <= 2e-2 * np.abs(want).max(), (note, np.abs(got - want).max())

@@ -245,8 +245,9 @@ def test_ctypes_record_matches_the_header():
     rec = simbev.photo_record(1.0, 1.1, 0.9, 3.0, 2.5, 0xDEADBEEF, 0x7FC00001)  # (a NaN's bits survive as a seed)
     p = P.from_buffer_copy(rec.tobytes())
     assert p.noise == 2.5 and list(p.seed) == [0xDEADBEEF, 0x7FC00001] and p.pad == 0
-    assert _lib.ABI_VERSION == 36
-    assert re.search(r"#define LSS_ABI_VERSION 36\b", open(os.path.join(REPO, "include", "lss_hip.h")).read())
+    assert _lib.ABI_VERSION >= 36  # the ABI that added the record; later ABIs keep it
+    assert re.search(r"#define LSS_ABI_VERSION %d\b" % _lib.ABI_VERSION,
+                     open(os.path.join(REPO, "include", "lss_hip.h")).read())
 
 
 # ----------------------------------------------------------------------------- command lines

@@ -68,6 +68,39 @@ def cumsum_trick(x, geom_feats, ranks):
 
 
 # ----------------------------------------------------------------------------- loss / metrics
+def _fused_loss(ctx, x, entry: str, head, tail, scaled: bool = False):
+    """What the fused training losses share. Allocates the block partials, the loss scalar and the stored gradient,
+    runs ``entry(x, dtype, *head, n, *tail, partial, loss, [scale,] grad, stream)`` (include/lss_convs.h) and saves
+    the gradient for _stored_grad_backward -- `scaled`: with the device scalar n / max(M, 1) the entry's fold writes,
+    and a second row of partials for its per-block counts."""
+    from . import _lib
+    lib = _lib.load()
+    n = x.numel()
+    partial = torch.empty((2 if scaled else 1) * int(lib.lss_bce_partials(n)), device=x.device, dtype=torch.float32)
+    loss = torch.empty((), device=x.device, dtype=torch.float32)
+    scale = (torch.empty((), device=x.device, dtype=torch.float32),) if scaled else ()
+    grad = torch.empty_like(x)
+    _lib.check(getattr(lib, entry)(_lib.ptr(x), _lib.dtype_code(x.dtype), *head, n, *tail, _lib.ptr(partial),
+                                   _lib.ptr(loss), *(_lib.ptr(v) for v in scale), _lib.ptr(grad),
+                                   _lib.stream_handle(x.device)), entry)
+    ctx.save_for_backward(grad, *scale)
+    return loss
+
+
+def _stored_grad_backward(ctx, g) -> torch.Tensor:
+    """dx = the stored gradient times the incoming one (read on the device): ``lss_bce_logits_bwd``, or, when a scale
+    was saved beside the gradient, ``lss_seg_loss_masked_bwd``, which multiplies by it too."""
+    from . import _lib
+    grad, *scale = ctx.saved_tensors
+    g = g.float().contiguous()
+    dx = torch.empty_like(grad)
+    entry = "lss_seg_loss_masked_bwd" if scale else "lss_bce_logits_bwd"
+    _lib.check(getattr(_lib.load(), entry)(_lib.ptr(grad), _lib.dtype_code(grad.dtype), grad.numel(), _lib.ptr(g),
+                                           *(_lib.ptr(v) for v in scale), _lib.ptr(dx),
+                                           _lib.stream_handle(grad.device)), entry)
+    return dx
+
+
 class _BceLogits(torch.autograd.Function):
     """BCEWithLogitsLoss(pos_weight), mean, on ``lss_bce_logits`` (include/lss_convs.h): the loss and
     its input gradient in one pass plus a fixed-order fold of the block sums -- two launches where
@@ -77,33 +110,23 @@ class _BceLogits(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, target, pos_weight: float):
         from . import _lib
-        lib = _lib.load()
-        n = x.numel()
-        partial = torch.empty(int(lib.lss_bce_partials(n)), device=x.device, dtype=torch.float32)
-        loss = torch.empty((), device=x.device, dtype=torch.float32)
-        grad = torch.empty_like(x)
-        _lib.check(lib.lss_bce_logits(_lib.ptr(x), _lib.dtype_code(x.dtype), _lib.ptr(target), n, float(pos_weight),
-                                      _lib.ptr(partial), _lib.ptr(loss), _lib.ptr(grad),
-                                      _lib.stream_handle(x.device)), "lss_bce_logits")
-        ctx.save_for_backward(grad)
-        return loss
+        return _fused_loss(ctx, x, "lss_bce_logits", (_lib.ptr(target),), (float(pos_weight),))
 
     @staticmethod
     def backward(ctx, g):
-        from . import _lib
-        (grad,) = ctx.saved_tensors
-        g = g.float().contiguous()
-        dx = torch.empty_like(grad)
-        _lib.check(_lib.load().lss_bce_logits_bwd(_lib.ptr(grad), _lib.dtype_code(grad.dtype), grad.numel(),
-                                                  _lib.ptr(g), _lib.ptr(dx), _lib.stream_handle(grad.device)),
-                   "lss_bce_logits_bwd")
-        return dx, None, None
+        return _stored_grad_backward(ctx, g), None, None
 
 
 def is_scalar_weight(w) -> bool:
     """One pos_weight for every class (a number, a numpy scalar or a 0-d tensor: what float() took before
     per-class weights existed), as opposed to a sequence / tensor of K."""
     return isinstance(w, (int, float)) or getattr(w, "ndim", None) == 0
+
+
+def _class_plane(x, K: int) -> tuple:
+    """(plane, K) as the per-class entries take them, for (N, K, ...) logits: plane = the elements of one class of one
+    sample."""
+    return x.numel() // (x.shape[0] * K), K
 
 
 class _BceLogitsPerClass(torch.autograd.Function):
@@ -113,22 +136,12 @@ class _BceLogitsPerClass(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, target, pos_weight: torch.Tensor):
         from . import _lib
-        lib = _lib.load()
-        n = x.numel()
-        K = x.shape[1]
-        partial = torch.empty(int(lib.lss_bce_partials(n)), device=x.device, dtype=torch.float32)
-        loss = torch.empty((), device=x.device, dtype=torch.float32)
-        grad = torch.empty_like(x)
-        _lib.check(lib.lss_bce_logits_pc(_lib.ptr(x), _lib.dtype_code(x.dtype), _lib.ptr(target), n,
-                                         n // (x.shape[0] * K), K, _lib.ptr(pos_weight), _lib.ptr(partial),
-                                         _lib.ptr(loss), _lib.ptr(grad), _lib.stream_handle(x.device)),
-                   "lss_bce_logits_pc")
-        ctx.save_for_backward(grad)
-        return loss
+        return _fused_loss(ctx, x, "lss_bce_logits_pc", (_lib.ptr(target),),
+                           (*_class_plane(x, x.shape[1]), _lib.ptr(pos_weight)))
 
     @staticmethod
     def backward(ctx, g):
-        return _BceLogits.backward(ctx, g)
+        return _stored_grad_backward(ctx, g), None, None
 
 
 def masked_mean_loss(x: torch.Tensor, target: torch.Tensor, valid: torch.Tensor, params: torch.Tensor):
@@ -177,30 +190,12 @@ class _SegLossMasked(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, target, valid, params: torch.Tensor):
         from . import _lib
-        lib = _lib.load()
-        n = x.numel()
-        K = params.shape[0]
-        partial = torch.empty(2 * int(lib.lss_bce_partials(n)), device=x.device, dtype=torch.float32)
-        loss = torch.empty((), device=x.device, dtype=torch.float32)
-        scale = torch.empty((), device=x.device, dtype=torch.float32)
-        grad = torch.empty_like(x)
-        _lib.check(lib.lss_seg_loss_masked(_lib.ptr(x), _lib.dtype_code(x.dtype), _lib.ptr(target), _lib.ptr(valid), n,
-                                           n // (x.shape[0] * K), K, _lib.ptr(params), _lib.ptr(partial),
-                                           _lib.ptr(loss), _lib.ptr(scale), _lib.ptr(grad),
-                                           _lib.stream_handle(x.device)), "lss_seg_loss_masked")
-        ctx.save_for_backward(grad, scale)
-        return loss
+        return _fused_loss(ctx, x, "lss_seg_loss_masked", (_lib.ptr(target), _lib.ptr(valid)),
+                           (*_class_plane(x, params.shape[0]), _lib.ptr(params)), scaled=True)
 
     @staticmethod
     def backward(ctx, g):
-        from . import _lib
-        grad, scale = ctx.saved_tensors
-        g = g.float().contiguous()
-        dx = torch.empty_like(grad)
-        _lib.check(_lib.load().lss_seg_loss_masked_bwd(_lib.ptr(grad), _lib.dtype_code(grad.dtype), grad.numel(),
-                                                       _lib.ptr(g), _lib.ptr(scale), _lib.ptr(dx),
-                                                       _lib.stream_handle(grad.device)), "lss_seg_loss_masked_bwd")
-        return dx, None, None, None
+        return _stored_grad_backward(ctx, g), None, None, None
 
 
 def _masked_loss(ypred, ytgt, valid, params: torch.Tensor):
@@ -326,22 +321,12 @@ class _FocalLogits(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, target, params: torch.Tensor):
         from . import _lib
-        lib = _lib.load()
-        n = x.numel()
-        K = params.shape[0]
-        partial = torch.empty(int(lib.lss_bce_partials(n)), device=x.device, dtype=torch.float32)
-        loss = torch.empty((), device=x.device, dtype=torch.float32)
-        grad = torch.empty_like(x)
-        _lib.check(lib.lss_focal_logits_pc(_lib.ptr(x), _lib.dtype_code(x.dtype), _lib.ptr(target), n,
-                                           n // (x.shape[0] * K), K, _lib.ptr(params), _lib.ptr(partial),
-                                           _lib.ptr(loss), _lib.ptr(grad), _lib.stream_handle(x.device)),
-                   "lss_focal_logits_pc")
-        ctx.save_for_backward(grad)
-        return loss
+        return _fused_loss(ctx, x, "lss_focal_logits_pc", (_lib.ptr(target),),
+                           (*_class_plane(x, params.shape[0]), _lib.ptr(params)))
 
     @staticmethod
     def backward(ctx, g):
-        return _BceLogits.backward(ctx, g)
+        return _stored_grad_backward(ctx, g), None, None
 
 
 def _per_class(value, K: int, name: str) -> list:
@@ -703,8 +688,7 @@ class _SoftmaxCe(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        dx, _, _, _ = _SegLossMasked.backward(ctx, g)
-        return dx, None, None, None
+        return _stored_grad_backward(ctx, g), None, None, None
 
 
 def softmax_ce_arm(x: torch.Tensor, labels: torch.Tensor, valid=None, grad=None) -> int:

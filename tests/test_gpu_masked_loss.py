@@ -3,7 +3,8 @@
 
 Loss shapes: (3, 3, 5, 7) -- 315 elements: one block with a tail vector, plane 35: a thread's 8 elements cross class
 planes and samples, and the mask is read a byte at a time -- and (2, 3, 20, 20): two blocks, plane 400: the mask is
-read 8 bytes at a time. fp32 and bf16 logits; rows: gamma 0 (BCE with pw 2.13), gamma 2 with alpha rows, gamma 0.5.
+read 8 bytes at a time -- and (2, 3, 19, 21): two blocks with a ragged last vector (2394 elements), plane 399: threads
+cross class planes beyond the first block and the mask index steps back mid-thread. fp32 and bf16 logits; rows: gamma 0 (BCE with pw 2.13), gamma 2 with alpha rows, gamma 0.5.
 Reference: the fp64 restatement of tests/valid_mask_cases.py. Bars: those tests/test_gpu_focal_loss.py holds the
 unmasked kernel to against the same closed form -- loss rtol 2e-6 / atol 1e-7; fp32 gradient rtol max(1e-5, 4 r32),
 atol 1e-12; bf16 gradient 8e-3. Each case prints its measured errors."""
@@ -23,7 +24,7 @@ from lss_carla_amd import _lib, tools as T  # noqa: E402
 from lss_carla_amd.predict import threshold_logit  # noqa: E402
 
 DEV = torch.device("cuda:0")
-SHAPES = [(3, 3, 5, 7), (2, 3, 20, 20)]
+SHAPES = [(3, 3, 5, 7), (2, 3, 20, 20), (2, 3, 19, 21)]
 DTYPES = [torch.float32, torch.bfloat16]
 ROWS = {"bce": [(2.13, 1.0, 0.0)] * 3, "focal2": [(0.25, 0.75, 2.0), (0.5, 0.5, 2.0), (0.75, 0.25, 2.0)],
         "focal05": C.rows(3, 0.5)}
@@ -313,6 +314,35 @@ def test_all_ones_mask_reproduces_the_unmasked_counts(shape, dtype):
     a, b = a.cpu().tolist(), b.cpu().tolist()
     assert a[1:] == b[1:] and cells.item() == (B - 1) * shape[2] * shape[3]
     assert a[0] == pytest.approx(b[0], rel=1e-12)  # nv * S / M with M = nv K plane is S / (K plane)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["fp32", "bf16"])
+def test_masked_metrics_of_misaligned_logits(dtype):
+    """Logits that start one element into a larger buffer (contiguous, off every 16-byte boundary): the entry takes
+    the guarded element loads for the whole call. Counts, cells and loss against the restatements above."""
+    shape, ladder = (3, 3, 5, 5), [0.35, 0.5, 0.65]
+    B, K = shape[:2]
+    x, t = C.data(shape, dtype, seed=14)
+    valid = _mask(shape, seed=15)
+    buf = torch.zeros(x.numel() + 1, device=DEV, dtype=dtype)
+    buf[1:] = x.to(DEV).view(-1)
+    xm = buf[1:].view(shape)
+    assert xm.is_contiguous() and xm.data_ptr() % 16 != 0
+    params = torch.tensor(ROWS["focal05"], device=DEV)
+    th = torch.tensor([threshold_logit(v) for v in ladder], device=DEV, dtype=torch.float32)
+    for nv in (B, 2):
+        totals = torch.zeros(1 + K + 2 * K * 3, device=DEV, dtype=torch.float64)
+        cells = torch.zeros(1, device=DEV, dtype=torch.float64)
+        n_valid = torch.tensor([nv], device=DEV, dtype=torch.int32)
+        T.seg_metrics_accumulate(xm, t.to(DEV), totals, n_valid, params, th, valid=valid.to(DEV), valid_cells=cells)
+        want, m = _metrics_ref(x, t, valid, params.cpu().tolist(), th.cpu().tolist(), nv)
+        got = totals.cpu().tolist()
+        assert got[1:] == [float(v) for v in want[1:]] and cells.item() == float(m)
+        S = _device_term_sum(x, t, valid, params.cpu().tolist(), nv)
+        print(f"{dtype} nv {nv}: loss total {got[0]:.12e} want {want[0]:.12e} device terms {nv * S / max(m * K, 1):.12e}")
+        assert got[0] == pytest.approx(nv * S / max(m * K, 1), rel=1e-12)
+        assert got[0] == pytest.approx(want[0], rel=C.LOSS_RTOL, abs=C.LOSS_ATOL)
+        assert m > 0 and sum(want[1:]) > 0
 
 
 def test_metrics_entry_refuses_bad_arguments():

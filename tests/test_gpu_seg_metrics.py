@@ -126,6 +126,31 @@ def test_gamma_zero_and_theta_zero_are_the_bce_entry(shape, dtype):
         assert sum(a[1 + K:]) > 0
 
 
+@pytest.mark.parametrize("dtype", DTYPES, ids=["fp32", "bf16"])
+def test_misaligned_logits_are_read_an_element_at_a_time(dtype):
+    """Logits that start one element into a larger buffer (contiguous, off every 16-byte boundary): the entry takes
+    the guarded element loads for the whole call. Counts and loss against the reference above."""
+    shape, Tn = (3, 3, 5, 5), 7
+    B, K = shape[:2]
+    x, t = C.data(shape, dtype, seed=6)
+    x = x / 4
+    buf = torch.zeros(x.numel() + 1, device=DEV, dtype=dtype)
+    buf[1:] = x.to(DEV).view(-1)
+    xm = buf[1:].view(shape)
+    assert xm.is_contiguous() and xm.data_ptr() % 16 != 0
+    thetas, rows = _thetas(_ladder(Tn)), _rows(K)
+    for nv in (1, B, None):
+        want = _reference(x, t, B if nv is None else nv, rows.tolist(), thetas)
+        n_valid = None if nv is None else torch.tensor([nv], device=DEV, dtype=torch.int32)
+        totals = torch.zeros(1 + K + 2 * K * Tn, device=DEV, dtype=torch.float64)
+        T.seg_metrics_accumulate(xm, t.to(DEV), totals, n_valid, rows.to(DEV), thetas.to(DEV))
+        got = totals.tolist()
+        print(f"{dtype} nv {nv}: loss {got[0]:.12e} fp64 {want[0]:.12e}")
+        assert got[0] == pytest.approx(want[0], rel=RTOL, abs=ATOL)
+        assert got[1:] == want[1:]
+    assert sum(want[1 + K:1 + K + K * Tn]) > 0
+
+
 def test_captured_accumulate_follows_n_valid():
     B, K, Tn = 3, 3, 7
     x, t = C.data((B, K, 30, 30), torch.bfloat16, seed=5)
